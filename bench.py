@@ -8,6 +8,11 @@ bench contract); `value_host_frames`: the same run with host buffers handed over
 PCIe upload inside the timed region.  `configs`: the other single-GPU configurations of BASELINE.json (1280x720 x 300 frames,
 3840x2160 x 16 frames) measured by the same process, outside the timed region.
 
+A plain run sets up, warms up, times --steps steps and prints the line (`value`, `ms_per_step`, the roofline figures read from the
+detector's own counters).  Everything else - the sequential verification pass, the host-frames passes, `configs`, the CPU baseline
+and the reference on the box's OpenCL device - runs only with --full.  --dump-outputs DIR writes the rectangle lists of the last
+timed step (rank 0) as DIR/*.npy in float64, so that two builds can be compared output for output.
+
 Prints ONE JSON line on rank 0.  Multi-GPU: launched by torch.distributed.run, one rank per GPU, no data-path
 collective (frames are independent); only a barrier, a MAX-reduce of the elapsed time and a gather of a few bytes per rank,
 over gloo (host side: no RCCL communicator and no extra stream on the device the detector is saturating).
@@ -293,6 +298,28 @@ def _api_detector(rect_detector):
     return ctypes.cast(rect_detector.h + 8, ctypes.POINTER(ctypes.c_void_p))[0]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+RECT_COLUMNS = ["c2_%d%s" % (i, a) for i in range(4) for a in "xy"] + ["c3_%d%s" % (i, a) for i in range(4) for a in "xyz"] + ["value", "status"]
+
+
+def dump_outputs(outdir, lists):
+    """The rectangle lists of the frames of one step, as a caller of the timed path receives them (poll() -> RECT_DTYPE), in float64 (exact for
+    the f64 fields and the u32 status): rects.npy (rectangles of all frames in stream order, one row of RECT_COLUMNS each) and rects_per_frame.npy.
+    Past DUMP_LIMIT_BYTES a fixed, seeded sample of the rows is written, with the rows' indices in rects_rows.npy."""
+    os.makedirs(outdir, exist_ok=True)
+    counts = np.array([len(r) for r in lists], np.float64)
+    rects = np.concatenate([np.ascontiguousarray(r) for r in lists]) if lists else np.zeros(0, dtype=np.dtype([("c2", "<f8", (4, 2)), ("c3", "<f8", (4, 3)), ("value", "<f8"), ("status", "<u4")]))
+    rows = np.concatenate([rects["c2"].reshape(-1, 8), rects["c3"].reshape(-1, 12), rects["value"].reshape(-1, 1), rects["status"].astype(np.float64).reshape(-1, 1)], axis=1)
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    if rows.nbytes + counts.nbytes + 4096 > DUMP_LIMIT_BYTES:      # (4096: the .npy headers)
+        max_rows = (DUMP_LIMIT_BYTES - counts.nbytes - 4096) // (rows.shape[1] * 8 + 8)      # (each row kept has its index in rects_rows.npy)
+        keep = np.sort(np.random.default_rng(0).choice(len(rows), size=max_rows, replace=False))
+        rows = rows[keep]
+        np.save(os.path.join(outdir, "rects_rows.npy"), keep.astype(np.float64))
+    np.save(os.path.join(outdir, "rects.npy"), rows)
+    np.save(os.path.join(outdir, "rects_per_frame.npy"), counts)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -302,10 +329,13 @@ def main():
     ap.add_argument("--slots", type=int, default=64, help="frames in flight per GPU (from three on: one stream per frame on four shared streams; from 6 / 12 / 32 on: groups of 2 / 4 / 8 frames per set of launches; 64 = two groups queued on each of the four streams, so that a stream never waits for the host to collect a group and hand over the next; 48 / 64 / 96 / 128 measured 2706-2717 / 2764-2782 / 2753-2754 / 2783-2810 frames/s on one box in round 5)")
     ap.add_argument("--host-frames", action="store_true", help="hand over host buffers (PCIe upload inside the timed region); not the headline value")
     ap.add_argument("--host-mode", default="pageable", choices=["pageable", "pinned"], help="with --host-frames (profiling runs): pageable buffers, copied by the caller's thread first, or pinned ones, read in place")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="profiling runs only: skip the sequential verification pass and the host-frames pass (the line then says outputs_verified: null)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline value does not need: the sequential verification pass, the host-frames passes, "
+                                                       "the 1280x720 / 3840x2160 / reference-API configurations, the CPU baseline and the reference on the OpenCL device")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the rectangle lists of the last timed step (rank 0) to DIR/*.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the reference on the OpenCL device")
+    ap.add_argument("--no-verify", action="store_true", help="with --full: skip the sequential verification pass, the host-frames passes and the configurations (the line then says outputs_verified: null)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: exercises sharding/aggregation only (CPU tests)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the side measurements of the 1280x720 and 3840x2160 configurations")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the side measurements of the 1280x720 and 3840x2160 configurations")
     ap.add_argument("--share-gpus", action="store_true", help="tests on a one-GPU box only: ranks beyond the device count share devices (rank mod count); without it more ranks than devices is an error")
     ap.add_argument("--frame", default=None, help="profiling runs only: another frame size than the headline's, e.g. 1280x720 or 3840x2160 (the line's metric then names that size); "
                                                   "the driver's line is always 1920x1080")
@@ -442,13 +472,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
         dist.barrier()
+    if args.dump_outputs and rank == 0 and det is not None:
+        dump_outputs(args.dump_outputs, results[-F:])
 
-    # (1) EVERY rank checks its timed run's outputs against a plain sequential pass over its own stream (one frame in flight, no worker threads,
+    # (1) with --full, EVERY rank checks its timed run's outputs against a plain sequential pass over its own stream (one frame in flight, no worker threads,
     #     post-process inline), outside the timed region: a run that returned garbage on any GPU cannot print a valid line
     digest = lambda lists: zlib.crc32(b"".join(np.ascontiguousarray(r).tobytes() for r in lists)) & 0xFFFFFFFF
     verify = None
     rho = None
-    if det is not None and not args.no_verify:
+    if det is not None and args.full and not args.no_verify:
         timed_lists = results[args.warmup * F:]
         nrect = int(sum(len(r) for r in timed_lists))
         chk = ra.Detector(IW, IH, device=dev, nslots=1, nworkers=0)
@@ -556,7 +588,7 @@ def main():
                          "frames_per_launch_budget": {str(8 + 2 * k): ra.lib().rd_detector_counter(det.h, 20 + k) for k in range(7)} if det is not None else None,
                          "frames_repeated": {"round_budget": det.region_round_budget()[1], "polyline_overflow": det.redone_frames(), "absorption_slow_path": det.absorption()[2]} if det is not None else None},
         }
-        if det is not None and world == 1 and not args.no_configs and not args.no_verify:
+        if det is not None and world == 1 and args.full and not args.no_configs and not args.no_verify:
             # BASELINE.json configs[2] and configs[3] (configs[1], the 1920x1080 still, is a frame of the headline stream), outside the timed region - each
             # configuration alone on the device, as it would run: the headline's detector (its 64 slots of planes, its worker threads) is closed first
             det.close()
@@ -568,7 +600,7 @@ def main():
                               side_config(ra, L, "vidrect 3840x2160 synthetic stream, 16 frames resident (BASELINE.json configs[3])", 3840, 2160, 4, 16, min(args.slots, 16), dev)]
             out["configs"] += reference_api_config(ra, frames, dev)
         out.update(verify or {"outputs_verified": None})
-        if not args.dry_run and not args.no_cpu_baseline and world == 1:
+        if args.full and not args.dry_run and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
             out["reference_opencl_same_gpu"] = reference_opencl_baseline()
         if args.dry_run:

@@ -112,3 +112,33 @@ def test_ranks_of_different_gpus_pin_to_different_cores(tmp_path):
             assert used is not None and os.sched_getaffinity(0) == set(mine)
         finally:
             os.sched_setaffinity(0, before)
+
+
+def test_dump_outputs_writes_float64_lists_within_the_limit(tmp_path):
+    """bench.py --dump-outputs: the rectangle lists of a step as float64 rows (c2, c3, value, status) with a count per frame; past the size limit a fixed,
+    seeded sample of the rows and their indices, the same from run to run"""
+    import importlib.util
+    import numpy as np
+    from rectdetect_amd import RECT_DTYPE
+    spec = importlib.util.spec_from_file_location("bench_for_test", os.path.join(helpers.ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(5)
+    lists = []
+    for n in (3, 0, 7, 2):
+        r = np.zeros(n, RECT_DTYPE)
+        r["c2"], r["c3"], r["value"], r["status"] = rng.random((n, 4, 2)), rng.random((n, 4, 3)), rng.random(n), rng.integers(0, 2**32, n, dtype=np.uint32)
+        lists.append(r)
+    bench.dump_outputs(str(tmp_path / "all"), lists)
+    rows, counts = np.load(tmp_path / "all" / "rects.npy"), np.load(tmp_path / "all" / "rects_per_frame.npy")
+    assert rows.dtype == np.float64 and counts.tolist() == [3, 0, 7, 2] and rows.shape == (12, len(bench.RECT_COLUMNS))
+    cat = np.concatenate(lists)
+    assert np.array_equal(rows[:, :8], cat["c2"].reshape(-1, 8)) and np.array_equal(rows[:, 8:20], cat["c3"].reshape(-1, 12))
+    assert np.array_equal(rows[:, 20], cat["value"]) and np.array_equal(rows[:, 21].astype(np.uint32), cat["status"])
+    assert not (tmp_path / "all" / "rects_rows.npy").exists()
+    bench.DUMP_LIMIT_BYTES = 4096 + 4 * 8 + (22 * 8 + 8) * 5      # room for 5 of the 12 rows and their indices
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / ("s%d" % k)), lists)
+    a, b = (np.load(tmp_path / d / "rects.npy") for d in ("s0", "s1"))
+    keep = np.load(tmp_path / "s0" / "rects_rows.npy")
+    assert a.shape == (5, 22) and np.array_equal(a, b) and np.array_equal(a, rows[keep.astype(int)])

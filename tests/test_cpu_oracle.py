@@ -148,24 +148,24 @@ def test_post_process_with_helper_threads_returns_the_same_bytes():
     assert not bad
 
 
-@pytest.mark.ref
 def test_oracle_against_live_reference_new_seed():
-    """where the reference build exists: a seed that has no golden file, compared plane by plane"""
+    """a seed that has no other golden file, compared plane by plane with what the reference computed for it (tests/golden/ref_checks.npz,
+    tools/make_golden_refchecks.py: the reference build oracle/_ref run on this frame)"""
+    g = golden("ref_checks")
     iw, ih = 320, 240
     img = synth.frame(synth.SEED0 + 11, iw, ih, 3)
-    r = helpers.RefRect(iw, ih)
-    names = ["plab0", "Lblur", "plab1", "vxy", "strength", "nms", "tidy", "str_sum", "smooth", "quant", "strong", "mergemask", "region", "boundary", "lsid", "table"]
-    rects, snaps = r.execute_once(img, 0.7, snapshots=names + ["lslist"])
-    r.close()
+    assert crc(img) == int(g["new_seed_input_crc"])
+    names = [str(p) for p in g["new_seed_planes"]]
+    assert names == ["plab0", "Lblur", "plab1", "vxy", "strength", "nms", "tidy", "str_sum", "smooth", "quant", "strong", "mergemask", "region", "boundary", "lsid", "table"]
     orc = helpers.OracleRect(iw, ih)
     orc.frame(img)
     N = iw * ih
     sizes = {"vxy": 2 * N, "table": (N * 4 // 5) * 5}
-    for p in names:
+    for p, want in zip(names, g["new_seed_plane_crc"]):
         k = sizes.get(p, N)
-        assert np.array_equal(orc.plane(p).view(np.uint32)[:k], snaps[p][:k]), p
+        assert crc(orc.plane(p).view(np.uint32)[:k]) == int(want), p
     mine = ra.postprocess_planes(orc.segments(), orc.plane("boundary"), orc.plane("table"), iw, ih, 0.7)
-    assert helpers.rects_equal(mine, rects)
+    assert helpers.rects_equal(mine, g["new_seed_rects"])
     orc.close()
 
 
@@ -327,58 +327,55 @@ def test_region_spec_stage_relations(iw, ih, seed):
     orc.close()
 
 
-@pytest.mark.ref
 @pytest.mark.parametrize("iw,ih,seed,nframes", [(333, 217, 2, 2), (640, 480, 0, 2)])
 def test_concurrent_merge_restatement_equals_the_references_own_kernel(iw, ih, seed, nframes):
     """pins rdo_region_concurrent: the reference itself (oracle/_ref: its kernels and host code) with the work-items of labelMergeMain
     running concurrently (rdcl_set_order group order 5: every work-item reads the labels the launch began with, the atomic minima take
     effect together) against the oracle in REGION_REFERENCE_CONCURRENT mode - region, size and boundary planes and the rectangle list,
-    bit for bit, on consecutive frames (the state carried from frame to frame included)"""
-    import ctypes
-    R = helpers.ref()
-    R.rdcl_set_order.argtypes = [ctypes.c_char_p] + [ctypes.c_int] * 4
+    bit for bit, on consecutive frames (the state carried from frame to frame included).  What the reference computed is stored in
+    tests/golden/ref_checks.npz (tools/make_golden_refchecks.py)."""
+    g = golden("ref_checks")
+    case = "merge_%dx%d_s%d_n%d" % (iw, ih, seed, nframes)
     tan = float(np.tan(36.0 / 180.0 * np.pi))
-    r = helpers.RefRect(iw, ih)
     orc = helpers.OracleRect(iw, ih, helpers.REGION_REFERENCE_CONCURRENT)
     try:
-        R.rdcl_set_order(b"rect:labelMergeMain", 0, 0, 5, 0)
         for t in range(nframes):
             img = synth.frame(synth.SEED0 + seed, iw, ih, t)
-            rects, snaps = r.execute_once(img, tan, snapshots=["region", "rsize", "boundary", "table"])
+            assert crc(img) == int(g[f"{case}_f{t}_input_crc"]), t
             orc.frame(img)
             for k in ("region", "rsize", "boundary"):
-                assert np.array_equal(snaps[k].view(np.int32), orc.plane(k).view(np.int32)), (t, k)
+                assert crc(orc.plane(k).view(np.int32)) == int(g[f"{case}_f{t}_{k}_crc"]), (t, k)
             mine = ra.postprocess_planes(orc.segments(), orc.plane("boundary"), orc.plane("table"), iw, ih, tan)
-            assert helpers.rects_equal(rects, mine), t
+            assert helpers.rects_equal(g[f"{case}_f{t}_rects"], mine), t
     finally:
-        R.rdcl_set_order(b"", 0, 0, 0, 0)
-        r.close()
         orc.close()
 
 
-@pytest.mark.ref
 @pytest.mark.parametrize("iw,ih,seed,nframes", [(333, 217, 2, 2), (640, 480, 5, 2), (640, 480, 0, 1)])
 def test_host_postprocess_equals_the_references_own_compiled_host_code(iw, ih, seed, nframes):
-    """pins csrc/rd_post.c (+ rd_post_core.h) from the outside: THE REFERENCE'S OWN compiled executeCPUTask (oclrect.c:1049-1226, unchanged, oracle/_ref) runs on the very
+    """pins csrc/rd_post.c (+ rd_post_core.h) from the outside: THE REFERENCE'S OWN compiled executeCPUTask (oclrect.c:1049-1226, unchanged, oracle/_ref) ran on the very
     planes rd_post.c is given - the stand-in hands them to the three read-backs of genGPUTask (oclrect.c:371-376) and runs none of the 220 launches
     (helpers.RefRect.host_postprocess) - and the two lists must agree in every bit AND in order; on the planes of the raster-order reference and on those of the concurrent,
-    settled region merge (what the HIP path computes), for two apertures.  The GPU suite repeats this on the HIP path's own planes over the long streams
+    settled region merge (what the HIP path computes), for two apertures.  The reference's lists are stored in tests/golden/ref_checks.npz (tools/make_golden_refchecks.py),
+    with the CRCs of the planes it was given.  The GPU suite repeats this on the HIP path's own planes over the long streams
     (test_references_own_host_code_on_the_hip_paths_planes)."""
-    r = helpers.RefRect(iw, ih)
+    g = golden("ref_checks")
+    case = "post_%dx%d_s%d_n%d" % (iw, ih, seed, nframes)
     checked = 0
     for mode in (helpers.REGION_REFERENCE_RASTER, helpers.REGION_SPEC):
         orc = helpers.OracleRect(iw, ih, mode)
         for t in range(nframes):
             orc.frame(synth.frame(synth.SEED0 + seed, iw, ih, t))
             segs, boundary, table = orc.segments(), orc.plane("boundary"), orc.plane("table")
+            key = f"{case}_m{mode}_f{t}"
+            assert [crc(segs), crc(boundary), crc(table)] == [int(v) for v in g[key + "_planes_crc"]], (mode, t, "not the planes the reference was given")
             for half_aov in (36.0, 25.0):
                 tan = float(np.tan(half_aov / 180.0 * np.pi))
                 mine = ra.postprocess_planes(segs, boundary, table, iw, ih, tan)
-                theirs = r.host_postprocess(segs, boundary, table, tan)
+                theirs = g[key + "_a%d_rects" % int(half_aov)]
                 assert helpers.rects_equal(mine, theirs), (mode, t, half_aov, len(mine), len(theirs))
                 checked += len(mine)
         orc.close()
-    r.close()
     assert checked > 0
 
 

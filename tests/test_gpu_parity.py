@@ -1313,7 +1313,7 @@ def test_two_real_detector_processes_share_the_gpu():
     s.close()
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     # (plain `python bench.py --gpus 2`: the script starts its two ranks itself; --share-gpus because this box has one device)
-    cmd = [sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--frames-per-step", "24", "--backend", "gloo", "--share-gpus"]
+    cmd = [sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--frames-per-step", "24", "--backend", "gloo", "--share-gpus", "--full"]
     p = subprocess.run(cmd, cwd=helpers.ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -1539,9 +1539,9 @@ def test_four_ranks_with_all_their_workers_keep_the_rate_of_one():
     0.9 of what one such process reaches alone on the same GPU: the host side (launches, event polling through the runtime's locks, post-process threads, the gloo control
     plane) is then not what limits a rank.  Every rank verifies its own lists."""
     import sys
-    one = _bench_line([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--frames-per-step", "256", "--no-cpu-baseline", "--no-configs"])
+    one = _bench_line([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--frames-per-step", "256", "--full", "--no-cpu-baseline", "--no-configs"])
     four = _bench_line([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "4", "--steps", "3", "--warmup", "1", "--frames-per-step", "64", "--backend", "gloo", "--share-gpus",
-                        "--no-cpu-baseline", "--no-configs"])
+                        "--full", "--no-cpu-baseline", "--no-configs"])
     assert four["n_gpus"] == 4 and four["outputs_verified"] is True and all(r["outputs_verified"] is True for r in four["ranks"])
     assert len({r["pid"] for r in four["ranks"]}) == 4 and len({r["stream_seed"] for r in four["ranks"]}) == 4
     ratio = four["value"] / one["value"]
@@ -1559,8 +1559,8 @@ def test_eight_ranks_rehearsal_on_one_gpu():
     failed: out of memory", which this test also checks, instead of running short.)"""
     import subprocess
     import sys
-    one = _bench_line([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--frames-per-step", "256", "--no-cpu-baseline", "--no-configs"])
-    common = ["--steps", "3", "--warmup", "1", "--frames-per-step", "64", "--backend", "gloo", "--share-gpus", "--no-cpu-baseline", "--no-configs"]
+    one = _bench_line([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--frames-per-step", "256", "--full", "--no-cpu-baseline", "--no-configs"])
+    common = ["--steps", "3", "--warmup", "1", "--frames-per-step", "64", "--backend", "gloo", "--share-gpus", "--full", "--no-cpu-baseline", "--no-configs"]
     eight = _bench_line([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--gpus", "8", "--slots", "32"] + common, timeout=1500)
     assert eight["n_gpus"] == 8 and eight["outputs_verified"] is True and all(r["outputs_verified"] is True for r in eight["ranks"])
     assert len({r["pid"] for r in eight["ranks"]}) == 8 and len({r["stream_seed"] for r in eight["ranks"]}) == 8
@@ -1586,6 +1586,30 @@ def test_bench_refuses_more_ranks_than_devices():
     assert not [l for l in p.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_dump_outputs_are_the_last_steps_lists(tmp_path):
+    """a plain `bench.py --dump-outputs DIR` run: DIR/rects.npy and rects_per_frame.npy (float64) hold the rectangle lists of the last timed step - the F frames
+    of the stream in order - and they are what a sequential pass over the same frames returns; a plain run does no verification of its own"""
+    import sys
+    F = 16
+    out = _bench_line([sys.executable, os.path.join(helpers.ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--frames-per-step", str(F), "--slots", "8",
+                       "--dump-outputs", str(tmp_path)])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["outputs_verified"] is None
+    rows, counts = np.load(tmp_path / "rects.npy"), np.load(tmp_path / "rects_per_frame.npy")
+    assert rows.dtype == np.float64 and counts.dtype == np.float64 and counts.shape == (F,) and rows.shape == (int(counts.sum()), 22)
+    assert not (tmp_path / "rects_rows.npy").exists()
+    tan = float(np.tan(72.0 / 2 / 180.0 * np.pi))
+    det = ra.Detector(1920, 1080, nslots=1)
+    want = []
+    for t in range(F):
+        det.enqueue(cframe(synth.SEED0, 1920, 1080, t))
+        want.append(det.poll(tan))
+    det.close()
+    assert [len(r) for r in want] == counts.astype(int).tolist()
+    want = np.concatenate(want)
+    cols = np.concatenate([want["c2"].reshape(-1, 8), want["c3"].reshape(-1, 12), want["value"].reshape(-1, 1), want["status"].astype(np.float64).reshape(-1, 1)], axis=1)
+    assert np.array_equal(rows, cols)
+
+
 def _bench_line(cmd, timeout=900):
     import json
     import subprocess
@@ -1605,7 +1629,7 @@ def test_bench_under_torchrun_with_one_rank_agrees_with_plain_bench():
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    args = ["--gpus", "1", "--steps", "6", "--warmup", "2", "--frames-per-step", "256", "--no-cpu-baseline", "--no-configs"]
+    args = ["--gpus", "1", "--steps", "6", "--warmup", "2", "--frames-per-step", "256", "--full", "--no-cpu-baseline", "--no-configs"]
     plain = _bench_line([sys.executable, os.path.join(helpers.ROOT, "bench.py")] + args)
     launched = _bench_line([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port),
                             os.path.join(helpers.ROOT, "bench.py")] + args)
