@@ -38,6 +38,17 @@ typedef struct rd_detector rd_detector;
 rd_detector *rd_detector_create(int device, int iw, int ih, int nslots, int nworkers);
 void rd_detector_destroy(rd_detector *d);
 
+/* The second kind of detector: line segments, what poly.cpp / vidpoly.cpp compute per frame (poly.cpp: strength_thre 500, minerror 1, size_thre 20;
+ * vidpoly.cpp: 2000, 1, 10), with nslots frames in flight in the same slots, groups, graphs and streams as the rectangle kind.  Every frame starts afresh
+ * (no state carried between frames).  NULL on invalid arguments (iw or ih < 16, nslots < 1, minerror <= 0, size_thre < 0, strength_thre < 0, no such device).
+ * rd_detector_enqueue (all three frame kinds), rd_detector_drain, rd_detector_destroy, rd_detector_counter and rd_detector_debug_plane work on it as on
+ * the rectangle kind; rd_detector_poll on it is fatal, as is rd_detector_poll_segments on a rectangle detector. */
+rd_detector *rd_polyline_detector_create(int device, int iw, int ih, int nslots, int strength_thre, float minerror, int size_thre);
+/* Result of the oldest frame not yet polled: a malloc'd linesegment_t array (56 bytes each) exactly as oclpolyline_execute leaves lsList - record 0 is the
+ * header (its first int = n), records 1..n follow, those with polyid == 0 included - owned by the caller.  Blocks until that frame is done.  ids_out != NULL:
+ * also the frame's per-pixel segment ids (iw * ih ints, oclpolyline_execute's lsIdOut), produced only when asked for. */
+void *rd_detector_poll_segments(rd_detector *d, int32_t *ids_out);
+
 /* Detectors with one or two frames in flight take their HIP streams from a process-wide cache (hardware queues of their own: DESIGN.md) and hand them back when they
  * are destroyed, so that the next detector runs on the same queues.  This destroys the cached streams of `device` (-1: all devices); live detectors are not affected. */
 void rd_release_cached_streams(int device);
@@ -81,7 +92,10 @@ int rd_detector_last_segments(rd_detector *d, void *dst, int max_records);
  * host post-process (sum over frames); 14 = frames whose small-region absorption (oclrect.cl:348-371) was finished by the slow path -
  * rounds over work lists until nothing changes - because they left more undecided pixels than the single-block tail holds (frames made of small regions);
  * 15 = frames per group launch; 16 / 17 = groups whose strong masks took one launch / one launch per frame; 18 = frames that travelled straight from the caller's pinned
- * memory (RD_FRAME_HOST_PINNED), 19 = host frames copied into the detector's own pinned staging first (RD_FRAME_HOST) */
+ * memory (RD_FRAME_HOST_PINNED), 19 = host frames copied into the detector's own pinned staging first (RD_FRAME_HOST);
+ * 30 = polyline kind: frames whose segment list was longer than the block handed to pinned host memory at the end of the frame and was fetched by the poll;
+ * 31 = device bytes of one slot's planes (both kinds; the polyline stage's compact scratch, the same for both, not included); 32 = records of that block (header included).
+ * The polyline kind keeps 0, 1, 2, 3, 15, 18, 19 as above (0: frames repeated in multi-launch form); the region, post-process and strong-mask counters stay 0 there. */
 long rd_detector_counter(rd_detector *d, int which);
 
 /* ---- Environment.  Everything is read when a detector is created (rd_detector_create / init_oclrect) and never again; an empty value counts as unset.
@@ -93,11 +107,14 @@ long rd_detector_counter(rd_detector *d, int which);
  *                the region merge pinned / cycling), RD_POLY_MULTILAUNCH, RD_POLY_FORCE_REDO, RD_ABSORB_FORCE_SLOW (the fallback paths for every frame), RD_MAXREC_DEV=n (small
  *                probe buffers), RD_TEST_THRESHOLDS=a,b (strength thresholds), RD_STRONG_BY_FRAME (a group's strong masks frame by frame), RD_IIR_FORCE_FIX (every blur column
  *                through the full-length path; read per call).  Each is driven by a test in tests/test_gpu_parity.py.
+ *                Polyline kind: RD_ZBATCH, RD_NO_GRAPH, RD_POLY_MULTILAUNCH and RD_POLY_FORCE_REDO as above, and RD_POLY_HANDOFF=n (records, header included,
+ *                handed to pinned host memory at the end of a frame; default 2048) - driven by tests/test_gpu_polyline_stream.py.
  * Switches of experiments that were measured and not kept exist only in tuning builds (-DRD_TUNING, tools/variants.sh). */
 
 /* Test hook: copy an internal plane of the most recently completed frame to host memory.  Returns bytes written,
  * 0 for an unknown name.  Names: plab0 plab1 lblur vxy strength nms mask0 tidy label1 strsum edge500 smooth quant
- * strong junction mergemask region0 (merged regions) rsize region (after absorbing small ones) boundarysrc boundary lsid table */
+ * strong junction mergemask region0 (merged regions) rsize region (after absorbing small ones) boundarysrc boundary lsid table;
+ * polyline kind: plab0 lblur nms mask0 (nms > 0) label1 (its components) strsum polymask (the traced mask, poly.cpp:121) lslist lsid polyctr */
 size_t rd_detector_debug_plane(rd_detector *d, const char *name, void *dst, size_t max_bytes);
 
 /* ---- host post-process alone (oclrect.c:1049-1226 restated): segments + samples -> rectangles.  Used by tests to

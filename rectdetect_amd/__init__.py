@@ -9,6 +9,7 @@ Mirrors of the reference programs' call sequences:
   * :func:`poly_frame`  - poly.cpp:104-131 (explicit operator sequence + ``oclpolyline_execute``)
   * :class:`RectDetector` - rect.cpp / vidrect.cpp (``oclrect_executeOnce`` / ``enqueueTask`` / ``pollTask``)
   * :class:`Detector` - the ``rd_detector`` extension (device-resident frames, several frames in flight)
+  * :class:`PolylineDetector` - its polyline kind: poly.cpp / vidpoly.cpp per frame, several frames in flight
 """
 import ctypes
 import os
@@ -59,6 +60,8 @@ def _declare(L):
         "rd_download": (None, [vp, vp, cz]),
         "rd_detector_create": (vp, [ci, ci, ci, ci, ci]),
         "rd_detector_destroy": (None, [vp]),
+        "rd_polyline_detector_create": (vp, [ci, ci, ci, ci, ci, cf, ci]),
+        "rd_detector_poll_segments": (vp, [vp, vp]),
         "rd_detector_enqueue": (ctypes.c_long, [vp, vp, ci, ci]),
         "rd_detector_poll": (vp, [vp, cd]),
         "rd_detector_drain": (None, [vp]),
@@ -330,6 +333,55 @@ class Detector:
 
     def close(self):
         lib().rd_detector_destroy(self.h)
+
+
+class PolylineDetector:
+    """The polyline kind of rd_detector (rd_polyline_detector_create): the line segments of poly.cpp (strength_thre 500, minerror 1, size_thre 20) or
+    vidpoly.cpp (2000, 1, 10) for a stream of frames, several in flight."""
+
+    def __init__(self, iw, ih, device=0, nslots=8, strength_thre=500, minerror=1.0, size_thre=20):
+        L = lib()
+        self.iw, self.ih, self.N = iw, ih, iw * ih
+        self.h = L.rd_polyline_detector_create(device, iw, ih, nslots, strength_thre, float(minerror), size_thre)
+        if not self.h:
+            raise ValueError("rd_polyline_detector_create: invalid arguments (%r)" % ((device, iw, ih, nslots, strength_thre, minerror, size_thre),))
+
+    def enqueue(self, frame, ws=None, on_device=False, pinned=False):
+        """as Detector.enqueue: a numpy BGR image (copied before the call returns), or the address of a frame in device / pinned host memory"""
+        if on_device or pinned:
+            return lib().rd_detector_enqueue(self.h, frame, ws, 1 if on_device else 2)
+        a = np.ascontiguousarray(frame)
+        self._keep = a
+        return lib().rd_detector_enqueue(self.h, a.ctypes.data, a.strides[0] if ws is None else ws, 0)
+
+    def poll(self, ids=False):
+        """(segments[LS_DTYPE] with the header record, per-pixel segment ids or None) of the oldest frame not yet polled"""
+        out = np.zeros(self.N, np.int32) if ids else None
+        ptr = lib().rd_detector_poll_segments(self.h, out.ctypes.data if ids else None)
+        if not ptr:
+            raise RuntimeError("rd_detector_poll_segments returned NULL")
+        n = ctypes.cast(ptr, ctypes.POINTER(ctypes.c_int))[0]
+        segs = np.frombuffer((ctypes.c_char * (56 * (n + 1))).from_address(ptr), dtype=LS_DTYPE).copy()
+        _libc.free(ptr)
+        return segs, out
+
+    def drain(self):
+        lib().rd_detector_drain(self.h)
+
+    def counter(self, which):
+        return lib().rd_detector_counter(self.h, which)
+
+    def plane(self, name, dtype=np.int32, count=None):
+        count = self.N if count is None else count
+        out = np.zeros(count, dtype)
+        if lib().rd_detector_debug_plane(self.h, name.encode(), out.ctypes.data, out.nbytes) == 0:
+            raise KeyError(name)
+        return out
+
+    def close(self):
+        if self.h:
+            lib().rd_detector_destroy(self.h)
+            self.h = None
 
 
 def postprocess_planes(segs, boundary, table, iw, ih, tan_aov):

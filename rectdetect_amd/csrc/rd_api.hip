@@ -389,7 +389,16 @@ struct rd_detector {
   long n_frames_pinned, n_frames_copied;     // host frames that travelled straight from the caller's pinned memory / through the detector's own staging pages
   long n_unsettled;          // frames whose region merge was still changing after RD_REGION_MAX_LAUNCHES launches (none on any fixture)
   long n_truncated;          // frames with more segment records than the slots' probe buffers hold (maxrec_dev): probed again into a larger buffer
+  // the polyline kind (rd_polyline_detector_create: poly.cpp / vidpoly.cpp per frame); a rectangle detector has kind RD_KIND_RECT and none of this
+  int kind;
+  int p_thre, p_size; float p_minerror;     // filterStrength threshold, sizeThre, minerror
+  int handoff_rec;           // records (header included) each slot's pinned block receives at the end of a frame (RD_POLY_HANDOFF)
+  long n_long_lists;         // frames whose list did not fit that block and was fetched by the poll (rd_detector_counter 30)
+  size_t slot_bytes;         // device bytes of one slot's planes (rd_detector_counter 31; evaluated on first request)
 };
+#define RD_KIND_RECT 0
+#define RD_KIND_POLY 1
+#define RD_POLY_HANDOFF_DEFAULT 2048      // records handed off per frame: 112 KB of pinned memory per slot
 
 // The device planes of a slot.  With frames batched per launch (rd_detector::zb > 1) every slot's planes are carved out of one allocation at
 // the same offsets, so that the planes of slot k + z lie a constant number of bytes (the slot pitch) behind those of slot k: a kernel of a
@@ -406,7 +415,26 @@ struct PlaneAlloc {
   bool real() const { return mode != 2; }
 };
 
+static bool front_is_fused(const rd_detector *d);
+// The planes of a polyline-kind slot: the front end up to the suppressed response, the labelling, the strength sums, the mask bits, the list and the id
+// plane.  None of the rect kind's later planes (edge-stopped blur, quantisation, merge mask, regions, boundaries, vote tables, probes, post-process).
+static void slot_planes_poly(rd_detector *d, Slot *s, PlaneAlloc &A) {
+  const size_t N = (size_t)d->N;
+  s->bgr = A.get<uint8_t>(N * 4);
+  s->plab0 = A.get<uint32_t>(N);         // (the colour conversion's packed output: read by nothing on this path but the debug plane)
+  for (int k = 0; k < 3; k++) { s->tr[k] = A.get<float>(N); s->fw[k] = A.get<float>(N); s->bw[k] = A.get<float>(N); s->hz[k] = A.get<float>(N); s->bl[k] = A.get<float>(N); }
+  if (!front_is_fused(d)) { s->plab1 = A.get<uint32_t>(N); s->vxy = A.get<float>(N * 2); s->strength = A.get<float>(N); }      // (frame sizes the fused kernel's tiles do not cover: the three operators)
+  s->nms = A.get<float>(N);
+  s->mask0 = A.get<int>(N); s->label1 = A.get<int>(N); s->strsum = A.get<int>(N); s->lsid = A.get<int>(N);
+  s->strongbits = A.get<unsigned long long>((size_t)((d->iw + 63) / 64) * d->ih + 8);      // the poly mask as a bit plane: what the polyline stage traces
+  { size_t a = rdk::iir_pass_scratch_floats(3, d->ih, d->iw), b = rdk::iir_pass_scratch_floats(3, d->iw, d->ih); s->tails = A.get<float>(a > b ? a : b); }
+  s->flags = A.get<int>(16); if (A.real()) { RD_HIP(hipMemset(s->flags, 0, 16 * sizeof(int))); RD_HIP(hipStreamSynchronize(0)); }
+  s->iir_chunked = 1;
+  s->lslist = A.get<uint8_t>(N * 16);
+}
+
 static void slot_planes(rd_detector *d, Slot *s, PlaneAlloc &A) {
+  if (d->kind == RD_KIND_POLY) { slot_planes_poly(d, s, A); return; }
   const size_t N = (size_t)d->N;
   s->bgr = A.get<uint8_t>(N * 4);
   s->plab0 = A.get<uint32_t>(N); s->plab1 = A.get<uint32_t>(N); s->smooth = A.get<uint32_t>(N); s->quant = A.get<uint32_t>(N);
@@ -520,7 +548,7 @@ static void slot_alloc(rd_detector *d, Slot *s, Slot *share) {
   { PlaneAlloc A = { d->arena ? d->arena + (size_t)(s - d->slots) * d->slot_pitch : NULL, 0, d->arena ? 1 : 0 }; slot_planes(d, s, A); }
   s->ps = rdk::poly_scratch_create(d->iw, d->ih);
   RD_HIP(hipHostMalloc(&s->h_bgr, N * 4, hipHostMallocDefault));
-  const size_t pack_ints = 64 + (size_t)RD_MAXREC * (14 + 15 * 6);
+  const size_t pack_ints = d->kind == RD_KIND_POLY ? 64 + (size_t)d->handoff_rec * 14 : 64 + (size_t)RD_MAXREC * (14 + 15 * 6);      // (poly kind: counters + records, no probes)
   RD_HIP(hipHostMalloc((void **)&s->h_pack, pack_ints * sizeof(int), hipHostMallocDefault)); memset(s->h_pack, 0, pack_ints * sizeof(int));
   RD_HIP(hipHostGetDevicePointer((void **)&s->h_pack_dev, s->h_pack, 0));
   s->h_ctr = s->h_pack; s->h_segs = s->h_pack + 64; s->h_probes = s->h_pack + 64 + (size_t)RD_MAXREC * 14;
@@ -536,7 +564,7 @@ static void slot_alloc(rd_detector *d, Slot *s, Slot *share) {
   rdk::PolyFrame &f = *s->frame;
   memset(&f, 0, sizeof(f));
   f.ps = *s->ps; f.in = NULL; f.in_bits = s->strongbits; f.ring_src = NULL; f.lslist = s->lslist; f.ids = s->lsid;
-  f.boundary = s->boundary; f.table = s->table; f.claim = s->claim; f.tlist = s->tlist; f.probes = s->probes; f.pack = s->h_pack_dev; f.rflags = s->scratch2 + N;
+  f.boundary = s->boundary; f.table = s->table; f.claim = s->claim; f.tlist = s->tlist; f.probes = s->probes; f.pack = s->h_pack_dev; f.rflags = s->scratch2 ? s->scratch2 + N : NULL;
   f.post_scratch = s->post_scratch; f.post_out = s->h_post_dev;
 }
 
@@ -1171,6 +1199,92 @@ static void *slot_worker(void *arg) {
   }
 }
 
+
+// ================================================================================================ polyline kind
+// poly.cpp:104-123 / vidpoly.cpp:165-183 per frame, nz frames of consecutive slots per launch (group mode, as the rect kind's): the front end of the rect
+// kind, the components of nms > 0 (no tidy), the strength sums from zero (no H1 carry-over: poly.cpp:118 clears them), filterStrength + `label > 0` as
+// a bit plane, the polyline stage with the frame ring at zero (the reference's tmp3 is a fresh, zeroed buffer: poly.cpp:93) and the hand-off of the
+// list's first records into pinned host memory.  Nothing depends on the frame before: the whole frame is one captured sequence.
+static void poly_segment(rd_detector *d, Slot *s, int nz, size_t zs, hipStream_t st, int mode) {
+  const int iw = d->iw, ih = d->ih, N = d->N;
+  { const float *c[3] = { s->tr[0], s->tr[1], s->tr[2] }; rdk::iir_blur_pass(st, s->hz, c, s->fw, s->bw, 3, ih, iw, 1, s->tails, s->flags, 1, nz, zs); }
+  { const float *c[3] = { s->hz[0], s->hz[1], s->hz[2] }; rdk::iir_blur_pass(st, s->bl, c, s->fw, s->bw, 3, iw, ih, 0, s->tails, s->flags + 1, 0, nz, zs); }
+  frames_grad_nms(d, s, st, nz, zs);
+  rdk::label8_positive(st, s->label1, s->mask0, s->nms, s->strsum, iw, ih, 1, nz, zs);      // (poly.cpp:115-118; the walk to the roots happens in the next kernel)
+  rdk::calc_strength(st, s->strsum, s->nms, s->label1, iw, ih, NULL, 1, nz, zs);           // (poly.cpp:119)
+  rdk::poly_mask_bits(st, s->strongbits, s->label1, s->strsum, d->p_thre, iw, ih, nz, zs);   // (poly.cpp:120-121)
+  rdk::polyline(st, s->frame, nz, N * 16, 0, d->p_minerror, d->p_size, iw, ih, mode);      // (poly.cpp:123)
+  rdk::polyline_handoff(st, s->frame, nz, d->handoff_rec);
+}
+
+// one frame (nz = 1) or a full group (nz = zb, s = its first slot), as a captured graph per polyline mode
+static void poly_run(rd_detector *d, Slot *s, int nz, hipStream_t st, int mode) {
+  const size_t zs = nz > 1 ? d->slot_pitch : 0;
+  if (!d->use_graph) { poly_segment(d, s, nz, zs, st, mode); return; }
+  hipGraphExec_t *ge = nz > 1 ? &s->gz2[mode] : &s->gexec[mode];
+  if (!*ge) {
+    hipGraph_t g = NULL;
+    pthread_mutex_lock(&d->launch_mu);
+    RD_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+    poly_segment(d, s, nz, zs, st, mode);
+    RD_HIP(hipStreamEndCapture(st, &g));
+    pthread_mutex_unlock(&d->launch_mu);
+    RD_HIP(hipGraphInstantiate(ge, g, NULL, NULL, 0));
+    RD_HIP(hipGraphDestroy(g));
+  }
+  RD_HIP(hipGraphLaunch(*ge, st));
+}
+
+static void poly_enqueue_frame(rd_detector *d, Slot *s, int ws) {
+  RD_HIP(hipEventRecord(s->ev_begin, s->st));
+  s->watch_begin = s->ev_begin; s->watch_done = s->ev_done;
+  s->group_n = 1;
+  rdk::bgr2plab_transposed(s->st, s->plab0, s->tr, s->src, d->iw, d->ih, ws);      // (outside the graph: its source changes from frame to frame)
+  s->poly_mode = current_poly_mode(d);
+  poly_run(d, s, 1, s->st, s->poly_mode);
+  RD_HIP(hipEventRecord(s->ev_done, s->st));
+  rdrt::check_launch("polyline frame");
+}
+
+// the frames waiting in the group that starts at slot g0 (see group_launch: a full group with one row stride -> one set of launches, anything else frame by frame)
+static void poly_group_launch(rd_detector *d, int g0) {
+  const int zb = d->zb;
+  int cnt = 0, same_ws = 1;
+  for (int i = g0; i < g0 + zb && i < d->nslots; i++) { Slot *s = &d->slots[i]; if (s->pending_dense) { cnt++; if (s->ws != d->slots[g0].ws) same_ws = 0; } }
+  if (cnt == 0) return;
+  bool travelled = false;
+  for (int i = g0; i < g0 + zb && i < d->nslots; i++) { Slot *s = &d->slots[i]; if (s->pending_dense && s->src == s->bgr && s->uploaded_early) travelled = true; }
+  if (travelled) RD_HIP(hipStreamSynchronize(d->st_upload));
+  if (cnt < zb || !same_ws) {
+    for (int i = g0; i < g0 + zb && i < d->nslots; i++) {
+      Slot *s = &d->slots[i];
+      if (!s->pending_dense) continue;
+      s->pending_dense = 0;
+      if (s->src == s->bgr && !s->uploaded_early) RD_HIP(hipMemcpyAsync(s->bgr, s->h_bgr, (size_t)s->ws * d->ih, hipMemcpyHostToDevice, s->st));
+      poly_enqueue_frame(d, s, s->ws);
+    }
+    return;
+  }
+  Slot *lead = &d->slots[g0];
+  hipStream_t st = group_stream(d, g0);
+  const int ws = lead->ws;
+  const uint8_t *srcs[RD_ZB_MAX];
+  const int pm = current_poly_mode(d);
+  for (int i = 0; i < zb; i++) {
+    Slot *s = &d->slots[g0 + i];
+    s->pending_dense = 0;
+    if (s->src == s->bgr && !s->uploaded_early) RD_HIP(hipMemcpyAsync(s->bgr, s->h_bgr, (size_t)ws * d->ih, hipMemcpyHostToDevice, st));
+    srcs[i] = s->src;
+    s->watch_begin = lead->ev_begin; s->watch_done = lead->ev_done;      // (one pair of events brackets the group)
+    s->group_n = zb; s->poly_mode = pm;
+  }
+  RD_HIP(hipEventRecord(lead->ev_begin, st));
+  rdk::bgr2plab_transposed(st, lead->plab0, lead->tr, srcs, d->iw, d->ih, ws, zb, d->slot_pitch);
+  poly_run(d, lead, zb, st, pm);
+  RD_HIP(hipEventRecord(lead->ev_done, st));
+  rdrt::check_launch("polyline frames, group launch");
+}
+
 extern "C" {
 
 rd_detector *rd_detector_create(int device, int iw, int ih, int nslots, int nworkers) {
@@ -1418,7 +1532,9 @@ long rd_detector_enqueue(rd_detector *d, const void *frame, int ws, int on_devic
     s->pending_dense = 1;
     // (the last group of slots may be short - nslots need not be a multiple of zb - and is launched when ITS last slot is filled: every group
     //  is launched the moment its last frame arrives, so frames reach the device in sequence order and at most one group is ever waiting)
-    if (si % d->zb == d->zb - 1 || si == d->nslots - 1) group_launch(d, si / d->zb * d->zb);
+    if (si % d->zb == d->zb - 1 || si == d->nslots - 1) { if (d->kind == RD_KIND_POLY) poly_group_launch(d, si / d->zb * d->zb); else group_launch(d, si / d->zb * d->zb); }
+  } else if (d->kind == RD_KIND_POLY) {
+  poly_enqueue_frame(d, s, ws);
   } else {
   enqueue_frame(d, s, ws);
   }
@@ -1444,6 +1560,7 @@ long rd_detector_enqueue(rd_detector *d, const void *frame, int ws, int on_devic
 
 void *rd_detector_poll(rd_detector *d, double tanAOV) {
   if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_poll: bad handle\n");
+  if (d->kind == RD_KIND_POLY) exitf(-1, "rd_detector_poll: this is a polyline detector (rd_polyline_detector_create) - its results come from rd_detector_poll_segments\n");
   if (d->next_poll >= d->next_enqueue) exitf(-1, "rd_detector_poll: nothing enqueued\n");
   RD_HIP(hipSetDevice(d->device));
   const int si = (int)(d->next_poll % d->nslots);
@@ -1506,7 +1623,10 @@ void rd_detector_drain(rd_detector *d) {
   if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_drain: bad handle\n");
   RD_HIP(hipSetDevice(d->device));
   if (d->batch > 1) for (int i = 0; i < d->nslots; i += d->batch) sparse_flush(d, i);
-  if (d->zb > 1) for (long q = d->next_poll; q < d->next_enqueue; q++) { const int si = (int)(q % d->nslots); if (d->slots[si].pending_dense) group_launch(d, si / d->zb * d->zb); }      // (sequence order)
+  if (d->zb > 1) for (long q = d->next_poll; q < d->next_enqueue; q++) {      // (sequence order)
+    const int si = (int)(q % d->nslots);
+    if (d->slots[si].pending_dense) { if (d->kind == RD_KIND_POLY) poly_group_launch(d, si / d->zb * d->zb); else group_launch(d, si / d->zb * d->zb); }
+  }
   for (int i = 0; i < d->nslots; i++) RD_HIP(hipStreamSynchronize(d->slots[i].st));
 }
 
@@ -1530,6 +1650,12 @@ long rd_detector_counter(rd_detector *d, int which) {
   if (which >= 40 && which <= 60) return d->need_count[which - 40];      // frames whose region merge needed 0..20 launches (the one that changes nothing included; 20: or more)
   if (which == 1) return d->dev_us;
   if (which == 2) return d->dev_frames;
+  if (which == 30) return __atomic_load_n(&d->n_long_lists, __ATOMIC_RELAXED);
+  if (which == 31) {      // (counted the way the slots were carved: every plane rounded up to 256 bytes)
+    if (!d->slot_bytes) { Slot tmp; memset(&tmp, 0, sizeof(tmp)); PlaneAlloc A = { NULL, 0, 2 }; slot_planes(d, &tmp, A); d->slot_bytes = A.at; }
+    return (long)d->slot_bytes;
+  }
+  if (which == 32) return d->kind == RD_KIND_POLY ? d->handoff_rec : RD_MAXREC;
   return which == 0 ? __atomic_load_n(&d->n_redo, __ATOMIC_RELAXED) : -1;
 }
 
@@ -1541,12 +1667,14 @@ int rd_detector_last_segments(rd_detector *d, void *dst, int max_records) {
   return d->last_nsegs;
 }
 
+static size_t poly_debug_plane(rd_detector *d, Slot *s, const char *name, void *dst, size_t max_bytes);
 size_t rd_detector_debug_plane(rd_detector *d, const char *name, void *dst, size_t max_bytes) {
   if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_debug_plane: bad handle\n");
   if (d->last_polled_slot < 0) return 0;
   RD_HIP(hipSetDevice(d->device));
   Slot *s = &d->slots[d->last_polled_slot];
   const size_t N = (size_t)d->N;
+  if (d->kind == RD_KIND_POLY) return poly_debug_plane(d, s, name, dst, max_bytes);
   struct { const char *n; const void *p; size_t bytes; } tab[] = {
     { "plab0", s->plab0, N * 4 }, { "plab1", s->plab1, N * 4 }, { "lblur", s->bl[0], N * 4 }, { "vxy", s->vxy, N * 8 }, { "strength", s->strength, N * 4 },
     { "nms", s->nms, N * 4 }, { "mask0", s->nms, N * 4 }, { "tidy", s->tidy, N * 4 }, { "label1", s->label1, N * 4 }, { "strsum", s->strsum, N * 4 },
@@ -1613,6 +1741,121 @@ size_t rd_detector_debug_plane(rd_detector *d, const char *name, void *dst, size
       }
       return b;
     }
+  return 0;
+}
+
+// ---- the polyline kind
+rd_detector *rd_polyline_detector_create(int device, int iw, int ih, int nslots, int strength_thre, float minerror, int size_thre) {
+  if (iw < 16 || ih < 16 || (long long)iw * ih >= (1ll << 25) || nslots < 1 || device < 0 || strength_thre < 0 || !(minerror > 0.0f) || size_thre < 0) return NULL;
+  if (rd_device_count() <= 0) exitf(-1, "rd_polyline_detector_create: no HIP device available - this library has no CPU path\n");
+  if (device >= rd_device_count()) return NULL;
+  RD_HIP(hipSetDevice(device));
+  rd_detector *d = (rd_detector *)calloc(1, sizeof(*d));
+  d->magic = MAGIC_RECT; d->kind = RD_KIND_POLY;
+  d->device = device; d->iw = iw; d->ih = ih; d->N = iw * ih; d->nslots = nslots; d->nworkers = 0;
+  d->p_thre = strength_thre; d->p_minerror = minerror; d->p_size = size_thre;
+  d->handoff_rec = RD_POLY_HANDOFF_DEFAULT;
+  { const int h = rd_env_int("RD_POLY_HANDOFF", 0); if (h >= 2) d->handoff_rec = h; }      // (tests: a small block, so that ordinary frames take the long-list path)
+  d->maxrec_dev = d->N * 16 / 56;
+  if (d->maxrec_dev > 65536) d->maxrec_dev = 65536;
+  d->use_graph = rd_env("RD_NO_GRAPH") ? 0 : 1;
+  d->poly_mode = rd_env("RD_POLY_MULTILAUNCH") ? 0 : 1;
+  d->force_redo = rd_env("RD_POLY_FORCE_REDO") ? 1 : 0;
+  d->poly_overflows = (long)iw * ih > 3000000L ? 1 : 0;      // (as the rect kind: 3840x2160 starts on the multi-launch form)
+  d->batch = 1; d->defer = 0; d->deferred_slot = -1; d->fork_poly = 0; d->device_post = 0;
+  pthread_mutex_init(&d->tan_mu, NULL); pthread_cond_init(&d->tan_cv, NULL);
+  pthread_mutex_init(&d->launch_mu, NULL);
+  d->slots = (Slot *)calloc((size_t)nslots, sizeof(Slot));
+  d->frames = (rdk::PolyFrame *)calloc((size_t)nslots, sizeof(rdk::PolyFrame));
+  // streams and group launches as the rect kind (rd_detector_create): four streams, groups of 2 / 4 / 8 frames from 6 / 12 / 32 slots on, none above 1920x1088
+  const int nstreams = 4;
+  d->nstreams = nstreams < nslots ? nstreams : nslots;
+  d->zb = nslots >= 32 ? 8 : (nslots >= 12 ? 4 : (nslots >= 6 ? 2 : 1));
+  if ((long long)iw * ih > 1920ll * 1088) d->zb = 1;
+  if (rd_env("RD_ZBATCH")) { const int z = rd_env_int("RD_ZBATCH", 1); d->zb = z < 1 ? 1 : (z > RD_ZB_MAX ? RD_ZB_MAX : z); }
+  if (d->zb > nslots) d->zb = 1;
+  if (d->zb > 1) {
+    Slot tmp; memset(&tmp, 0, sizeof(tmp));
+    PlaneAlloc A = { NULL, 0, 2 };
+    slot_planes(d, &tmp, A);
+    d->slot_pitch = A.at;
+    d->arena = dnew<char>((size_t)nslots * d->slot_pitch);
+  }
+  for (int i = 0; i < nslots; i++) {
+    Slot *s = &d->slots[i];
+    slot_alloc(d, s, i >= nstreams ? &d->slots[i % nstreams] : NULL);
+    s->owner = d;
+    pthread_mutex_init(&s->mu, NULL); pthread_cond_init(&s->cv, NULL);
+  }
+  d->last_polled_slot = -1;
+  RD_HIP(hipDeviceSynchronize());
+  return d;
+}
+
+void *rd_detector_poll_segments(rd_detector *d, int32_t *ids_out) {
+  if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_poll_segments: bad handle\n");
+  if (d->kind != RD_KIND_POLY) exitf(-1, "rd_detector_poll_segments: this is a rectangle detector (rd_detector_create) - its results come from rd_detector_poll\n");
+  if (d->next_poll >= d->next_enqueue) exitf(-1, "rd_detector_poll_segments: nothing enqueued\n");
+  RD_HIP(hipSetDevice(d->device));
+  const int si = (int)(d->next_poll % d->nslots);
+  Slot *s = &d->slots[si];
+  const size_t N = (size_t)d->N;
+  if (s->pending_dense) poly_group_launch(d, si / d->zb * d->zb);      // (an incomplete group: the caller wants a result before handing over more frames)
+  RD_HIP(hipEventSynchronize(s->watch_done));
+  // the single-block polyline kernel gave up on this frame (on-chip tables too small): the stage again in multi-launch form, on the slot's own stream (the
+  // frame is finished; its slot is not reused before this poll returns); two such frames in a row send the stream's later frames to the multi-launch form
+  const bool over = s->poly_mode == 1 && s->h_pack[25] != 0;
+  if (s->poly_mode == 1) { if (over) { if (++d->overflow_streak >= 2) d->poly_overflows = 1; } else d->overflow_streak = 0; }
+  if (!s->st_redo) s->st_redo = make_redo_stream();
+  if (over || (d->force_redo & 1)) {
+    rdk::polyline(s->st_redo, s->frame, 1, d->N * 16, 0, d->p_minerror, d->p_size, d->iw, d->ih, 0);
+    rdk::polyline_handoff(s->st_redo, s->frame, 1, d->handoff_rec);
+    rdrt::check_launch("polyline frame, multi-launch repeat");
+    RD_HIP(hipStreamSynchronize(s->st_redo));
+    d->n_redo++;
+  }
+  const int n = s->h_pack[64];
+  void *out = malloc((size_t)(n + 1) * 56);
+  if (!out) exitf(-1, "rd_detector_poll_segments: out of memory\n");
+  if (n + 1 <= d->handoff_rec) memcpy(out, s->h_pack + 64, (size_t)(n + 1) * 56);
+  else { slot_fetch(s, out, s->lslist, (size_t)(n + 1) * 56); d->n_long_lists++; }      // (nothing is dropped: the rest of a long list comes from the device)
+  if (ids_out) {      // the dense id plane, only on request: from the slot's compact scratch
+    rdk::polyline_ids(s->st_redo, s->frame, 1, (int)N);
+    RD_HIP(hipMemcpyAsync(ids_out, s->lsid, N * 4, hipMemcpyDeviceToHost, s->st_redo));
+    RD_HIP(hipStreamSynchronize(s->st_redo));
+  }
+  { float ms = 0.0f; if (hipEventElapsedTime(&ms, s->watch_begin, s->watch_done) == hipSuccess) { d->dev_us += (long)(ms * 1000.0f) / (s->group_n > 0 ? s->group_n : 1); d->dev_frames++; } }
+  d->last_polled_slot = si;
+  d->next_poll++;
+  return out;
+}
+
+// debug planes of the polyline kind (the planes it has): plab0 lblur nms mask0 label1 strsum polymask lslist lsid polyctr
+static size_t poly_debug_plane(rd_detector *d, Slot *s, const char *name, void *dst, size_t max_bytes) {
+  const size_t N = (size_t)d->N;
+  const int wpr = (d->iw + 63) / 64;
+  struct { const char *n; const void *p; size_t bytes; } tab[] = {
+    { "plab0", s->plab0, N * 4 }, { "lblur", s->bl[0], N * 4 }, { "nms", s->nms, N * 4 }, { "mask0", s->mask0, N * 4 }, { "label1", s->label1, N * 4 },
+    { "strsum", s->strsum, N * 4 }, { "polymask", s->strongbits, (size_t)wpr * d->ih * 8 }, { "lslist", s->lslist, N * 16 }, { "lsid", s->lsid, N * 4 },
+    { "polyctr", rdk::poly_scratch_counters(s->ps), 64 * 4 },
+  };
+  for (size_t i = 0; i < sizeof(tab) / sizeof(tab[0]); i++) {
+    if (strcmp(tab[i].n, name)) continue;
+    if (!strcmp(name, "lsid")) { rdk::polyline_ids(s->st, s->frame, 1, (int)N); rdrt::check_launch("polyline ids"); }
+    RD_HIP(hipStreamSynchronize(s->st));
+    if (!strcmp(name, "polymask")) {      // a bit plane on the device: handed out as the int plane of poly.cpp:121
+      const size_t n = N * 4 <= max_bytes ? N : max_bytes / 4;
+      unsigned long long *tmp = (unsigned long long *)malloc((size_t)wpr * d->ih * 8 + 8);
+      if (!tmp) exitf(-1, "rd_detector_debug_plane: out of memory\n");
+      RD_HIP(hipMemcpy(tmp, tab[i].p, (size_t)wpr * d->ih * 8, hipMemcpyDeviceToHost));
+      for (size_t k = 0; k < n; k++) { const int y = (int)(k / d->iw), x = (int)(k % d->iw); ((int *)dst)[k] = (int)((tmp[(size_t)y * wpr + (x >> 6)] >> (x & 63)) & 1ull); }
+      free(tmp);
+      return n * 4;
+    }
+    const size_t b = tab[i].bytes < max_bytes ? tab[i].bytes : max_bytes;
+    RD_HIP(hipMemcpy(dst, tab[i].p, b, hipMemcpyDeviceToHost));
+    return b;
+  }
   return 0;
 }
 

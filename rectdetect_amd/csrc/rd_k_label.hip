@@ -80,6 +80,18 @@ __global__ __launch_bounds__(64 * TY) void k_label_tile(int *__restrict__ label,
     if (threadIdx.y == 0 && tx == 0) s_t00 = pv8[0];
     __syncthreads();
     v00 = s_t00;
+  } else if constexpr (SRC == 3) {
+    // the poly kind's mask (poly.cpp:115-116: threshold_f_f(0, 0, 1) + cast_i_f) straight from the suppressed response, no tidy; written to pix_out for the
+    // border kernel, and the strength sums (zero_plane) cleared on the way (poly.cpp:118)
+#pragma unroll
+    for (int k = 0; k < LT_H / TY; k++) {
+      const int y = y0 + threadIdx.y + k * TY;
+      const bool in = xin && y < ih;
+      const float e = nms[in ? y * iw + x : 0];
+      pv8[k] = e > 0.0f ? 1 : 0;
+      if (in) { pix_out[y * iw + x] = pv8[k]; zero_plane[y * iw + x] = 0; }
+    }
+    v00 = nms[(size_t)y0 * iw + rd_b.x * LT_W] > 0.0f ? 1 : 0;   // the tile's first pixel is always inside the frame
   } else if constexpr (!BOUNDARY) {
     v00 = pix[(size_t)y0 * iw + rd_b.x * LT_W];   // the tile's first pixel is always inside the frame
 #pragma unroll
@@ -585,6 +597,23 @@ __global__ __launch_bounds__(256) void k_strength_masks_group(int8_t *ring, int8
   if (ln[0] != l[0] || ln[1] != l[1] || ln[2] != l[2] || ln[3] != l[3]) *(int4 *)(label + p) = make_int4(ln[0], ln[1], ln[2], ln[3]);
 }
 
+// The poly kind's mask (poly.cpp:120-121): filterStrength(thre) - interior pixels whose component's sum stays below thre leave - then label > 0,
+// as a bit plane (ceil(iw / 64) words per row; a wave is one 64-pixel word of a row).  The frame ring is never filtered, and a component whose
+// smallest pixel index is 0 is dropped by the `label > 0` test as in the reference.  No frame-to-frame dependency: nz frames per launch.
+__global__ __launch_bounds__(256) void k_poly_mask_bits(unsigned long long *__restrict__ bits, const int *__restrict__ label, const int *__restrict__ str, int thre, int iw, int ih, size_t zs) {
+  RD_ZSHIFT(zs, bits, label, str);
+  const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+  if (y >= ih) return;      // (whole waves: a wave is one row)
+  bool on = false;
+  if (x < iw) {
+    const int l = label[y * iw + x];
+    const bool interior = x > 0 && y > 0 && x < iw - 1 && y < ih - 1;
+    on = l > 0 && (!interior || str[l] >= thre);
+  }
+  const unsigned long long m = __ballot(on);
+  if (threadIdx.x == 0) bits[(size_t)y * ((iw + 63) >> 6) + blockIdx.x] = m;
+}
+
 }  // namespace
 
 namespace rdk {
@@ -624,6 +653,24 @@ void label8_tidy(hipStream_t s, int *label, int *mask0, int *tidy, const float *
   const int n = iw * ih;
   int g = cdiv(n, 256 * 4);
   hipLaunchKernelGGL(k_label_flatten, dim3(g < 1 ? 1 : g, 1, nz), dim3(256), 0, s, label, n, (int *)nullptr, (int *)nullptr, (int *)nullptr, zs);
+}
+
+// poly kind: label8(nms > 0, background 0 -> -1) with the mask computed inside the tile kernel and written to `mask` (what the border kernel reads);
+// zero_plane (the strength sums) is cleared on the way.  Components are small and sparse: both kinds of border in one launch, as label8 does.
+void label8_positive(hipStream_t s, int *label, int *mask, const float *nms, int *zero_plane, int iw, int ih, int skip_flatten, int nz, size_t zs) {
+  hipLaunchKernelGGL((k_label_tile<3, LT_TY>), dim3(rd_tile_blocks(cdiv(iw, LT_W), cdiv(ih, LT_H), nz)), dim3(64, LT_TY), 0, s, label, (const int *)nullptr, 0, iw, ih, mask, nms, (int *)nullptr, zero_plane, zs, rd_gdim(cdiv(iw, LT_W), cdiv(ih, LT_H), nz));
+  const int nh = ((ih - 1) / LT_H) * iw, nv = ((iw - 1) / LT_W) * ih;
+  const int hb = cdiv(nh, 256), vb = cdiv(nv, 256);
+  if (hb + vb > 0) hipLaunchKernelGGL(k_label_border, dim3(hb + vb, 1, nz), dim3(256), 0, s, label, (const int *)mask, 0, iw, ih, hb, zs);
+  if (skip_flatten) return;
+  const int n = iw * ih;
+  int g = cdiv(n, 256 * 4);
+  hipLaunchKernelGGL(k_label_flatten, dim3(g < 1 ? 1 : g, 1, nz), dim3(256), 0, s, label, n, (int *)nullptr, (int *)nullptr, (int *)nullptr, zs);
+}
+
+// poly kind: filterStrength(thre) + threshold_i_i(0, 0, 1) of poly.cpp:120-121 as the bit plane the polyline stage traces, nz frames per launch
+void poly_mask_bits(hipStream_t s, unsigned long long *bits, const int *label, const int *str, int thre, int iw, int ih, int nz, size_t zs) {
+  hipLaunchKernelGGL(k_poly_mask_bits, dim3(cdiv(iw, 64), cdiv(ih, 4), nz), block2, 0, s, bits, label, str, thre, iw, ih, zs);
 }
 
 // region boundaries (oclrect.cl:373-390) marked into `marks` and their 8-connected components labelled into `label`

@@ -1132,6 +1132,20 @@ __global__ void k_scatter_ids(const rdk::PolyFrames FRS) {
   SPARSE_LOOP(j, nlive) { const int i = s.live[j]; ids[s.pos[i]] = s.id[i]; }
 }
 
+// Result hand-off of the poly kind: the frame's counters ([0, 32): ctr[25] = the single-block kernel gave up) and the first `records` records of its list -
+// header included - written straight into the slot's pinned host block (FRM.pack, device address of pinned host memory) at [64, 64 + 14 * records): the
+// poll finds them there without a copy launch.  Longer lists are fetched by the poll from FRM.lslist.
+__global__ __launch_bounds__(256) void k_poly_handoff(const rdk::PolyFrames FRS, int records) {
+  RD_FRAME;
+  const int *__restrict__ ls = (const int *)FRM.lslist;
+  int *__restrict__ pack = FRM.pack;
+  const int n = ls[0];
+  const int m = (n + 1 < records ? n + 1 : records) * 14;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < 32) pack[t] = s.ctr[t];
+  for (int i = t; i < m; i += gridDim.x * blockDim.x) pack[64 + i] = ls[i];
+}
+
 template <typename T> T *dalloc(size_t n) { void *p = nullptr; if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) return nullptr; return (T *)p; }
 
 }  // namespace
@@ -1239,6 +1253,14 @@ void polyline(hipStream_t st, const PolyFrame *frames_host, int nb, int lslist_b
   hipLaunchKernelGGL(k_refine1, sg, sb, 0, st, frames, maxrec, iw);
   hipLaunchKernelGGL(k_refine2, sg, sb, 0, st, frames, maxrec);
   hipLaunchKernelGGL(k_refine3, dim3(1, 1, nb), dim3(1024), 0, st, frames, maxrec);
+}
+
+// the poly kind's hand-off of nb frames (k_poly_handoff): records = capacity of each frame's pinned block in records, header included
+void polyline_handoff(hipStream_t st, const PolyFrame *frames_host, int nb, int records) {
+  const PolyFrames frames = pack_frames(frames_host, nb);
+  int g = cdiv(records * 14, 256);
+  if (g > 128) g = 128;
+  hipLaunchKernelGGL(k_poly_handoff, dim3(g < 1 ? 1 : g, 1, nb), dim3(256), 0, st, frames, records);
 }
 
 // per-pixel segment ids as a dense plane (lsIdOut = frames[z].ids) from the compact state

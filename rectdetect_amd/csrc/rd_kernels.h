@@ -74,6 +74,10 @@ void label8_flatten(hipStream_t s, int *label, int n);      // phase 3 alone, la
 // add (optional): a plane whose non-zero elements are added to out element by element in the same launch (out = zeros + add + sums)
 void calc_strength(hipStream_t s, int *out, const float *edge, int *label, int iw, int ih, const int8_t *add = nullptr, int flatten = 0, int nz = 1, size_t zs = 0);   // add (optional): a 0/1 byte plane added to the sums (H1)
 void filter_strength(hipStream_t s, int *label, const int *str, int thre, int iw, int ih);
+// poly kind (rd_polyline_detector_create): components of nms > 0 (background -> -1, label = smallest pixel index, no tidy) in the tile kernel, which writes the
+// 0/1 mask plane the border kernel reads and clears zero_plane (the strength sums); then filterStrength(thre) + `label > 0` as a bit plane for the polyline stage
+void label8_positive(hipStream_t s, int *label, int *mask, const float *nms, int *zero_plane, int iw, int ih, int skip_flatten, int nz = 1, size_t zs = 0);
+void poly_mask_bits(hipStream_t s, unsigned long long *bits, const int *label, const int *str, int thre, int iw, int ih, int nz = 1, size_t zs = 0);
 // strong mask at t_strong (two copies) + edge mask at t_edge (int, int8), both from the unfiltered labels, + filter_strength at t_strong (label in place), one pass; t_edge <= t_strong
 // prev (optional): a 0/1 byte plane added to the sums element by element (sum of label l = str[l] + prev[l]: quirk H1 without a pass of its own); strong2 != prev
 // the strong masks of the nz frames of a group launch (frame z = sequence number t0 + z, planes zs bytes apart, masks in ring planes (t0 + z + 1) mod nring) in one launch
@@ -129,6 +133,8 @@ void poly_scratch_destroy(PolyScratch *ps);
 const int *poly_scratch_counters(const PolyScratch *ps);   // device pointer: [0] chain pixels, [1] chains, [2+r] split candidates of round r
 // frames: nb descriptors (host memory); frames[z].ring_src: plane whose 2-px frame ring supplies the stale ring values (null -> ring_const)
 void polyline(hipStream_t s, const PolyFrame *frames, int nb, int lslist_bytes, int ring_const, float minerror, int sizeThre, int iw, int ih, int mode);
+// poly kind: counters + the first `records` records of each frame's list (header included) into frames[z].pack (pinned host memory)
+void polyline_handoff(hipStream_t s, const PolyFrame *frames, int nb, int records);
 // materialises the dense id planes frames[z].ids from the compact state
 void polyline_ids(hipStream_t s, const PolyFrame *frames, int nb, int n);
 
