@@ -66,6 +66,29 @@ void rd_release_cached_streams(int device);
 #define RD_FRAME_HOST_PINNED 2
 long rd_detector_enqueue(rd_detector *d, const void *frame, int ws, int on_device);
 
+/* Enqueue one frame in another pixel format: what video decoders, renderers and image libraries hand out, without a BGR copy of it.
+ * planes[k] / pitches[k]: plane k and its row stride in bytes (planes a format does not use are ignored).  on_device, the frame kinds and their contracts as for
+ * rd_detector_enqueue (host: copied before the call returns; device and pinned: read in place until the frame's poll; under RD_FRAME_HOST_PINNED every plane
+ * the format uses must be pinned - fatal otherwise, as is a call with nslots frames already in flight).  Both detector kinds; the format may change from frame to frame.
+ * Returns the frame's sequence number, or -1 for an argument error, in which case nothing was enqueued: an unknown format or on_device, a NULL plane the format
+ * uses, a pitch smaller than its plane's row, NV12 / I420 with an odd iw or ih.  RD_PIX_BGR is rd_detector_enqueue(d, planes[0], pitches[0], on_device).
+ *
+ * Conversion contract.  The packed formats are a permutation of their bytes into (B, G, R).  NV12 and I420 are BT.601 limited range with 2x2 nearest chroma
+ * (OpenCV's cvtColor COLOR_YUV2BGR_NV12 / _I420 fixed point): pixel (x, y) takes U and V at chroma (x/2, y/2) and, in int32 with arithmetic shifts,
+ *   u = U - 128;  v = V - 128;  yy = max(Y - 16, 0) * 1220542
+ *   R = clamp((yy + 1673527*v             + (1 << 19)) >> 20, 0, 255)
+ *   G = clamp((yy -  852492*v - 409993*u  + (1 << 19)) >> 20, 0, 255)
+ *   B = clamp((yy + 2116026*u             + (1 << 19)) >> 20, 0, 255)
+ * The (B, G, R) goes through the detector's sRGB -> Lab arithmetic unchanged: the result for such a frame is bit-identical to the result for the BGR frame
+ * this formula gives. */
+#define RD_PIX_BGR  0   /* 3 bytes per pixel B,G,R: what rd_detector_enqueue takes */
+#define RD_PIX_RGB  1   /* 3 bytes per pixel R,G,B */
+#define RD_PIX_BGRA 2   /* 4 bytes per pixel B,G,R,A (A ignored) */
+#define RD_PIX_RGBA 3   /* 4 bytes per pixel R,G,B,A (A ignored) */
+#define RD_PIX_NV12 4   /* plane 0: Y, iw x ih; plane 1: U,V interleaved, iw bytes x ih/2 rows */
+#define RD_PIX_I420 5   /* plane 0: Y, iw x ih; plane 1: U, plane 2: V, each iw/2 x ih/2 */
+long rd_detector_enqueue_planes(rd_detector *d, int format, const void *const planes[3], const int pitches[3], int on_device);
+
 /* Result of the oldest frame not yet polled: malloc'd array of rect_t-compatible records (176 bytes each, element 0
  * holds nItems), owned by the caller.  Blocks until that frame is done. */
 void *rd_detector_poll(rd_detector *d, double tanAOV);

@@ -25,6 +25,10 @@ LS_DTYPE = np.dtype([("x0", "<f4"), ("y0", "<f4"), ("x1", "<f4"), ("y1", "<f4"),
                      ("polyid", "<i4"), ("npix", "<i4"), ("level", "<i4")])
 assert RECT_DTYPE.itemsize == 176 and LS_DTYPE.itemsize == 56
 
+# pixel formats of enqueue_planes (rd_detector_enqueue_planes; the conversion contract is in include/rectdetect_hip.h)
+PIX_BGR, PIX_RGB, PIX_BGRA, PIX_RGBA, PIX_NV12, PIX_I420 = range(6)
+PIX_NAMES = {PIX_BGR: "BGR", PIX_RGB: "RGB", PIX_BGRA: "BGRA", PIX_RGBA: "RGBA", PIX_NV12: "NV12", PIX_I420: "I420"}
+
 CL_MEM_READ_WRITE = 1 << 0
 CL_MEM_COPY_HOST_PTR = 1 << 5
 CL_TRUE = 1
@@ -63,6 +67,7 @@ def _declare(L):
         "rd_polyline_detector_create": (vp, [ci, ci, ci, ci, ci, cf, ci]),
         "rd_detector_poll_segments": (vp, [vp, vp]),
         "rd_detector_enqueue": (ctypes.c_long, [vp, vp, ci, ci]),
+        "rd_detector_enqueue_planes": (ctypes.c_long, [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci]),
         "rd_detector_poll": (vp, [vp, cd]),
         "rd_detector_drain": (None, [vp]),
         "rd_detector_set_aperture": (None, [vp, cd]),
@@ -265,6 +270,34 @@ class RectDetector:
         L.dispose_oclimgutil(self.iu)
 
 
+def _enqueue_planes(h, fmt, planes, pitches, on_device, pinned):
+    """rd_detector_enqueue_planes for both detector kinds.  Host frames: numpy arrays (packed formats one HxWxC image; NV12 (Y, UV); I420 (Y, U, V)),
+    pitches from their strides (copied before the call returns).  on_device / pinned: plane ADDRESSES, with `pitches` required.  ValueError on an argument error."""
+    if not isinstance(planes, (list, tuple)):
+        planes = (planes,)
+    planes = list(planes)[:3]
+    if on_device or pinned:
+        if pitches is None:
+            raise ValueError("enqueue_planes: pitches are required for device / pinned planes")
+        ptrs = [int(p) if p else None for p in planes]
+        pitch = list(pitches)
+    else:
+        arrs = []
+        for p in planes:
+            a = np.asarray(p, dtype=np.uint8)
+            if a.ndim < 2 or a.strides[0] < 0 or a.strides[-1] != 1 or (a.ndim == 3 and a.strides[1] != a.shape[2]):
+                a = np.ascontiguousarray(a)      # (rows need not be adjacent - the pitch says where the next one starts - but a row's bytes must be)
+            arrs.append(a)
+        ptrs = [a.ctypes.data for a in arrs]
+        pitch = [a.strides[0] for a in arrs] if pitches is None else list(pitches)
+    ptrs += [None] * (3 - len(ptrs))
+    pitch += [0] * (3 - len(pitch))
+    r = lib().rd_detector_enqueue_planes(h, int(fmt), (ctypes.c_void_p * 3)(*ptrs), (ctypes.c_int * 3)(*pitch), 1 if on_device else (2 if pinned else 0))
+    if r == -1:
+        raise ValueError("rd_detector_enqueue_planes: invalid arguments (format %r, pitches %r)" % (fmt, pitch))
+    return r
+
+
 class Detector:
     """The rd_detector extension: frames may already live in HBM, several frames in flight."""
 
@@ -285,6 +318,11 @@ class Detector:
         a = np.ascontiguousarray(frame)
         self._keep = a
         return lib().rd_detector_enqueue(self.h, a.ctypes.data, a.strides[0] if ws is None else ws, 0)
+
+    def enqueue_planes(self, fmt, planes, pitches=None, on_device=False, pinned=False):
+        """a frame in pixel format `fmt` (PIX_*): numpy planes (HxWxC; NV12 (Y, UV); I420 (Y, U, V)), copied before the call returns - or, with on_device / pinned,
+        the planes' addresses and their `pitches`, read in place until the frame's poll returned.  ValueError on an argument error (nothing enqueued)."""
+        return _enqueue_planes(self.h, fmt, planes, pitches, on_device, pinned)
 
     def poll(self, tan_aov):
         return _take_rects(lib().rd_detector_poll(self.h, float(tan_aov)))
@@ -353,6 +391,10 @@ class PolylineDetector:
         a = np.ascontiguousarray(frame)
         self._keep = a
         return lib().rd_detector_enqueue(self.h, a.ctypes.data, a.strides[0] if ws is None else ws, 0)
+
+    def enqueue_planes(self, fmt, planes, pitches=None, on_device=False, pinned=False):
+        """as Detector.enqueue_planes"""
+        return _enqueue_planes(self.h, fmt, planes, pitches, on_device, pinned)
 
     def poll(self, ids=False):
         """(segments[LS_DTYPE] with the header record, per-pixel segment ids or None) of the oldest frame not yet polled"""

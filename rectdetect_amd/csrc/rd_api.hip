@@ -328,6 +328,10 @@ struct Slot {
   int *h_pack, *h_pack_dev;                // everything the host needs from a frame, assembled by the device in pinned host memory (host / device address)
   long seq;
   int ws;
+  // the frame's pixel format (RD_PIX_*; calloc'd: RD_PIX_BGR).  Other formats (rd_detector_enqueue_planes) keep their planes and row strides here, src = pl[0] and
+  // ws = pitch[0]; a host frame's planes are packed into bgr
+  int fmt;
+  const uint8_t *pl[3]; int pitch[3];
   // captured launch sequences (three segments, see enqueue_frame) and the stride they were captured for
   hipGraphExec_t gexec[3]; int graph_ws;   // gexec[2] unused: the last segment has one graph per round budget (gexec2)
   hipGraphExec_t gexec2[3 * RD_NBUDGETS];  // [round budget index][polyline mode]
@@ -385,6 +389,7 @@ struct rd_detector {
   // on an event of their own (ev_redo), never on the stream.
   pthread_mutex_t launch_mu;
   const void *pinned_lo, *pinned_hi;        // the last caller buffer that was verified to be pinned host memory (RD_FRAME_HOST_PINNED)
+  const void *pinned_pl[4][2]; unsigned pinned_pl_next;   // the same for the planes of rd_detector_enqueue_planes: the last 4 plane ranges verified (a frame's planes may lie in allocations of their own)
   const void *probed[2]; int probed_pinned[2];      // RD_FRAME_HOST, one or two frames in flight: the last two frame pointers asked about (a loop alternates between its two pages) and the answer
   long n_frames_pinned, n_frames_copied;     // host frames that travelled straight from the caller's pinned memory / through the detector's own staging pages
   long n_unsettled;          // frames whose region merge was still changing after RD_REGION_MAX_LAUNCHES launches (none on any fixture)
@@ -801,8 +806,21 @@ static void run_segment(rd_detector *d, Slot *s, int ws, int seg, hipStream_t st
   RD_HIP(hipGraphLaunch(*ge, lst));
 }
 
+// The first kernel of a frame in another format than BGR (rd_detector_enqueue_planes): the nz frames of the slots from s on, which share format and pitches.
+static void pix_front(rd_detector *d, Slot *s, int nz, hipStream_t st) {
+  const uint8_t *planes[RD_ZB_MAX][3];
+  for (int i = 0; i < nz; i++) for (int k = 0; k < 3; k++) planes[i][k] = s[i].pl[k];
+  rdk::pix2plab_transposed(st, s->fmt, s->plab0, s->tr, planes, s->pitch, d->iw, d->ih, nz, nz > 1 ? d->slot_pitch : 0);
+}
+
+// may two frames of a group share one front launch?  (one format, one set of row strides)
+static bool same_layout(const Slot *a, const Slot *b) {
+  if (a->fmt != b->fmt || a->ws != b->ws) return false;
+  return a->fmt == RD_PIX_BGR || (a->pitch[1] == b->pitch[1] && a->pitch[2] == b->pitch[2]);
+}
+
 static void enqueue_frame(rd_detector *d, Slot *s, int ws) {
-  if (d->use_graph && s->graph_ws != ws) {
+  if (d->use_graph && s->fmt == RD_PIX_BGR && s->graph_ws != ws) {      // (other formats leave the key alone: the segments read no frame)
     for (int k = 0; k < 3; k++) if (s->gexec[k]) { RD_HIP(hipGraphExecDestroy(s->gexec[k])); s->gexec[k] = NULL; }
     for (int k = 0; k < 3 * RD_NBUDGETS; k++) if (s->gexec2[k]) { RD_HIP(hipGraphExecDestroy(s->gexec2[k])); s->gexec2[k] = NULL; }
     s->graph_ws = ws;
@@ -810,7 +828,8 @@ static void enqueue_frame(rd_detector *d, Slot *s, int ws) {
   RD_HIP(hipEventRecord(s->ev_begin, s->st));
   s->watch_begin = s->ev_begin; s->watch_done = s->ev_done;
   s->group_n = 1;
-  rdk::bgr2plab_transposed(s->st, s->plab0, s->tr, s->src, d->iw, d->ih, ws);
+  if (s->fmt == RD_PIX_BGR) rdk::bgr2plab_transposed(s->st, s->plab0, s->tr, s->src, d->iw, d->ih, ws);
+  else pix_front(d, s, 1, s->st);
   run_segment(d, s, ws, 0);
   if (d->have_last_strong) RD_HIP(hipStreamWaitEvent(s->st, d->last_strong, 0));
   frame_strong(d, s, s->st);
@@ -890,7 +909,7 @@ static void slot_submitted(rd_detector *d, Slot *s);
 static void group_launch(rd_detector *d, int g0) {
   const int zb = d->zb;
   int cnt = 0, same_ws = 1;
-  for (int i = g0; i < g0 + zb && i < d->nslots; i++) { Slot *s = &d->slots[i]; if (s->pending_dense) { cnt++; if (s->ws != d->slots[g0].ws) same_ws = 0; } }
+  for (int i = g0; i < g0 + zb && i < d->nslots; i++) { Slot *s = &d->slots[i]; if (s->pending_dense) { cnt++; if (!same_layout(s, &d->slots[g0])) same_ws = 0; } }
   if (cnt == 0) return;
   // Host frames travelled when they were handed over, one after the other on the detector's upload stream (rd_detector_enqueue).  The launching thread waits for that
   // stream here - at most for the transfer just issued, 0.1 ms, on a thread that has nothing else to do until the next group completes - and what the host has seen
@@ -915,7 +934,7 @@ static void group_launch(rd_detector *d, int g0) {
   Slot *lead = &d->slots[g0];
   hipStream_t st = group_stream(d, g0);
   const int ws = lead->ws;
-  if (d->use_graph && lead->gz_ws != ws) {
+  if (d->use_graph && lead->fmt == RD_PIX_BGR && lead->gz_ws != ws) {
     if (lead->gz0) { RD_HIP(hipGraphExecDestroy(lead->gz0)); lead->gz0 = NULL; }
     for (int k = 0; k < 3 * RD_NBUDGETS; k++) if (lead->gz2[k]) { RD_HIP(hipGraphExecDestroy(lead->gz2[k])); lead->gz2[k] = NULL; }
     lead->gz_ws = ws;
@@ -931,7 +950,8 @@ static void group_launch(rd_detector *d, int g0) {
     if (i == 0 || !one_event) RD_HIP(hipEventRecord(s->ev_begin, st));
     s->watch_begin = one_event ? lead->ev_begin : s->ev_begin; s->watch_done = one_event ? lead->ev_done : s->ev_done;
   }
-  rdk::bgr2plab_transposed(st, lead->plab0, lead->tr, srcs, d->iw, d->ih, ws, zb, d->slot_pitch);
+  if (lead->fmt == RD_PIX_BGR) rdk::bgr2plab_transposed(st, lead->plab0, lead->tr, srcs, d->iw, d->ih, ws, zb, d->slot_pitch);
+  else pix_front(d, lead, zb, st);
   run_group_segment(d, lead, zb, 0, st);
   // the strong masks: each frame's on top of its predecessor's (H1) - one launch for the group where its planes allow 16-byte accesses (the mask of the frame before
   // only decides sums that stand one below a threshold, and is then evaluated on the spot: k_strength_masks_group), else frame by frame
@@ -1239,7 +1259,8 @@ static void poly_enqueue_frame(rd_detector *d, Slot *s, int ws) {
   RD_HIP(hipEventRecord(s->ev_begin, s->st));
   s->watch_begin = s->ev_begin; s->watch_done = s->ev_done;
   s->group_n = 1;
-  rdk::bgr2plab_transposed(s->st, s->plab0, s->tr, s->src, d->iw, d->ih, ws);      // (outside the graph: its source changes from frame to frame)
+  if (s->fmt == RD_PIX_BGR) rdk::bgr2plab_transposed(s->st, s->plab0, s->tr, s->src, d->iw, d->ih, ws);      // (outside the graph: its source changes from frame to frame)
+  else pix_front(d, s, 1, s->st);
   s->poly_mode = current_poly_mode(d);
   poly_run(d, s, 1, s->st, s->poly_mode);
   RD_HIP(hipEventRecord(s->ev_done, s->st));
@@ -1250,7 +1271,7 @@ static void poly_enqueue_frame(rd_detector *d, Slot *s, int ws) {
 static void poly_group_launch(rd_detector *d, int g0) {
   const int zb = d->zb;
   int cnt = 0, same_ws = 1;
-  for (int i = g0; i < g0 + zb && i < d->nslots; i++) { Slot *s = &d->slots[i]; if (s->pending_dense) { cnt++; if (s->ws != d->slots[g0].ws) same_ws = 0; } }
+  for (int i = g0; i < g0 + zb && i < d->nslots; i++) { Slot *s = &d->slots[i]; if (s->pending_dense) { cnt++; if (!same_layout(s, &d->slots[g0])) same_ws = 0; } }
   if (cnt == 0) return;
   bool travelled = false;
   for (int i = g0; i < g0 + zb && i < d->nslots; i++) { Slot *s = &d->slots[i]; if (s->pending_dense && s->src == s->bgr && s->uploaded_early) travelled = true; }
@@ -1279,7 +1300,8 @@ static void poly_group_launch(rd_detector *d, int g0) {
     s->group_n = zb; s->poly_mode = pm;
   }
   RD_HIP(hipEventRecord(lead->ev_begin, st));
-  rdk::bgr2plab_transposed(st, lead->plab0, lead->tr, srcs, d->iw, d->ih, ws, zb, d->slot_pitch);
+  if (lead->fmt == RD_PIX_BGR) rdk::bgr2plab_transposed(st, lead->plab0, lead->tr, srcs, d->iw, d->ih, ws, zb, d->slot_pitch);
+  else pix_front(d, lead, zb, st);
   poly_run(d, lead, zb, st, pm);
   RD_HIP(hipEventRecord(lead->ev_done, st));
   rdrt::check_launch("polyline frames, group launch");
@@ -1448,6 +1470,39 @@ static bool host_buffer_is_pinned(rd_detector *d, const void *frame) {
   return pinned;
 }
 
+// what follows the hand-over of a frame (rd_detector_enqueue, rd_detector_enqueue_planes): its launches - now, or with its group - and the caller's wait for the copy engine
+static long enqueue_launch(rd_detector *d, Slot *s, int ws, Slot *wait_upload, struct timespec ts0) {
+  if (d->zb > 1) {      // group mode: launched together with the other frames of its group, once that is full (or a poll needs one of them)
+    const int si = (int)(s - d->slots);
+    s->pending_dense = 1;
+    // (the last group of slots may be short - nslots need not be a multiple of zb - and is launched when ITS last slot is filled: every group
+    //  is launched the moment its last frame arrives, so frames reach the device in sequence order and at most one group is ever waiting)
+    if (si % d->zb == d->zb - 1 || si == d->nslots - 1) { if (d->kind == RD_KIND_POLY) poly_group_launch(d, si / d->zb * d->zb); else group_launch(d, si / d->zb * d->zb); }
+  } else if (d->kind == RD_KIND_POLY) {
+  poly_enqueue_frame(d, s, ws);
+  } else {
+  enqueue_frame(d, s, ws);
+  }
+  if (d->zb > 1) ;
+  else if (d->batch == 1) slot_submitted(d, s);
+  else {
+    const int si = (int)(s - d->slots);
+    if (si % d->batch == d->batch - 1 || si == d->nslots - 1) {      // the group is complete
+      // Launched right away, the sparse stages would sit in their stream between this group's dense stages and the next one's, waiting
+      // for the slowest of the group's four streams: a barrier per group (measured: 10 % slower than no batching).  One group later,
+      // everything they wait for is long done and the stream they land on has the next group's dense work queued in front of them.
+      if (d->defer) {
+        const int prev = d->deferred_slot;
+        d->deferred_slot = si;
+        if (prev >= 0) sparse_flush(d, prev);
+      } else sparse_flush(d, si);
+    }
+  }
+  if (wait_upload) RD_HIP(hipEventSynchronize(wait_upload->ev_upload));      // (the caller may touch its buffer again)
+  { struct timespec ts1; clock_gettime(CLOCK_MONOTONIC, &ts1); d->host_enqueue_ns += (ts1.tv_sec - ts0.tv_sec) * 1000000000L + (ts1.tv_nsec - ts0.tv_nsec); }
+  return d->next_enqueue++;
+}
+
 long rd_detector_enqueue(rd_detector *d, const void *frame, int ws, int on_device) {
   if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_enqueue: bad handle\n");
   if (d->next_enqueue - d->next_poll >= d->nslots) exitf(-1, "rd_detector_enqueue: %d frames already in flight (poll first)\n", d->nslots);
@@ -1455,7 +1510,7 @@ long rd_detector_enqueue(rd_detector *d, const void *frame, int ws, int on_devic
   RD_HIP(hipSetDevice(d->device));
   struct timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
   Slot *s = &d->slots[d->next_enqueue % d->nslots];
-  s->seq = d->next_enqueue; s->ws = ws;
+  s->seq = d->next_enqueue; s->ws = ws; s->fmt = RD_PIX_BGR;
   const size_t bytes = (size_t)ws * d->ih;
   Slot *wait_upload = NULL;
   if (on_device == RD_FRAME_DEVICE) s->src = (const uint8_t *)frame;      // read where it lies (the caller keeps it valid until the frame's poll returned)
@@ -1527,35 +1582,121 @@ long rd_detector_enqueue(rd_detector *d, const void *frame, int ws, int on_devic
       s->uploaded_early = 1;      // (no event here: group_launch records ONE behind the uploads of all its frames)
     }
   }
-  if (d->zb > 1) {      // group mode: launched together with the other frames of its group, once that is full (or a poll needs one of them)
-    const int si = (int)(s - d->slots);
-    s->pending_dense = 1;
-    // (the last group of slots may be short - nslots need not be a multiple of zb - and is launched when ITS last slot is filled: every group
-    //  is launched the moment its last frame arrives, so frames reach the device in sequence order and at most one group is ever waiting)
-    if (si % d->zb == d->zb - 1 || si == d->nslots - 1) { if (d->kind == RD_KIND_POLY) poly_group_launch(d, si / d->zb * d->zb); else group_launch(d, si / d->zb * d->zb); }
-  } else if (d->kind == RD_KIND_POLY) {
-  poly_enqueue_frame(d, s, ws);
-  } else {
-  enqueue_frame(d, s, ws);
-  }
-  if (d->zb > 1) ;
-  else if (d->batch == 1) slot_submitted(d, s);
-  else {
-    const int si = (int)(s - d->slots);
-    if (si % d->batch == d->batch - 1 || si == d->nslots - 1) {      // the group is complete
-      // Launched right away, the sparse stages would sit in their stream between this group's dense stages and the next one's, waiting
-      // for the slowest of the group's four streams: a barrier per group (measured: 10 % slower than no batching).  One group later,
-      // everything they wait for is long done and the stream they land on has the next group's dense work queued in front of them.
-      if (d->defer) {
-        const int prev = d->deferred_slot;
-        d->deferred_slot = si;
-        if (prev >= 0) sparse_flush(d, prev);
-      } else sparse_flush(d, si);
+  return enqueue_launch(d, s, ws, wait_upload, ts0);
+}
+
+// ---- frames in other pixel formats (rd_detector_enqueue_planes)
+// The planes a format uses, their row bytes and rows; and the layout of a host frame packed into a slot's buffers (row strides rounded up to 4 bytes, so that
+// the front kernel reads them a dword per lane; every format then still fits the 4 bytes per pixel of bgr / h_bgr).
+struct PixLayout { int np, row[3], rows[3], pitch[3]; size_t off[3], bytes; };
+static PixLayout pix_layout(int fmt, int iw, int ih) {
+  PixLayout L;
+  memset(&L, 0, sizeof(L));
+  const int bpp = fmt == RD_PIX_BGR || fmt == RD_PIX_RGB ? 3 : 4;
+  if (fmt <= RD_PIX_RGBA) { L.np = 1; L.row[0] = iw * bpp; L.rows[0] = ih; }
+  else if (fmt == RD_PIX_NV12) { L.np = 2; L.row[0] = L.row[1] = iw; L.rows[0] = ih; L.rows[1] = ih / 2; }
+  else { L.np = 3; L.row[0] = iw; L.rows[0] = ih; L.row[1] = L.row[2] = iw / 2; L.rows[1] = L.rows[2] = ih / 2; }
+  for (int k = 0; k < L.np; k++) { L.pitch[k] = (L.row[k] + 3) & ~3; L.off[k] = L.bytes; L.bytes += (size_t)L.pitch[k] * L.rows[k]; }
+  return L;
+}
+
+// a host frame's pieces (byte ranges of the packed layout) gathered from the caller's planes by the caller and whichever helper threads are awake, uploaded in order
+// as they complete (upload_progress; the same piecewise hand-over as a BGR frame's)
+struct PackJob { UploadJob u; PixLayout L; const uint8_t *src[3]; int spitch[3]; };
+static void pack_range(const PackJob *j, size_t o, size_t end) {
+  for (int k = 0; k < j->L.np; k++) {
+    const size_t p0 = j->L.off[k], pp = (size_t)j->L.pitch[k];
+    const size_t a = o > p0 ? o : p0, b = end < p0 + pp * j->L.rows[k] ? end : p0 + pp * j->L.rows[k];
+    for (size_t r = a < b ? (a - p0) / pp : 0, at = a; at < b; r++) {      // rows of plane k that meet [a, b)
+      const size_t rs = p0 + r * pp, re = rs + (size_t)j->L.row[k];
+      const size_t c0 = at > rs ? at : rs, c1 = b < re ? b : re;
+      if (c0 < c1) {
+        if (j->u.nt) rd_copy_to_staging(j->u.dst + c0, j->src[k] + r * j->spitch[k] + (c0 - rs), c1 - c0);
+        else memcpy(j->u.dst + c0, j->src[k] + r * j->spitch[k] + (c0 - rs), c1 - c0);
+      }
+      at = rs + pp;
     }
   }
-  if (wait_upload) RD_HIP(hipEventSynchronize(wait_upload->ev_upload));      // (the caller may touch its buffer again)
-  { struct timespec ts1; clock_gettime(CLOCK_MONOTONIC, &ts1); d->host_enqueue_ns += (ts1.tv_sec - ts0.tv_sec) * 1000000000L + (ts1.tv_nsec - ts0.tv_nsec); }
-  return d->next_enqueue++;
+}
+static void pack_copy_piece(void *ctx, int i) {
+  PackJob *j = (PackJob *)ctx;
+  const size_t o = (size_t)i * j->u.piece, m = j->u.bytes - o < j->u.piece ? j->u.bytes - o : j->u.piece;
+  pack_range(j, o, o + m);
+  __atomic_store_n(&j->u.ready[i], 1, __ATOMIC_RELEASE);
+}
+static void pack_progress(void *ctx) { upload_progress(&((PackJob *)ctx)->u); }
+
+long rd_detector_enqueue_planes(rd_detector *d, int format, const void *const planes[3], const int pitches[3], int on_device) {
+  if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_enqueue_planes: bad handle\n");
+  // argument errors: -1, nothing enqueued
+  if (format < RD_PIX_BGR || format > RD_PIX_I420 || !planes || !pitches) return -1;
+  if (on_device != RD_FRAME_HOST && on_device != RD_FRAME_DEVICE && on_device != RD_FRAME_HOST_PINNED) return -1;
+  if (format >= RD_PIX_NV12 && ((d->iw | d->ih) & 1)) return -1;
+  const PixLayout L = pix_layout(format, d->iw, d->ih);
+  for (int k = 0; k < L.np; k++) if (!planes[k] || pitches[k] < L.row[k]) return -1;
+  if (format == RD_PIX_BGR) return rd_detector_enqueue(d, planes[0], pitches[0], on_device);
+  if (d->next_enqueue - d->next_poll >= d->nslots) exitf(-1, "rd_detector_enqueue_planes: %d frames already in flight (poll first)\n", d->nslots);
+  RD_HIP(hipSetDevice(d->device));
+  struct timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
+  Slot *s = &d->slots[d->next_enqueue % d->nslots];
+  s->seq = d->next_enqueue; s->fmt = format;
+  for (int k = 0; k < 3; k++) { s->pl[k] = NULL; s->pitch[k] = 0; }
+  if (on_device == RD_FRAME_DEVICE) {      // read where they lie
+    for (int k = 0; k < L.np; k++) { s->pl[k] = (const uint8_t *)planes[k]; s->pitch[k] = pitches[k]; }
+  } else {      // host frames: packed into the slot's buffers, one plane after the other
+    for (int k = 0; k < L.np; k++) { s->pl[k] = s->bgr + L.off[k]; s->pitch[k] = L.pitch[k]; }
+    s->uploaded_early = 0;
+    hipStream_t ust = s->st;
+    if (d->zb > 1) {      // (group mode: on the detector's upload stream, one transfer queued at a time, no event: as rd_detector_enqueue's frames - see group_launch)
+      if (!d->st_upload) d->st_upload = pooled_stream(d->device);
+      ust = d->st_upload;
+      s->uploaded_early = 1;
+    }
+    if (on_device == RD_FRAME_HOST_PINNED) {      // every plane pinned; the copy engine gathers them
+      for (int k = 0; k < L.np; k++) {
+        const size_t span = (size_t)pitches[k] * (L.rows[k] - 1) + L.row[k];
+        const void *lo = planes[k], *hi = (const char *)planes[k] + span;
+        bool known = false;      // (one look per plane range, not per frame: a capture loop reuses its pages)
+        for (int e = 0; e < 4 && !known; e++) known = lo >= d->pinned_pl[e][0] && hi <= d->pinned_pl[e][1];
+        if (known) continue;
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, planes[k]) != hipSuccess || at.type != hipMemoryTypeHost) { (void)hipGetLastError(); exitf(-1, "rd_detector_enqueue_planes: RD_FRAME_HOST_PINNED needs pinned host memory (rd_host_alloc, allocatePinnedMemory, hipHostMalloc, hipHostRegister); plane %d at %p is not\n", k, planes[k]); }
+        const unsigned e = d->pinned_pl_next++ & 3;
+        d->pinned_pl[e][0] = lo; d->pinned_pl[e][1] = hi;
+      }
+      if (d->zb > 1) RD_HIP(hipStreamSynchronize(ust));
+      for (int k = 0; k < L.np; k++) {
+        if (pitches[k] == L.row[k] && L.row[k] == L.pitch[k]) RD_HIP(hipMemcpyAsync(s->bgr + L.off[k], planes[k], (size_t)L.row[k] * L.rows[k], hipMemcpyHostToDevice, ust));
+        else RD_HIP(hipMemcpy2DAsync(s->bgr + L.off[k], L.pitch[k], planes[k], pitches[k], L.row[k], L.rows[k], hipMemcpyHostToDevice, ust));
+      }
+      d->n_frames_pinned++;
+    } else {
+      static const bool nt_copy = RD_LAB_INT("RD_NT_COPY", 1) != 0;
+      PackJob j;
+      j.L = L;
+      for (int k = 0; k < 3; k++) { j.src[k] = (const uint8_t *)planes[k]; j.spitch[k] = pitches[k]; }
+      UploadJob &u = j.u;
+      u.dst = (char *)s->h_bgr; u.src = NULL; u.dev = (char *)s->bgr; u.bytes = L.bytes; u.st = ust; u.nt = nt_copy; u.uploaded = 0;
+      if (d->zb > 1) {      // (group mode: the caller's thread packs, then the frame travels at once)
+        pack_range(&j, 0, L.bytes);
+        RD_HIP(hipStreamSynchronize(ust));
+        RD_HIP(hipMemcpyAsync(s->bgr, s->h_bgr, L.bytes, hipMemcpyHostToDevice, ust));
+      } else {      // (a single frame: in pieces, as rd_detector_enqueue's)
+        const bool helpers = d->post_helpers > 0;
+        if (helpers) rd_post_helpers_arm();
+        const int npieces = helpers ? 16 : 4;
+        u.piece = ((L.bytes + npieces - 1) / npieces + 4095) & ~(size_t)4095;
+        u.n = (int)((L.bytes + u.piece - 1) / u.piece);
+        for (int i = 0; i < u.n; i++) u.ready[i] = 0;
+        rd_helpers_run(pack_copy_piece, &j, u.n, pack_progress);
+        pack_progress(&j);
+        if (u.uploaded != u.n) exitf(-1, "rd_detector_enqueue_planes: internal error (pieces of the frame left behind)\n");
+      }
+      d->n_frames_copied++;
+    }
+  }
+  s->src = s->pl[0]; s->ws = s->pitch[0];
+  return enqueue_launch(d, s, s->ws, NULL, ts0);
 }
 
 void *rd_detector_poll(rd_detector *d, double tanAOV) {

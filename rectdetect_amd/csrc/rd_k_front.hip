@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include "rd_device.h"
 #include "rd_kernels.h"
+#include "rectdetect_hip.h"
 
 #define RD_LUT_ATTR __device__
 #include "rd_luts.h"
@@ -28,6 +29,24 @@ inline int grid1(int n) { int g = cdiv(n, 256); return g < 1 ? 1 : g; }
 // 34476 / 30097 = (int)(32768/xn + 0.5f), (int)(32768/zn + 0.5f); the three LUTs are staged in LDS because every
 // lane indexes them with a different colour.
 __device__ __forceinline__ int lerp_lut(const unsigned short *t, int c) { return t[c >> 8] * (256 - (c & 255)) + t[(c >> 8) + 1] * (c & 255); }
+
+// one pixel (b, g, r bytes) -> packed Lab, with the three tables in LDS: the arithmetic of k_bgr2plab_t below, which keeps its own copy (its gfx950
+// code, which the profiles and notes refer to, changes when it calls this)
+__device__ __forceinline__ uint32_t plab_of(const unsigned short *s_s2l, const unsigned short *s_cf, const unsigned short *s_cf2, int b, int g, int r) {
+  const int ib = s_s2l[b], ig = s_s2l[g], ir = s_s2l[r];
+  const int cx = (((ir * 6758 + ig * 5859 + ib * 2956 + (1 << 14)) >> 15) * 34476 + (1 << 10)) >> 11;
+  const int cy = ((ir * 3484 + ig * 11717 + ib * 1182) + (1 << 10)) >> 11;
+  const int cz = (((ir * 317 + ig * 1953 + ib * 15569 + (1 << 14)) >> 15) * 30097 + (1 << 10)) >> 11;
+  const int cl = ((lerp_lut(s_cf2, cy) >> 12) + 1) >> 1;
+  const int fx = lerp_lut(s_cf, cx), fy = lerp_lut(s_cf, cy), fz = lerp_lut(s_cf, cz);
+  const int fxy = (fx - fy + (1 << 7)) >> 8, fyz = (fy - fz + (1 << 7)) >> 8;
+  const int ca = (fxy * 8031 + (134744072 + (1 << 17))) >> 18;
+  const int cb = (fyz * 3213 + (134744072 + (1 << 17))) >> 18;
+  uint32_t v = clampu((uint32_t)cb, 0u, 1023u);
+  v = (v << 10) | clampu((uint32_t)ca, 0u, 1023u);
+  v = (v << 12) | clampu((uint32_t)cl, 0u, 4095u);
+  return v;
+}
 
 __global__ __launch_bounds__(256) void k_bgr2plab(uint32_t *__restrict__ out, const uint8_t *__restrict__ bgr, int iw, int ih, int ws) {
   __shared__ unsigned short s_s2l[RD_LUT_S2L_N], s_cf[RD_LUT_CF_N], s_cf2[RD_LUT_CF_N];
@@ -101,6 +120,107 @@ __global__ __launch_bounds__(256) void k_bgr2plab_t(uint32_t *__restrict__ out, 
     v = (v << 12) | clampu((uint32_t)cl, 0u, 4095u);
     out[y * iw + x] = v;
     tile[0][r][threadIdx.x] = (unsigned short)(v & 4095u); tile[1][r][threadIdx.x] = (unsigned short)((v >> 12) & 1023u); tile[2][r][threadIdx.x] = (unsigned short)((v >> 22) & 1023u);
+  }
+  __syncthreads();
+  for (int r = rd_ty(); r < 64; r += 4) {
+    const int ox = y0 + threadIdx.x, oy = x0 + r;   // output planes are ih wide, iw tall
+    if (ox < ih && oy < iw)
+      for (int k = 0; k < 3; k++) ((unsigned short *)dst.p[k])[(size_t)oy * ih + ox] = tile[k][threadIdx.x][r];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ other pixel formats
+// k_bgr2plab_t for the formats of rd_detector_enqueue_planes (RD_PIX_RGB .. RD_PIX_I420, rectdetect_hip.h): the same outputs - packed plab0 and the three
+// transposed 16-bit field planes of the 64x64 tile - read straight from the caller's planes, with no BGR plane in between.  A lane owns 4 consecutive pixels of
+// 4 rows (16 lanes per tile row), so that Y and the 4-byte formats arrive a dword per lane or more; groups of 4 that run past the row end, and planes whose
+// addresses or pitches are not multiples of 4 (`wide` = 0), are read byte by byte into the same words.
+struct PixZ { const uint8_t *p[3][RD_ZB_MAX]; int pitch[3]; int wide; };   // plane k of frame z of a group launch; one set of pitches for the group
+
+// the raw words of the 4 pixels x..x+3 of row y (m of them inside the row): packed formats 3 or 4 words of pixel bytes; NV12: Y, then U0 V0 U1 V1; I420: Y, then U0 U1 V0 V1
+__device__ __forceinline__ uint32_t ld_bytes(const uint8_t *p, int n) {
+  uint32_t w = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) if (i < n) w |= (uint32_t)p[i] << (8 * i);
+  return w;
+}
+template <int FMT> __device__ __forceinline__ void pix_load4(uint32_t (&w)[4], const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, const int (&pitch)[3], int x, int y, int m, bool wide) {
+  if (FMT == RD_PIX_RGB) {
+    const uint8_t *q = p0 + (size_t)y * pitch[0] + 3 * x;
+    if (wide && m == 4) { const uint32_t *q4 = (const uint32_t *)q; w[0] = q4[0]; w[1] = q4[1]; w[2] = q4[2]; }
+    else for (int k = 0; k < 3; k++) w[k] = ld_bytes(q + 4 * k, 3 * m - 4 * k);
+  } else if (FMT == RD_PIX_BGRA || FMT == RD_PIX_RGBA) {
+    const uint8_t *q = p0 + (size_t)y * pitch[0] + 4 * x;
+    if (wide && m == 4) { const uint4 v = *(const uint4 *)q; w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
+    else for (int k = 0; k < 4; k++) w[k] = ld_bytes(q + 4 * k, k < m ? 4 : 0);
+  } else {
+    const uint8_t *q = p0 + (size_t)y * pitch[0] + x;
+    const int c = (m + 1) >> 1;                     // chroma samples of the group inside the row
+    if (FMT == RD_PIX_NV12) {
+      const uint8_t *uv = p1 + (size_t)(y >> 1) * pitch[1] + x;
+      if (wide && m == 4) { w[0] = *(const uint32_t *)q; w[1] = *(const uint32_t *)uv; }
+      else { w[0] = ld_bytes(q, m); w[1] = ld_bytes(uv, 2 * c); }
+    } else {
+      const uint8_t *u = p1 + (size_t)(y >> 1) * pitch[1] + (x >> 1), *v = p2 + (size_t)(y >> 1) * pitch[2] + (x >> 1);
+      if (wide && m == 4) { w[0] = *(const uint32_t *)q; w[1] = (uint32_t)*(const unsigned short *)u | ((uint32_t)*(const unsigned short *)v << 16); }
+      else { w[0] = ld_bytes(q, m); w[1] = ld_bytes(u, c) | (ld_bytes(v, c) << 16); }
+    }
+  }
+}
+
+// BT.601 limited range, OpenCV's fixed point (the contract in rectdetect_hip.h)
+__device__ __forceinline__ void yuv_bgr(int Y, int U, int V, int &b, int &g, int &r) {
+  const int u = U - 128, v = V - 128, yy = max(Y - 16, 0) * 1220542;
+  r = min(max((yy + 1673527 * v + (1 << 19)) >> 20, 0), 255);
+  g = min(max((yy - 852492 * v - 409993 * u + (1 << 19)) >> 20, 0), 255);
+  b = min(max((yy + 2116026 * u + (1 << 19)) >> 20, 0), 255);
+}
+
+// pixel j (0..3) of a group's raw words -> b, g, r
+template <int FMT> __device__ __forceinline__ void pix_bgr(const uint32_t (&w)[4], int j, int &b, int &g, int &r) {
+  const auto byte = [&](int i) { return (int)((w[i >> 2] >> (8 * (i & 3))) & 255u); };
+  if (FMT == RD_PIX_RGB) { r = byte(3 * j); g = byte(3 * j + 1); b = byte(3 * j + 2); }
+  else if (FMT == RD_PIX_BGRA) { b = byte(4 * j); g = byte(4 * j + 1); r = byte(4 * j + 2); }
+  else if (FMT == RD_PIX_RGBA) { r = byte(4 * j); g = byte(4 * j + 1); b = byte(4 * j + 2); }
+  else if (FMT == RD_PIX_NV12) yuv_bgr(byte(j), byte(4 + 2 * (j >> 1)), byte(5 + 2 * (j >> 1)), b, g, r);
+  else yuv_bgr(byte(j), byte(4 + (j >> 1)), byte(6 + (j >> 1)), b, g, r);
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void k_pix2plab_t(uint32_t *__restrict__ out, P3 dst, PixZ src, int iw, int ih, size_t zs) {
+  const int z = blockIdx.z;
+  const uint8_t *__restrict__ p0 = src.p[0][z], *__restrict__ p1 = src.p[1][z], *__restrict__ p2 = src.p[2][z];
+  RD_ZSHIFT(zs, out, dst.p[0], dst.p[1], dst.p[2]);
+  __shared__ unsigned short s_s2l[RD_LUT_S2L_N], s_cf[RD_LUT_CF_N], s_cf2[RD_LUT_CF_N];
+  __shared__ unsigned short tile[3][64][66];
+  const int tid = rd_ty() * 64 + threadIdx.x;
+  const int x0 = blockIdx.x * 64, y0 = blockIdx.y * 64;
+  const int cx = (tid & 15) * 4, r0 = tid >> 4;    // the lane's pixels: columns x0 + cx .. + 3 of rows y0 + r0 + 16 k
+  const int x = x0 + cx, m = min(iw - x, 4);
+  // every word of the lane's 16 pixels requested before the tables are staged (as k_bgr2plab_t does)
+  uint32_t w[4][4] = {};
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int y = y0 + r0 + 16 * k;
+    if (m > 0 && y < ih) pix_load4<FMT>(w[k], p0, p1, p2, src.pitch, x, y, m, src.wide != 0);
+  }
+  for (int i = tid; i < RD_LUT_S2L_N; i += 256) s_s2l[i] = rd_lut_s2l[i];
+  for (int i = tid; i < RD_LUT_CF_N; i += 256) { s_cf[i] = rd_lut_cfunc[i]; s_cf2[i] = rd_lut_cfunc2[i]; }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int r = r0 + 16 * k, y = y0 + r;
+    if (m <= 0 || y >= ih) continue;
+    uint32_t v[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      int b, g, rr;
+      pix_bgr<FMT>(w[k], j, b, g, rr);
+      v[j] = plab_of(s_s2l, s_cf, s_cf2, b, g, rr);
+      tile[0][r][cx + j] = (unsigned short)(v[j] & 4095u); tile[1][r][cx + j] = (unsigned short)((v[j] >> 12) & 1023u); tile[2][r][cx + j] = (unsigned short)((v[j] >> 22) & 1023u);
+    }
+    uint32_t *o = out + (size_t)y * iw + x;
+    if (m == 4 && (iw & 3) == 0) *(uint4 *)o = make_uint4(v[0], v[1], v[2], v[3]);
+    else for (int j = 0; j < m; j++) o[j] = v[j];
   }
   __syncthreads();
   for (int r = rd_ty(); r < 64; r += 4) {
@@ -859,6 +979,25 @@ void bgr2plab_transposed(hipStream_t s, uint32_t *out, float *const dst[3], cons
 }
 void bgr2plab_transposed(hipStream_t s, uint32_t *out, float *const dst[3], const uint8_t *bgr, int iw, int ih, int ws) {
   bgr2plab_transposed(s, out, dst, &bgr, iw, ih, ws, 1, 0);
+}
+void pix2plab_transposed(hipStream_t s, int fmt, uint32_t *out, float *const dst[3], const uint8_t *const (*planes)[3], const int pitch[3], int iw, int ih, int nz, size_t zs) {
+  P3 d = { { dst[0], dst[1], dst[2] } };
+  PixZ z;
+  z.wide = 1;
+  for (int k = 0; k < 3; k++) {
+    z.pitch[k] = pitch[k];
+    if (pitch[k] & 3) z.wide = 0;
+    for (int i = 0; i < RD_ZB_MAX; i++) { z.p[k][i] = planes[i < nz ? i : 0][k]; if ((uintptr_t)z.p[k][i] & 3) z.wide = 0; }
+  }
+  const dim3 grid(cdiv(iw, 64), cdiv(ih, 64), nz);
+  switch (fmt) {
+    case RD_PIX_RGB: hipLaunchKernelGGL(k_pix2plab_t<RD_PIX_RGB>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
+    case RD_PIX_BGRA: hipLaunchKernelGGL(k_pix2plab_t<RD_PIX_BGRA>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
+    case RD_PIX_RGBA: hipLaunchKernelGGL(k_pix2plab_t<RD_PIX_RGBA>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
+    case RD_PIX_NV12: hipLaunchKernelGGL(k_pix2plab_t<RD_PIX_NV12>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
+    case RD_PIX_I420: hipLaunchKernelGGL(k_pix2plab_t<RD_PIX_I420>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
+    default: abort();
+  }
 }
 void unpack_plab(hipStream_t s, float *L, float *a, float *b, const uint32_t *in, int n) {
   hipLaunchKernelGGL(k_unpack_plab, dim3(ew_grid(n)), dim3(256), 0, s, L, a, b, in, n);
