@@ -285,12 +285,12 @@ cl_event oclpolyline_execute(oclpolyline_t *thiz, cl_mem lsList, int lsListSize,
 
 // ================================================================================================ detector
 #define RD_NBUDGETS 7       // launch budgets of the region merge: 8, 10, .. 20 (kRoundBudgets)
+#define RD_NSEQ (1 + 2 * RD_NBUDGETS)      // captured launch sequences of a frame or a group (Slot::graphs)
 #define RD_MAXREC 512       // records copied back per frame without a second transfer (the copy runs at PCIe speed: 16 us for 2048)
 
 struct Slot {
   hipStream_t st;
   hipStream_t st2;                        // second stream of the slot: polyline stage, parallel to the region stages
-  int uploaded_early;                     // group mode, host frames: the upload was issued when the frame was handed over (ev_fork marks its end)
   int pooled_streams;                     // st / st2 come from the process-wide pool of high-priority streams and go back there
   int shares_streams;                     // st / st2 belong to another slot (see rd_detector_create)
   hipEvent_t ev_fork, ev_mm, ev_join;
@@ -318,7 +318,6 @@ struct Slot {
   int pending_sparse;                     // batched mode: dense stages enqueued, sparse stages not launched yet
   int pending_dense;                      // group mode (rd_detector::zb > 1): frame handed over, nothing launched yet
   int group_n;                            // frames that ran between this frame's ev_begin and ev_done (1, or the group's size: the interval is shared)
-  hipGraphExec_t gz0, gz2[3 * RD_NBUDGETS]; int gz_ws;      // group mode, first slot of a group: the group's launch sequences (dense stages up to the first labelling; everything after the strong masks)
   // rectangles on the device (RD_DEVICE_POST): scratch, result block in pinned host memory, whether this frame's block is valid and for which aperture
   int *post_scratch, *h_post, *h_post_dev;
   int post_mode; double post_tan;
@@ -328,14 +327,14 @@ struct Slot {
   int *h_pack, *h_pack_dev;                // everything the host needs from a frame, assembled by the device in pinned host memory (host / device address)
   long seq;
   int ws;
-  // the frame's pixel format (RD_PIX_*; calloc'd: RD_PIX_BGR).  Other formats (rd_detector_enqueue_planes) keep their planes and row strides here, src = pl[0] and
-  // ws = pitch[0]; a host frame's planes are packed into bgr
+  // the frame's pixel format (RD_PIX_*), its planes and their row strides (hand_over); src = pl[0] and ws = pitch[0]; a host frame's planes are packed into bgr
   int fmt;
   const uint8_t *pl[3]; int pitch[3];
-  // captured launch sequences (three segments, see enqueue_frame) and the stride they were captured for
-  hipGraphExec_t gexec[3]; int graph_ws;   // gexec[2] unused: the last segment has one graph per round budget (gexec2)
-  hipGraphExec_t gexec2[3 * RD_NBUDGETS];  // [round budget index][polyline mode]
-  int poly_mode;                           // polyline mode of the frame in flight (1 = single block, 0 = multi-launch)
+  // Captured launch sequences: [0] this slot's frame on its own, [1] the group this slot leads (group mode); by sequence - 0: the dense stages up to the first
+  // labelling, 1 + 2 * round budget index + polyline mode: everything after the strong masks (the polyline kind's one sequence: 1 + polyline mode).  None reads the
+  // frame (the colour conversion runs in front of them, outside), so a change of format or row stride re-captures nothing.
+  hipGraphExec_t graphs[2][RD_NSEQ];
+  int poly_mode;                          // polyline mode of the frame in flight (1 = single block, 0 = multi-launch)
   int rounds;                             // region-merge round budget of the frame in flight
   // post-process worker
   pthread_t th; pthread_mutex_t mu; pthread_cond_t cv;
@@ -376,7 +375,6 @@ struct rd_detector {
   int overflow_streak;
   int poly_overflows;                     // set once two frames in a row overflowed the single-launch polyline kernel: later frames go multi-launch
   int rounds_budget, need_hist[64]; unsigned need_pos; long budget_count[RD_NBUDGETS], need_count[21];
-  int graph_fork;            // the forked segment (one or two frames in flight: polyline chain beside the blur / region chain) as a captured graph too
   hipStream_t st_upload;     // group mode, host frames: the stream the frames travel on (created on first use, from the pool of high-priority streams)
   int post_helpers;          // helper threads armed by every poll (rd_post.c), 0 = none
   long host_enqueue_ns;      // wall time the caller spent inside rd_detector_enqueue
@@ -388,8 +386,7 @@ struct rd_detector {
   // a stream that is capturing must not be synchronised.  launch_mu serialises captures against the launches of a repeat; repeats wait
   // on an event of their own (ev_redo), never on the stream.
   pthread_mutex_t launch_mu;
-  const void *pinned_lo, *pinned_hi;        // the last caller buffer that was verified to be pinned host memory (RD_FRAME_HOST_PINNED)
-  const void *pinned_pl[4][2]; unsigned pinned_pl_next;   // the same for the planes of rd_detector_enqueue_planes: the last 4 plane ranges verified (a frame's planes may lie in allocations of their own)
+  const void *pinned[4][2]; unsigned pinned_next;   // the last 4 ranges of caller memory that were verified to be pinned host memory (RD_FRAME_HOST_PINNED; a frame's planes may lie in allocations of their own)
   const void *probed[2]; int probed_pinned[2];      // RD_FRAME_HOST, one or two frames in flight: the last two frame pointers asked about (a loop alternates between its two pages) and the answer
   long n_frames_pinned, n_frames_copied;     // host frames that travelled straight from the caller's pinned memory / through the detector's own staging pages
   long n_unsettled;          // frames whose region merge was still changing after RD_REGION_MAX_LAUNCHES launches (none on any fixture)
@@ -597,15 +594,15 @@ static void slot_free(Slot *s, int device) {
   }
 }
 
-// The device part of one frame (reference oclrect.c:235-381), enqueued on the slot's stream in three segments so that
-// each can be captured into a hipGraph: [0] up to the first labelling, [1] up to the hand-over of the strong-edge mask
-// to the next frame (quirk H1, needs an event wait before it and an event record after it), [2] the rest.
+// The device part of one frame (reference oclrect.c:235-381), enqueued on the slot's stream in three segments: [0] up to
+// the first labelling and [2] the rest, each captured into a hipGraph (frame_segment), and between them [1] the hand-over of the
+// strong-edge mask to the next frame (quirk H1, needs an event wait before it and an event record after it: rect_frames).
 // last part of a frame: polylines of the strong edges, votes, probes, transfers.  mode 1 uses the single-launch polyline
 // stage, which reports frames that do not fit its on-chip tables in counter 25; slot_postprocess() then repeats this
 // part with mode 0.
-static void frame_polyline(rd_detector *d, Slot *s, hipStream_t st, int mode) {
+static void frame_polyline(rd_detector *d, Slot *s, hipStream_t st, int mode, int nz = 1) {
   // frame ring of the bridging step is "non-zero" on this path (oclrect.c:361, H3); the dense id plane is only produced on request (debug plane)
-  rdk::polyline(st, s->frame, 1, d->N * 16, 1, 4.0f, 20, d->iw, d->ih, mode);
+  rdk::polyline(st, s->frame, nz, d->N * 16, 1, 4.0f, 20, d->iw, d->ih, mode);
 }
 
 // segment / boundary votes (oclrect.c:365-367) and the probes the host needs (oclrect.c:1066-1098) for nb consecutive slots.
@@ -628,28 +625,26 @@ static int aperture_snapshot(rd_detector *d, double *tan_out) {
   pthread_mutex_unlock(&d->tan_mu);
   return have;
 }
-static void frame_votes(rd_detector *d, Slot *s, int tables_are_clean) { frames_votes(d, s->frame, 1, s->st, tables_are_clean, 0); }
 
 static void frame_tail(rd_detector *d, Slot *s, int mode) {   // both, in order, on the slot's main stream (overflow redo)
   frame_polyline(d, s, s->st, mode);
-  frame_votes(d, s, 0);
+  frames_votes(d, s->frame, 1, s->st, 0, 0);
 }
 
-// regions, their sizes, absorption of small ones, boundaries and boundary components (oclrect.c:325-342).  Reads planes that
+// regions, their sizes, absorption of small ones, boundaries and boundary components (oclrect.c:325-342) of nz frames.  Reads planes that
 // nothing later in the frame modifies (quant, mergemask, label1, junction), so it can be repeated with a larger round budget.
-static void frame_regions(rd_detector *d, Slot *s, hipStream_t st_over = NULL) {
+static void frame_regions(rd_detector *d, Slot *s, hipStream_t st, int nz, size_t zs) {
   const int iw = d->iw, ih = d->ih, N = d->N;
-  hipStream_t st = st_over ? st_over : s->st;
   // regions (oclrect.c:325-336)
   int *d2scratch = s->d2s;
   int marked = 0;
   rdk::region_merge(st, s->region0, s->scratch2, (const int *)s->quant, s->mmbits, s->strongbits, iw, ih, s->rounds,
-                    s->rsize, &marked);   // H2: the sizes start from the junction counts (evaluated by the first kernel)
-  rdk::region_size(st, s->rsize, s->region0, N, d2scratch + N, marked);      // (also strips the rounds' marks from the labels)
-  rdk::despeckle2(st, s->region, s->region0, d2scratch, s->rsize, 16, iw, ih, 1, s->scratch2 + N + RD_REGION_STATUS_AT);   // (status words: they travel to the host with the round flags)
+                    s->rsize, &marked, nz, zs);   // H2: the sizes start from the junction counts (evaluated by the first kernel)
+  rdk::region_size(st, s->rsize, s->region0, N, d2scratch + N, marked, nz, zs);      // (also strips the rounds' marks from the labels)
+  rdk::despeckle2(st, s->region, s->region0, d2scratch, s->rsize, 16, iw, ih, 1, s->scratch2 + N + RD_REGION_STATUS_AT, nz, zs);   // (status words: they travel to the host with the round flags)
 
   // region boundaries and their components (oclrect.c:340-342)
-  rdk::label8_boundary(st, s->boundary, s->boundarysrc, s->region, iw, ih, s->table, s->claim, s->tlist, 1, 0, RD_BOUNDARY_FLATTEN);   // (also undoes the previous frame's vote-table entries)
+  rdk::label8_boundary(st, s->boundary, s->boundarysrc, s->region, iw, ih, s->table, s->claim, s->tlist, nz, zs, RD_BOUNDARY_FLATTEN);   // (also undoes the previous frame's vote-table entries)
 }
 
 // votes and probes of a frame whose regions were computed again (a frame whose rectangles the device computes gets them again as well,
@@ -708,74 +703,89 @@ static void frames_grad_nms(rd_detector *d, Slot *s, hipStream_t st, int nz, siz
   rdk::thinthres(st, s->nms, s->strength, s->vxy, iw, ih, nz, zs);
 }
 
-static void frame_segment(rd_detector *d, Slot *s, int ws, int seg, hipStream_t st_over = NULL) {
-  const int iw = d->iw, ih = d->ih, N = d->N;
-  hipStream_t st = st_over ? st_over : s->st;
+// the front both detector kinds share, for nz frames: sigma=1 blur of L, a, b -> blurred planes (oclrect.c:246-251), then gradient direction (+ the packing of the
+// blurred Lab, oclrect.c:251, on the way), strength, non-max suppression (oclrect.c:253-258)
+static void frames_front(rd_detector *d, Slot *s, hipStream_t st, int nz, size_t zs) {
+  const int iw = d->iw, ih = d->ih;
+  { const float *c[3] = { s->tr[0], s->tr[1], s->tr[2] }; rdk::iir_blur_pass(st, s->hz, c, s->fw, s->bw, 3, ih, iw, 1, s->tails, s->flags, 1, nz, zs); }        // along x (source: 16-bit fields)
+  { const float *c[3] = { s->hz[0], s->hz[1], s->hz[2] }; rdk::iir_blur_pass(st, s->bl, c, s->fw, s->bw, 3, iw, ih, 0, s->tails, s->flags + 1, 0, nz, zs); }   // along y
+  frames_grad_nms(d, s, st, nz, zs);
+}
+
+// Segment 0 or 2 of one frame (nz = 1, zs = 0) or of the nz frames of a group, whose first slot is s and whose planes lie zs bytes apart.
+static void frame_segment(rd_detector *d, Slot *s, int seg, hipStream_t st, int nz, size_t zs) {
+  const int iw = d->iw, ih = d->ih;
   if (seg == 0) {
-
-  // (colour conversion, oclrect.c:245: launched by enqueue_frame in front of this segment, outside the recorded graph - its source is the
+  // (colour conversion, oclrect.c:245: launched by launch_frames in front of this segment, outside the recorded graph - its source is the
   //  caller's device buffer when the frame is resident in HBM: no copy of the frame)
-  // sigma=1 blur of L, a, b -> packed blurred Lab (oclrect.c:246-251)
-  { const float *c[3] = { s->tr[0], s->tr[1], s->tr[2] }; rdk::iir_blur_pass(st, s->hz, c, s->fw, s->bw, 3, ih, iw, 1, s->tails, s->flags, 1); }    // along x (source: 16-bit fields)
-  { const float *c[3] = { s->hz[0], s->hz[1], s->hz[2] }; rdk::iir_blur_pass(st, s->bl, c, s->fw, s->bw, 3, iw, ih, 0, s->tails, s->flags + 1); }   // along y
-  // gradient direction (+ the packing of the blurred Lab, oclrect.c:251, on the way), strength, non-max suppression (oclrect.c:253-258)
-  frames_grad_nms(d, s, st, 1, 0);
-
+  frames_front(d, s, st, nz, zs);
   // mask of positive responses and the rect-path tidy (oclrect.c:262-272)
   // components (background included) of the tidied mask; the tidy itself runs inside the labelling's tile kernel (and clears the
   // strength sums for the H1 segment); the walk to the roots happens in the first kernel of the next segment
-  rdk::label8_tidy(st, s->label1, NULL, s->tidy, s->nms, s->strsum, iw, ih, 1);      // (the mask of positive responses, oclrect.c:262-264, is not stored: nothing reads it - debug plane "mask0" derives it from the responses)
+  rdk::label8_tidy(st, s->label1, NULL, s->tidy, s->nms, s->strsum, iw, ih, 1, nz, zs);      // (the mask of positive responses, oclrect.c:262-264, is not stored: nothing reads it - debug plane "mask0" derives it from the responses)
   // strength sums per component (oclrect.c:274-275) - without the strong mask of the frame before (H1), which frame_strong() adds
-  rdk::calc_strength(st, s->strsum, s->nms, s->label1, iw, ih, NULL, 1);
+  rdk::calc_strength(st, s->strsum, s->nms, s->label1, iw, ih, NULL, 1, nz, zs);
   return;
   }
   // Three chains leave this point and meet again before the region stage / the votes:
   //   main stream: edge-stopped blur x20 -> quantise -> despeckle                              (oclrect.c:286-303)
   //   2nd stream : junction counts of the filtered labels -> merge mask                      (oclrect.c:315-321)
   //                then the polyline stage, which needs nothing but the strong mask          (oclrect.c:361)
-  // Inside a captured graph the streams become parallel branches.
-  static const int fork_order = RD_LAB_INT("RD_FORK_ORDER", 1);      // (0: polyline chain launched first, 1: after the region stage, 2: before it)
-  if (d->fork_poly) {      // (else: everything on the main stream, blur chain first)
+  // With one or two frames in flight (fork_poly: never a group) the second chain runs on the slot's second stream; else everything on the main stream, blur chain first.
+  const bool fork = d->fork_poly != 0;
+  if (fork) {
     RD_HIP(hipEventRecord(s->ev_fork, st));
     RD_HIP(hipStreamWaitEvent(s->st2, s->ev_fork, 0));
     rdk::junction_bits(s->st2, (unsigned long long *)s->scratch2, s->strongbits, iw, ih);
     rdk::merge_mask(s->st2, s->mmbits, (const unsigned long long *)s->scratch2, iw, ih);
     RD_HIP(hipEventRecord(s->ev_mm, s->st2));
-    if (fork_order == 0) {
-    frame_polyline(d, s, s->st2, s->poly_mode);
-    RD_HIP(hipEventRecord(s->ev_join, s->st2));
-    }
   }
 
   // edge-preserving smoothing x10, quantise, despeckle (oclrect.c:286-303)
-  rdk::blblur_extents(st, s->ext, s->e8, iw, ih);
+  rdk::blblur_extents(st, s->ext, s->e8, iw, ih, nz, zs);
   // (Two pairs per launch - halo of 8 cells, four passes through two LDS planes, with and without running sums - halve the launches and
   //  the HBM traffic of this stage and were measured 6 % SLOWER at full rate: 100 KB of LDS leave one 1024-thread block per CU and the
   //  extra barriers cost more than the saved traffic; the stage is bound by vector instructions, not by memory.  DESIGN.md.)
   { const uint32_t *src = s->plab0;     // ping-pong between i0 and smooth; the 10th pair lands in smooth
-    for (int i = 0; i < 10; i++) { uint32_t *dst = (i & 1) ? s->smooth : (uint32_t *)s->i0; rdk::blblur_pair(st, dst, s->ext, src, iw, ih); src = dst; } }
-  rdk::despeckle(st, s->quant, s->smooth, s->nms, iw, ih, 1);      // quantisation to 24 levels per field (oclrect.c:298) happens on the fly
+    for (int i = 0; i < 10; i++) { uint32_t *dst = (i & 1) ? s->smooth : (uint32_t *)s->i0; rdk::blblur_pair(st, dst, s->ext, src, iw, ih, nz, zs); src = dst; } }
+  rdk::despeckle(st, s->quant, s->smooth, s->nms, iw, ih, 1, nz, zs);      // quantisation to 24 levels per field (oclrect.c:298) happens on the fly
 
-  if (d->fork_poly) RD_HIP(hipStreamWaitEvent(st, s->ev_mm, 0));
+  if (fork) RD_HIP(hipStreamWaitEvent(st, s->ev_mm, 0));
   else {
-    rdk::junction_bits(st, (unsigned long long *)s->scratch2, s->strongbits, iw, ih);
-    rdk::merge_mask(st, s->mmbits, (const unsigned long long *)s->scratch2, iw, ih);
+    rdk::junction_bits(st, (unsigned long long *)s->scratch2, s->strongbits, iw, ih, nz, zs);
+    rdk::merge_mask(st, s->mmbits, (const unsigned long long *)s->scratch2, iw, ih, nz, zs);
   }
 
-  if (d->fork_poly && fork_order == 2) { frame_polyline(d, s, s->st2, s->poly_mode); RD_HIP(hipEventRecord(s->ev_join, s->st2)); }
-  frame_regions(d, s);
-  if (d->fork_poly && fork_order == 1) { frame_polyline(d, s, s->st2, s->poly_mode); RD_HIP(hipEventRecord(s->ev_join, s->st2)); }
+  frame_regions(d, s, st, nz, zs);
+  if (fork) { frame_polyline(d, s, s->st2, s->poly_mode); RD_HIP(hipEventRecord(s->ev_join, s->st2)); }      // (the polyline chain's launches follow the region stage's: of the three places tried - first, before that stage, after it - the one kept)
 
-  if (d->batch > 1) return;      // the sparse stages of the group's frames follow in one set of launches (sparse_launch)
-  if (d->fork_poly) RD_HIP(hipStreamWaitEvent(st, s->ev_join, 0));
-  else frame_polyline(d, s, st, s->poly_mode);
-  frame_votes(d, s, 1);
+  if (d->batch > 1) return;      // the sparse stages of the batch's frames follow in one set of launches (sparse_launch)
+  if (fork) RD_HIP(hipStreamWaitEvent(st, s->ev_join, 0));
+  else frame_polyline(d, s, st, s->poly_mode, nz);
+  frames_votes(d, s->frame, nz, st, 1, 0);
+}
+
+// The polyline kind (rd_polyline_detector_create): poly.cpp:104-123 / vidpoly.cpp:165-183 per frame, for nz frames as above.  The front of the rect kind, the
+// components of nms > 0 (no tidy), the strength sums from zero (no H1 carry-over: poly.cpp:118 clears them), filterStrength + `label > 0` as a bit plane, the
+// polyline stage with the frame ring at zero (the reference's tmp3 is a fresh, zeroed buffer: poly.cpp:93) and the hand-off of the list's first records into
+// pinned host memory.  Nothing depends on the frame before: the whole frame is one captured sequence.
+static void poly_segment(rd_detector *d, Slot *s, int nz, size_t zs, hipStream_t st, int mode) {
+  const int iw = d->iw, ih = d->ih, N = d->N;
+  frames_front(d, s, st, nz, zs);
+  rdk::label8_positive(st, s->label1, s->mask0, s->nms, s->strsum, iw, ih, 1, nz, zs);      // (poly.cpp:115-118; the walk to the roots happens in the next kernel)
+  rdk::calc_strength(st, s->strsum, s->nms, s->label1, iw, ih, NULL, 1, nz, zs);           // (poly.cpp:119)
+  rdk::poly_mask_bits(st, s->strongbits, s->label1, s->strsum, d->p_thre, iw, ih, nz, zs);   // (poly.cpp:120-121)
+  rdk::polyline(st, s->frame, nz, N * 16, 0, d->p_minerror, d->p_size, iw, ih, mode);      // (poly.cpp:123)
+  rdk::polyline_handoff(st, s->frame, nz, d->handoff_rec);
 }
 
 // region-merge round budgets a frame can be launched with; the rounds stop changing anything after ~10 on typical frames
 // and every launched round costs two dispatches even when it exits at once, so the budget follows what recent frames
 // needed (+ margin).  A frame whose last launched round still changed something is repeated with the full budget
 // (slot_postprocess), so the result never depends on the budget.
+static const int kRoundBudgets[RD_NBUDGETS] = { 8, 10, 12, 14, 16, 18, 20 };
+static int budget_index(int rounds) { for (int k = 0; k < RD_NBUDGETS; k++) if (kRoundBudgets[k] == rounds) return k; return RD_NBUDGETS - 1; }
+
 // how the polyline stage of the next frame is launched: the single-block kernel (1) until two frames in a row overflowed its on-chip tables
 // (e.g. 3840x2160), from then on the ~85-launch form (0), which is also what repeats a frame the single-block kernel gave up on.  (One
 // cooperative launch of several blocks per frame was built in round 3 and measured slower than the 85 launches: profiles/NOTES_r03.md.)
@@ -784,115 +794,22 @@ static int current_poly_mode(const rd_detector *d) {
   return __atomic_load_n(&d->poly_overflows, __ATOMIC_RELAXED) ? 0 : 1;
 }
 
-static const int kRoundBudgets[RD_NBUDGETS] = { 8, 10, 12, 14, 16, 18, 20 };
-
-static void run_segment(rd_detector *d, Slot *s, int ws, int seg, hipStream_t st_over = NULL) {      // st_over (segment 1 only): another stream than the slot's
-  hipStream_t lst = st_over ? st_over : s->st;
-  // (one or two frames in flight: kernel by kernel - the captured graph of the forked segment starts its second branch 170 us late, and the front segment, a straight
-  //  line of ten kernels, is no faster as a graph either: 1615-1623 against 1636-1652 frames/s two deep; RD_GRAPH_FORK=1 brings both graphs back)
-  if (!d->use_graph || (d->fork_poly && !d->graph_fork)) { frame_segment(d, s, ws, seg, lst); return; }
-  hipGraphExec_t *ge = &s->gexec[seg];
-  if (seg == 2) for (int k = 0; k < RD_NBUDGETS; k++) if (kRoundBudgets[k] == s->rounds) ge = &s->gexec2[k * 3 + (d->batch == 1 ? s->poly_mode : 0)];
-  if (!*ge) {
-    hipGraph_t g = NULL;
-    pthread_mutex_lock(&d->launch_mu);
-    RD_HIP(hipStreamBeginCapture(lst, hipStreamCaptureModeThreadLocal));
-    frame_segment(d, s, ws, seg, lst);
-    RD_HIP(hipStreamEndCapture(lst, &g));
-    pthread_mutex_unlock(&d->launch_mu);
-    RD_HIP(hipGraphInstantiate(ge, g, NULL, NULL, 0));
-    RD_HIP(hipGraphDestroy(g));
-  }
-  RD_HIP(hipGraphLaunch(*ge, lst));
+// Where slot s keeps the captured form of launch sequence `seq` for nz frames (Slot::graphs), or NULL where the sequence runs kernel by kernel: without graphs
+// (RD_NO_GRAPH), and with one or two frames in flight - the captured graph of the forked segment starts its second branch 170 us late, and the front segment, a
+// straight line of ten kernels, is no faster as a graph either: 1615-1623 against 1636-1652 frames/s two deep (profiles/NOTES_r05.md).
+static hipGraphExec_t *slot_graph(rd_detector *d, Slot *s, int nz, int seq) {
+  if (!d->use_graph || d->fork_poly) return NULL;
+  return &s->graphs[nz > 1 ? 1 : 0][seq];
 }
 
-// The first kernel of a frame in another format than BGR (rd_detector_enqueue_planes): the nz frames of the slots from s on, which share format and pitches.
-static void pix_front(rd_detector *d, Slot *s, int nz, hipStream_t st) {
-  const uint8_t *planes[RD_ZB_MAX][3];
-  for (int i = 0; i < nz; i++) for (int k = 0; k < 3; k++) planes[i][k] = s[i].pl[k];
-  rdk::pix2plab_transposed(st, s->fmt, s->plab0, s->tr, planes, s->pitch, d->iw, d->ih, nz, nz > 1 ? d->slot_pitch : 0);
-}
-
-// may two frames of a group share one front launch?  (one format, one set of row strides)
-static bool same_layout(const Slot *a, const Slot *b) {
-  if (a->fmt != b->fmt || a->ws != b->ws) return false;
-  return a->fmt == RD_PIX_BGR || (a->pitch[1] == b->pitch[1] && a->pitch[2] == b->pitch[2]);
-}
-
-static void enqueue_frame(rd_detector *d, Slot *s, int ws) {
-  if (d->use_graph && s->fmt == RD_PIX_BGR && s->graph_ws != ws) {      // (other formats leave the key alone: the segments read no frame)
-    for (int k = 0; k < 3; k++) if (s->gexec[k]) { RD_HIP(hipGraphExecDestroy(s->gexec[k])); s->gexec[k] = NULL; }
-    for (int k = 0; k < 3 * RD_NBUDGETS; k++) if (s->gexec2[k]) { RD_HIP(hipGraphExecDestroy(s->gexec2[k])); s->gexec2[k] = NULL; }
-    s->graph_ws = ws;
-  }
-  RD_HIP(hipEventRecord(s->ev_begin, s->st));
-  s->watch_begin = s->ev_begin; s->watch_done = s->ev_done;
-  s->group_n = 1;
-  if (s->fmt == RD_PIX_BGR) rdk::bgr2plab_transposed(s->st, s->plab0, s->tr, s->src, d->iw, d->ih, ws);
-  else pix_front(d, s, 1, s->st);
-  run_segment(d, s, ws, 0);
-  if (d->have_last_strong) RD_HIP(hipStreamWaitEvent(s->st, d->last_strong, 0));
-  frame_strong(d, s, s->st);
-  RD_HIP(hipEventRecord(s->ev_strong, s->st));
-  d->last_strong = s->ev_strong; d->have_last_strong = 1;
-  s->rounds = d->fixed_rounds ? d->fixed_rounds : __atomic_load_n(&d->rounds_budget, __ATOMIC_RELAXED);
-  if (d->budget_cycle) s->rounds = kRoundBudgets[2 + (int)((s->seq / d->budget_cycle) % (RD_NBUDGETS - 2))];      // (tests: a new graph every few frames)
-  s->poly_mode = current_poly_mode(d);
-  if (d->batch == 1) { double tn = 0; const int have = aperture_snapshot(d, &tn); s->post_mode = d->device_post && have; s->post_tan = tn; }
-  for (int k = 0; k < RD_NBUDGETS; k++) if (kRoundBudgets[k] == s->rounds) d->budget_count[k]++;
-  run_segment(d, s, ws, 2);
-  if (d->batch > 1) { RD_HIP(hipEventRecord(s->ev_dense, s->st)); s->pending_sparse = 1; }
-  else {
-    if (s->post_mode) rdk::post_device(s->st, s->frame, 1, d->maxrec_dev, d->iw, d->ih, s->post_tan);      // (outside the captured graphs: the aperture is a launch argument)
-    RD_HIP(hipEventRecord(s->ev_done, s->st));
-  }
-  rdrt::check_launch("rect frame");
-}
-
-
-// ---- group mode (rd_detector::zb > 1): the frames of zb consecutive slots in ONE set of launches, dense stages included (frame =
-// blockIdx.z; the slots' planes lie slot_pitch bytes apart).  For frames so small that a launch does not fill the device (a 640x480
-// plane is 75 tiles for 256 CUs): the frame rate is then set by the number of launches the four hardware queues get through, and a
-// group needs as many as a single frame.  What cannot be shared is the short middle segment - a frame's strength sums start from
-// the strong mask of the frame before it (H1) - which runs frame by frame between the two group segments, on the same stream.
-static hipStream_t group_stream(rd_detector *d, int g0) { return d->slots[(g0 / d->zb) % (d->nstreams > 0 ? d->nstreams : 1)].st; }
-
-static void group_segment(rd_detector *d, Slot *s, int nz, int seg, hipStream_t st) {      // s: the group's first slot
-  const int iw = d->iw, ih = d->ih, N = d->N;
-  const size_t zs = d->slot_pitch;
-  if (seg == 0) {
-    { const float *c[3] = { s->tr[0], s->tr[1], s->tr[2] }; rdk::iir_blur_pass(st, s->hz, c, s->fw, s->bw, 3, ih, iw, 1, s->tails, s->flags, 1, nz, zs); }
-    { const float *c[3] = { s->hz[0], s->hz[1], s->hz[2] }; rdk::iir_blur_pass(st, s->bl, c, s->fw, s->bw, 3, iw, ih, 0, s->tails, s->flags + 1, 0, nz, zs); }
-    frames_grad_nms(d, s, st, nz, zs);
-    rdk::label8_tidy(st, s->label1, NULL, s->tidy, s->nms, s->strsum, iw, ih, 1, nz, zs);
-    rdk::calc_strength(st, s->strsum, s->nms, s->label1, iw, ih, NULL, 1, nz, zs);
-    return;
-  }
-  // seg 2: everything after the strong masks, in the order of a single frame on one stream (frame_segment without its fork)
-  rdk::blblur_extents(st, s->ext, s->e8, iw, ih, nz, zs);
-  { const uint32_t *src = s->plab0;
-    for (int i = 0; i < 10; i++) { uint32_t *dst = (i & 1) ? s->smooth : (uint32_t *)s->i0; rdk::blblur_pair(st, dst, s->ext, src, iw, ih, nz, zs); src = dst; } }
-  rdk::despeckle(st, s->quant, s->smooth, s->nms, iw, ih, 1, nz, zs);
-  rdk::junction_bits(st, (unsigned long long *)s->scratch2, s->strongbits, iw, ih, nz, zs);
-  rdk::merge_mask(st, s->mmbits, (const unsigned long long *)s->scratch2, iw, ih, nz, zs);
-  int marked = 0;
-  rdk::region_merge(st, s->region0, s->scratch2, (const int *)s->quant, s->mmbits, s->strongbits, iw, ih, s->rounds, s->rsize, &marked, nz, zs);
-  rdk::region_size(st, s->rsize, s->region0, N, s->d2s + N, marked, nz, zs);
-  rdk::despeckle2(st, s->region, s->region0, s->d2s, s->rsize, 16, iw, ih, 1, s->scratch2 + N + RD_REGION_STATUS_AT, nz, zs);
-  rdk::label8_boundary(st, s->boundary, s->boundarysrc, s->region, iw, ih, s->table, s->claim, s->tlist, nz, zs, RD_BOUNDARY_FLATTEN);
-  rdk::polyline(st, s->frame, nz, N * 16, 1, 4.0f, 20, iw, ih, s->poly_mode);
-  frames_votes(d, s->frame, nz, st, 1, 0);
-}
-
-static void run_group_segment(rd_detector *d, Slot *s, int nz, int seg, hipStream_t st) {
-  if (!d->use_graph) { group_segment(d, s, nz, seg, st); return; }
-  hipGraphExec_t *ge = &s->gz0;
-  if (seg == 2) for (int k = 0; k < RD_NBUDGETS; k++) if (kRoundBudgets[k] == s->rounds) ge = &s->gz2[k * 3 + s->poly_mode];
+// Enqueues on st what `record` enqueues there: directly (ge == NULL), or as a graph that is captured from it on first use and kept in *ge.
+template <typename F> static void launch_captured(rd_detector *d, hipGraphExec_t *ge, hipStream_t st, F record) {
+  if (!ge) { record(); return; }
   if (!*ge) {
     hipGraph_t g = NULL;
     pthread_mutex_lock(&d->launch_mu);
     RD_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    group_segment(d, s, nz, seg, st);
+    record();
     RD_HIP(hipStreamEndCapture(st, &g));
     pthread_mutex_unlock(&d->launch_mu);
     RD_HIP(hipGraphInstantiate(ge, g, NULL, NULL, 0));
@@ -901,91 +818,44 @@ static void run_group_segment(rd_detector *d, Slot *s, int nz, int seg, hipStrea
   RD_HIP(hipGraphLaunch(*ge, st));
 }
 
-static void enqueue_frame(rd_detector *d, Slot *s, int ws);
-static void slot_submitted(rd_detector *d, Slot *s);
-
-// the frames waiting in the group that starts at slot g0: all zb of them with one row stride -> one set of launches; anything else (a poll
-// that wants a result before the group is full, the end of a stream) -> frame by frame, the way a detector without groups launches them
-static void group_launch(rd_detector *d, int g0) {
-  const int zb = d->zb;
-  int cnt = 0, same_ws = 1;
-  for (int i = g0; i < g0 + zb && i < d->nslots; i++) { Slot *s = &d->slots[i]; if (s->pending_dense) { cnt++; if (!same_layout(s, &d->slots[g0])) same_ws = 0; } }
-  if (cnt == 0) return;
-  // Host frames travelled when they were handed over, one after the other on the detector's upload stream (rd_detector_enqueue).  The launching thread waits for that
-  // stream here - at most for the transfer just issued, 0.1 ms, on a thread that has nothing else to do until the next group completes - and what the host has seen
-  // complete needs no ordering on the device: no event.  Round 6 found the 7-8 % that host frames cost against frames resident in HBM in exactly two places: an event
-  // recorded after every upload (a record is a system-scope release, a write-back of the device's caches, 2 900 times a second in the middle of everybody's kernels:
-  // 2671-2698 frames/s with it, 2886-2901 without) and - pinned frames, whose hand-over takes microseconds - eight transfers queued on the copy engine at once
-  // (2701-2723 against 2849-2884 with one at a time).  profiles/NOTES_r06.md.
-  bool travelled = false;
-  for (int i = g0; i < g0 + zb && i < d->nslots; i++) { Slot *s = &d->slots[i]; if (s->pending_dense && s->src == s->bgr && s->uploaded_early) travelled = true; }
-  if (travelled) RD_HIP(hipStreamSynchronize(d->st_upload));
-  if (cnt < zb || !same_ws) {
-    for (int i = g0; i < g0 + zb && i < d->nslots; i++) {
-      Slot *s = &d->slots[i];
-      if (!s->pending_dense) continue;
-      s->pending_dense = 0;
-      if (s->src == s->bgr) { if (s->uploaded_early) { /* arrived: waited for above */ } else RD_HIP(hipMemcpyAsync(s->bgr, s->h_bgr, (size_t)s->ws * d->ih, hipMemcpyHostToDevice, s->st)); }
-      enqueue_frame(d, s, s->ws);
-      slot_submitted(d, s);
-    }
-    return;
-  }
-  Slot *lead = &d->slots[g0];
-  hipStream_t st = group_stream(d, g0);
-  const int ws = lead->ws;
-  if (d->use_graph && lead->fmt == RD_PIX_BGR && lead->gz_ws != ws) {
-    if (lead->gz0) { RD_HIP(hipGraphExecDestroy(lead->gz0)); lead->gz0 = NULL; }
-    for (int k = 0; k < 3 * RD_NBUDGETS; k++) if (lead->gz2[k]) { RD_HIP(hipGraphExecDestroy(lead->gz2[k])); lead->gz2[k] = NULL; }
-    lead->gz_ws = ws;
-  }
-  static const bool one_event = RD_LAB_INT("RD_GROUP_ONE_EVENT", 1) != 0;
-  const uint8_t *srcs[RD_ZB_MAX];
-  for (int i = 0; i < zb; i++) {
-    Slot *s = &d->slots[g0 + i];
-    s->pending_dense = 0;
-    if (s->src == s->bgr && !s->uploaded_early) RD_HIP(hipMemcpyAsync(s->bgr, s->h_bgr, (size_t)ws * d->ih, hipMemcpyHostToDevice, st));
-    srcs[i] = s->src;
-    // (ONE pair of events brackets the group - its frames start and end together -, not one per frame: every record is a release fence in the stream)
-    if (i == 0 || !one_event) RD_HIP(hipEventRecord(s->ev_begin, st));
-    s->watch_begin = one_event ? lead->ev_begin : s->ev_begin; s->watch_done = one_event ? lead->ev_done : s->ev_done;
-  }
-  if (lead->fmt == RD_PIX_BGR) rdk::bgr2plab_transposed(st, lead->plab0, lead->tr, srcs, d->iw, d->ih, ws, zb, d->slot_pitch);
-  else pix_front(d, lead, zb, st);
-  run_group_segment(d, lead, zb, 0, st);
-  // the strong masks: each frame's on top of its predecessor's (H1) - one launch for the group where its planes allow 16-byte accesses (the mask of the frame before
+// What the rect kind launches behind the front kernel of one frame (nz = 1) or of the full group that slot s leads.  What cannot be shared by a group is the short
+// middle part - a frame's strength sums start from the strong mask of the frame before it (H1) - which runs between the two captured segments, on the same stream.
+static void rect_frames(rd_detector *d, Slot *s, int nz, hipStream_t st) {
+  const size_t zs = nz > 1 ? d->slot_pitch : 0;
+  launch_captured(d, slot_graph(d, s, nz, 0), st, [&] { frame_segment(d, s, 0, st, nz, zs); });
+  // the strong masks: each frame's on top of its predecessor's (H1) - one launch for a group where its planes allow 16-byte accesses (the mask of the frame before
   // only decides sums that stand one below a threshold, and is then evaluated on the spot: k_strength_masks_group), else frame by frame
   if (d->have_last_strong) RD_HIP(hipStreamWaitEvent(st, d->last_strong, 0));      // (only the first frame waits for the group before - another stream - and only the last is waited for)
-  bool consecutive = true;
-  for (int i = 1; i < zb; i++) consecutive = consecutive && d->slots[g0 + i].seq == lead->seq + i;
-  if (!d->strong_by_frame && consecutive && rdk::strength_masks_group_fits(d->iw, lead->label1, d->prev_ring, lead->e8, d->slot_pitch) && (d->N & 3) == 0) {
-    for (int i = 0; i < zb; i++) d->slots[g0 + i].prev_in = d->prev_ring + (size_t)(d->slots[g0 + i].seq % d->nring) * (size_t)d->N;
-    rdk::strength_masks_group(st, d->prev_ring, lead->e8, lead->label1, lead->strsum, d->t_edge, d->t_strong, d->iw, d->ih, lead->strongbits, lead->seq, d->nring, zb, d->slot_pitch);
+  bool one_launch = nz > 1 && !d->strong_by_frame && (d->N & 3) == 0 && rdk::strength_masks_group_fits(d->iw, s->label1, d->prev_ring, s->e8, zs);
+  for (int i = 1; i < nz; i++) one_launch = one_launch && s[i].seq == s->seq + i;
+  if (one_launch) {
+    for (int i = 0; i < nz; i++) s[i].prev_in = d->prev_ring + (size_t)(s[i].seq % d->nring) * (size_t)d->N;
+    rdk::strength_masks_group(st, d->prev_ring, s->e8, s->label1, s->strsum, d->t_edge, d->t_strong, d->iw, d->ih, s->strongbits, s->seq, d->nring, nz, zs);
     d->n_strong_group++;
   } else {
-    for (int i = 0; i < zb; i++) frame_strong(d, &d->slots[g0 + i], st);
-    d->n_strong_by_frame++;
+    for (int i = 0; i < nz; i++) frame_strong(d, &s[i], st);
+    if (nz > 1) d->n_strong_by_frame++;
   }
-  { Slot *s = &d->slots[g0 + zb - 1]; RD_HIP(hipEventRecord(s->ev_strong, st)); d->last_strong = s->ev_strong; d->have_last_strong = 1; }
-  const int rounds = d->fixed_rounds ? d->fixed_rounds : __atomic_load_n(&d->rounds_budget, __ATOMIC_RELAXED);
-  const int pm = current_poly_mode(d);
-  for (int i = 0; i < zb; i++) {
-    Slot *s = &d->slots[g0 + i];
-    s->rounds = rounds; s->poly_mode = pm; s->post_mode = 0;
-    if (d->budget_cycle) s->rounds = kRoundBudgets[2 + (int)((lead->seq / d->budget_cycle) % (RD_NBUDGETS - 2))];
-    for (int k = 0; k < RD_NBUDGETS; k++) if (kRoundBudgets[k] == s->rounds) d->budget_count[k]++;
-  }
-  run_group_segment(d, lead, zb, 2, st);
+  RD_HIP(hipEventRecord(s[nz - 1].ev_strong, st));
+  d->last_strong = s[nz - 1].ev_strong; d->have_last_strong = 1;
+  int rounds = d->fixed_rounds ? d->fixed_rounds : __atomic_load_n(&d->rounds_budget, __ATOMIC_RELAXED);
+  if (d->budget_cycle) rounds = kRoundBudgets[2 + (int)((s->seq / d->budget_cycle) % (RD_NBUDGETS - 2))];      // (tests: a new graph every few frames)
+  const int pm = current_poly_mode(d), bi = budget_index(rounds);
+  for (int i = 0; i < nz; i++) { s[i].rounds = rounds; s[i].poly_mode = pm; d->budget_count[bi]++; }
+  launch_captured(d, slot_graph(d, s, nz, 1 + 2 * bi + (d->batch == 1 ? pm : 0)), st, [&] { frame_segment(d, s, 2, st, nz, zs); });
+  if (d->batch > 1) return;      // (votes, probes and rectangles follow with the batch's sparse stages)
   double tn = 0;
   const int with_post = aperture_snapshot(d, &tn) && d->device_post;
-  if (with_post) rdk::post_device(st, lead->frame, zb, d->maxrec_dev, d->iw, d->ih, tn);
-  for (int i = 0; i < zb; i++) {
-    Slot *s = &d->slots[g0 + i];
-    s->post_mode = with_post; s->post_tan = tn; s->group_n = zb;
-    if (i == 0 || !one_event) RD_HIP(hipEventRecord(s->ev_done, st));
-  }
-  rdrt::check_launch("rect frames, group launch");
-  for (int i = 0; i < zb; i++) slot_submitted(d, &d->slots[g0 + i]);
+  if (with_post) rdk::post_device(st, s->frame, nz, d->maxrec_dev, d->iw, d->ih, tn);      // (outside the captured graphs: the aperture is a launch argument)
+  for (int i = 0; i < nz; i++) { s[i].post_mode = with_post; s[i].post_tan = tn; }
+}
+
+// the polyline kind's: its one sequence, captured per polyline mode
+static void poly_frames(rd_detector *d, Slot *s, int nz, hipStream_t st) {
+  const size_t zs = nz > 1 ? d->slot_pitch : 0;
+  const int pm = current_poly_mode(d);
+  for (int i = 0; i < nz; i++) s[i].poly_mode = pm;
+  launch_captured(d, slot_graph(d, s, nz, 1 + pm), st, [&] { poly_segment(d, s, nz, zs, st, pm); });
 }
 
 // the frame is on its way: its worker thread may start waiting for ev_done (which has been recorded by now - an event that was never
@@ -997,6 +867,66 @@ static void slot_submitted(rd_detector *d, Slot *s) {
     pthread_cond_broadcast(&s->cv);
     pthread_mutex_unlock(&s->mu);
   }
+}
+
+// All launches of one frame (nz = 1, st = its slot's stream) or of the full group that slot s leads, for either detector kind.
+// Group mode (rd_detector::zb > 1): the frames of zb consecutive slots in ONE set of launches, dense stages included (frame = blockIdx.z; the
+// slots' planes lie slot_pitch bytes apart).  For frames so small that a launch does not fill the device (a 640x480 plane is 75 tiles for
+// 256 CUs): the frame rate is then set by the number of launches the four hardware queues get through, and a group needs as many as a
+// single frame.
+static void launch_frames(rd_detector *d, Slot *s, int nz, hipStream_t st) {
+  // (ONE pair of events brackets a group - its frames start and end together -, not one per frame: every record is a release fence in the stream)
+  RD_HIP(hipEventRecord(s->ev_begin, st));
+  for (int i = 0; i < nz; i++) { s[i].pending_dense = 0; s[i].watch_begin = s->ev_begin; s[i].watch_done = s->ev_done; s[i].group_n = nz; }
+  // the colour conversion, outside the captured sequences: its source changes from frame to frame
+  if (s->fmt != RD_PIX_BGR) {      // (rd_detector_enqueue_planes: the frames share format and pitches)
+    const uint8_t *planes[RD_ZB_MAX][3];
+    for (int i = 0; i < nz; i++) for (int k = 0; k < 3; k++) planes[i][k] = s[i].pl[k];
+    rdk::pix2plab_transposed(st, s->fmt, s->plab0, s->tr, planes, s->pitch, d->iw, d->ih, nz, nz > 1 ? d->slot_pitch : 0);
+  } else if (nz == 1) rdk::bgr2plab_transposed(st, s->plab0, s->tr, s->src, d->iw, d->ih, s->ws);
+  else {
+    const uint8_t *srcs[RD_ZB_MAX];
+    for (int i = 0; i < nz; i++) srcs[i] = s[i].src;
+    rdk::bgr2plab_transposed(st, s->plab0, s->tr, srcs, d->iw, d->ih, s->ws, nz, d->slot_pitch);
+  }
+  if (d->kind == RD_KIND_POLY) poly_frames(d, s, nz, st); else rect_frames(d, s, nz, st);
+  if (d->batch > 1) { RD_HIP(hipEventRecord(s->ev_dense, st)); s->pending_sparse = 1; }      // (ev_done: behind the batch's sparse stages, sparse_launch)
+  else RD_HIP(hipEventRecord(s->ev_done, st));
+  rdrt::check_launch(d->kind == RD_KIND_POLY ? "polyline frames" : "rect frames");
+  if (d->batch == 1) for (int i = 0; i < nz; i++) slot_submitted(d, &s[i]);
+}
+
+// may two frames of a group share one front launch?  (one format, one set of row strides)
+static bool same_layout(const Slot *a, const Slot *b) {
+  if (a->fmt != b->fmt || a->ws != b->ws) return false;
+  return a->fmt == RD_PIX_BGR || (a->pitch[1] == b->pitch[1] && a->pitch[2] == b->pitch[2]);
+}
+
+static hipStream_t group_stream(rd_detector *d, int g0) { return d->slots[(g0 / d->zb) % (d->nstreams > 0 ? d->nstreams : 1)].st; }
+
+// the frames waiting in the group that starts at slot g0: all zb of them with one layout -> one set of launches; anything else (a poll
+// that wants a result before the group is full, the end of a stream) -> frame by frame, the way a detector without groups launches them
+static void group_launch(rd_detector *d, int g0) {
+  const int g1 = g0 + d->zb < d->nslots ? g0 + d->zb : d->nslots;
+  int cnt = 0;
+  bool same = true, travelled = false;
+  for (int i = g0; i < g1; i++) {
+    const Slot *s = &d->slots[i];
+    if (!s->pending_dense) continue;
+    cnt++;
+    same = same && same_layout(s, &d->slots[g0]);
+    travelled = travelled || s->src == s->bgr;
+  }
+  if (cnt == 0) return;
+  // Host frames travelled when they were handed over, one after the other on the detector's upload stream (hand_over).  The launching thread waits for that
+  // stream here - at most for the transfer just issued, 0.1 ms, on a thread that has nothing else to do until the next group completes - and what the host has seen
+  // complete needs no ordering on the device: no event.  Round 6 found the 7-8 % that host frames cost against frames resident in HBM in exactly two places: an event
+  // recorded after every upload (a record is a system-scope release, a write-back of the device's caches, 2 900 times a second in the middle of everybody's kernels:
+  // 2671-2698 frames/s with it, 2886-2901 without) and - pinned frames, whose hand-over takes microseconds - eight transfers queued on the copy engine at once
+  // (2701-2723 against 2849-2884 with one at a time).  profiles/NOTES_r06.md.
+  if (travelled) RD_HIP(hipStreamSynchronize(d->st_upload));
+  if (cnt == d->zb && same) { launch_frames(d, &d->slots[g0], d->zb, group_stream(d, g0)); return; }
+  for (int i = g0; i < g1; i++) if (d->slots[i].pending_dense) launch_frames(d, &d->slots[i], 1, d->slots[i].st);
 }
 
 // Batched mode: the sparse stages of slots a..b (consecutive slots of one group, dense stages enqueued) as one set of launches on
@@ -1051,7 +981,7 @@ static void slot_finish_device(rd_detector *d, Slot *s) {
     for (int budget = 32; budget <= RD_REGION_MAX_LAUNCHES; budget *= 2) {
       s->rounds = budget;
       pthread_mutex_lock(&d->launch_mu);
-      frame_regions(d, s, rst);
+      frame_regions(d, s, rst, 1, 0);
       redo_votes(d, s, rst);
       RD_HIP(hipEventRecord(s->ev_redo, rst));
       pthread_mutex_unlock(&d->launch_mu);
@@ -1101,7 +1031,7 @@ static void slot_finish_device(rd_detector *d, Slot *s) {
 // on a slot's stream whenever a (slot, launch budget) pair is used for the first time - in the middle of a run, since the budget of the
 // region merge follows the stream.  HIP refuses hipEventSynchronize / hipEventQuery on an event whose stream is being captured ("operation
 // not permitted on an event last recorded in a capturing stream"), so the wait is a poll whose queries exclude captures (launch_mu: held by
-// run_segment for the duration of a capture, a few hundred microseconds).
+// launch_captured for the duration of a capture, a few hundred microseconds).
 static void wait_event_outside_captures(rd_detector *d, hipEvent_t ev) {
   for (;;) {
     pthread_mutex_lock(&d->launch_mu);
@@ -1219,92 +1149,65 @@ static void *slot_worker(void *arg) {
   }
 }
 
-
-// ================================================================================================ polyline kind
-// poly.cpp:104-123 / vidpoly.cpp:165-183 per frame, nz frames of consecutive slots per launch (group mode, as the rect kind's): the front end of the rect
-// kind, the components of nms > 0 (no tidy), the strength sums from zero (no H1 carry-over: poly.cpp:118 clears them), filterStrength + `label > 0` as
-// a bit plane, the polyline stage with the frame ring at zero (the reference's tmp3 is a fresh, zeroed buffer: poly.cpp:93) and the hand-off of the
-// list's first records into pinned host memory.  Nothing depends on the frame before: the whole frame is one captured sequence.
-static void poly_segment(rd_detector *d, Slot *s, int nz, size_t zs, hipStream_t st, int mode) {
-  const int iw = d->iw, ih = d->ih, N = d->N;
-  { const float *c[3] = { s->tr[0], s->tr[1], s->tr[2] }; rdk::iir_blur_pass(st, s->hz, c, s->fw, s->bw, 3, ih, iw, 1, s->tails, s->flags, 1, nz, zs); }
-  { const float *c[3] = { s->hz[0], s->hz[1], s->hz[2] }; rdk::iir_blur_pass(st, s->bl, c, s->fw, s->bw, 3, iw, ih, 0, s->tails, s->flags + 1, 0, nz, zs); }
-  frames_grad_nms(d, s, st, nz, zs);
-  rdk::label8_positive(st, s->label1, s->mask0, s->nms, s->strsum, iw, ih, 1, nz, zs);      // (poly.cpp:115-118; the walk to the roots happens in the next kernel)
-  rdk::calc_strength(st, s->strsum, s->nms, s->label1, iw, ih, NULL, 1, nz, zs);           // (poly.cpp:119)
-  rdk::poly_mask_bits(st, s->strongbits, s->label1, s->strsum, d->p_thre, iw, ih, nz, zs);   // (poly.cpp:120-121)
-  rdk::polyline(st, s->frame, nz, N * 16, 0, d->p_minerror, d->p_size, iw, ih, mode);      // (poly.cpp:123)
-  rdk::polyline_handoff(st, s->frame, nz, d->handoff_rec);
+// ---- detector set-up: what rd_detector_create and rd_polyline_detector_create share (the argument checks stay with their entry point)
+static rd_detector *detector_new(int kind, int device, int iw, int ih, int nslots, int nworkers) {
+  RD_HIP(hipSetDevice(device));
+  rd_detector *d = (rd_detector *)calloc(1, sizeof(*d));
+  d->magic = MAGIC_RECT; d->kind = kind; d->device = device; d->iw = iw; d->ih = ih; d->N = iw * ih; d->nslots = nslots; d->nworkers = nworkers;
+  d->maxrec_dev = d->N * 16 / 56;
+  if (d->maxrec_dev > 65536) d->maxrec_dev = 65536;      // the slots' probe buffers; frames with more records are probed again into a buffer that grows (slot_rectangles)
+  { const int m = rd_env_int("RD_MAXREC_DEV", 0); if (m >= 16 && m < d->maxrec_dev) d->maxrec_dev = m; }      // (tests: exercise that path)
+  d->use_graph = rd_env("RD_NO_GRAPH") ? 0 : 1;
+  d->poly_mode = rd_env("RD_POLY_MULTILAUNCH") ? 0 : 1;      // (tests: the ~85-launch form for every frame)
+  d->force_redo = (rd_env("RD_POLY_FORCE_REDO") ? 1 : 0) | (rd_env("RD_ABSORB_FORCE_SLOW") ? 2 : 0);   // tests: every frame also takes the polyline / absorption fallback
+  // The single-block polyline kernel holds 16 384 live chain pixels; a 1920x1080 frame of the synthetic streams has ~11 000, frames of 3 megapixels and
+  // more are beyond it as a rule: their streams start on the multi-launch form instead of overflowing - and being repeated - until the two-overflow rule
+  // (slot_finish_device, rd_detector_poll_segments) finds that out (3840x2160: 12 of the first 16 frames).  Smaller frames that overflow anyway are still caught by that rule.
+  d->poly_overflows = (long)iw * ih > 3000000L ? 1 : 0;
+  d->batch = 1; d->deferred_slot = -1; d->last_polled_slot = -1;
+  pthread_mutex_init(&d->tan_mu, NULL); pthread_cond_init(&d->tan_cv, NULL);
+  pthread_mutex_init(&d->launch_mu, NULL);
+  d->slots = (Slot *)calloc((size_t)nslots, sizeof(Slot));
+  d->frames = (rdk::PolyFrame *)calloc((size_t)nslots, sizeof(rdk::PolyFrame));
+  return d;
 }
 
-// one frame (nz = 1) or a full group (nz = zb, s = its first slot), as a captured graph per polyline mode
-static void poly_run(rd_detector *d, Slot *s, int nz, hipStream_t st, int mode) {
-  const size_t zs = nz > 1 ? d->slot_pitch : 0;
-  if (!d->use_graph) { poly_segment(d, s, nz, zs, st, mode); return; }
-  hipGraphExec_t *ge = nz > 1 ? &s->gz2[mode] : &s->gexec[mode];
-  if (!*ge) {
-    hipGraph_t g = NULL;
-    pthread_mutex_lock(&d->launch_mu);
-    RD_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-    poly_segment(d, s, nz, zs, st, mode);
-    RD_HIP(hipStreamEndCapture(st, &g));
-    pthread_mutex_unlock(&d->launch_mu);
-    RD_HIP(hipGraphInstantiate(ge, g, NULL, NULL, 0));
-    RD_HIP(hipGraphDestroy(g));
+// streams, group mode, planes and slots, once the kind's own settings (fork_poly, batch) stand
+static void detector_slots(rd_detector *d, int nstreams) {
+  const int nslots = d->nslots;
+  // One stream per frame: the frames beyond the fourth queue up behind earlier ones on the same four streams (slot i uses the
+  // streams of slot i mod 4) - a stream of its own would be time-sliced onto the same four hardware queues and stall frames
+  // that have nothing to do with each other, while a queued frame keeps its queue busy as soon as its predecessor is done
+  // (the host's turn-around between "frame polled" and "next frame enqueued" otherwise idles a quarter of the device).
+  d->nstreams = nstreams < nslots ? nstreams : nslots;
+  // Group mode: four frames per launch from twelve frame slots on (three groups: one being filled, two in flight), two from six on, eight from 32 on
+  // (640x480: 9100 frames/s with 16 slots in groups of four, 11700 with 32 in groups of eight; 1080p: no difference);
+  // RD_ZBATCH=k overrides (k frames per launch, 2..8; 0 / 1: off).
+  d->zb = nslots >= 32 ? 8 : (nslots >= 12 ? 4 : (nslots >= 6 ? 2 : 1));      // (always at least three or four groups: one being filled, the others in flight on the four streams)
+  if ((long long)d->iw * d->ih > 1920ll * 1088) d->zb = 1;      // (launches of larger frames fill the device on their own: 3840x2160 measured 1 % slower in groups)
+  if (rd_env("RD_ZBATCH")) { const int z = rd_env_int("RD_ZBATCH", 1); d->zb = z < 1 ? 1 : (z > RD_ZB_MAX ? RD_ZB_MAX : z); }
+  if (d->fork_poly || d->zb > nslots) d->zb = 1;
+  if (d->zb > 1) { d->batch = 1; d->defer = 0; }      // (a group's sparse stages follow its dense stages on the same stream)
+  if (d->zb > 1) {
+    Slot tmp; memset(&tmp, 0, sizeof(tmp));
+    PlaneAlloc A = { NULL, 0, 2 };
+    slot_planes(d, &tmp, A);
+    d->slot_pitch = A.at;
+    d->arena = dnew<char>((size_t)nslots * d->slot_pitch);
   }
-  RD_HIP(hipGraphLaunch(*ge, st));
+  for (int i = 0; i < nslots; i++) {
+    Slot *s = &d->slots[i];
+    slot_alloc(d, s, (!d->fork_poly && i >= nstreams) ? &d->slots[i % nstreams] : NULL);
+    s->owner = d;
+    pthread_mutex_init(&s->mu, NULL); pthread_cond_init(&s->cv, NULL);
+    if (d->nworkers > 0 && pthread_create(&s->th, NULL, slot_worker, s) != 0) exitf(-1, "rd_detector_create: cannot start worker thread\n");
+  }
+  if (d->kind == RD_KIND_RECT) rdk::quant_lut_init(d->slots[0].st);
+  RD_HIP(hipDeviceSynchronize());
 }
 
-static void poly_enqueue_frame(rd_detector *d, Slot *s, int ws) {
-  RD_HIP(hipEventRecord(s->ev_begin, s->st));
-  s->watch_begin = s->ev_begin; s->watch_done = s->ev_done;
-  s->group_n = 1;
-  if (s->fmt == RD_PIX_BGR) rdk::bgr2plab_transposed(s->st, s->plab0, s->tr, s->src, d->iw, d->ih, ws);      // (outside the graph: its source changes from frame to frame)
-  else pix_front(d, s, 1, s->st);
-  s->poly_mode = current_poly_mode(d);
-  poly_run(d, s, 1, s->st, s->poly_mode);
-  RD_HIP(hipEventRecord(s->ev_done, s->st));
-  rdrt::check_launch("polyline frame");
-}
-
-// the frames waiting in the group that starts at slot g0 (see group_launch: a full group with one row stride -> one set of launches, anything else frame by frame)
-static void poly_group_launch(rd_detector *d, int g0) {
-  const int zb = d->zb;
-  int cnt = 0, same_ws = 1;
-  for (int i = g0; i < g0 + zb && i < d->nslots; i++) { Slot *s = &d->slots[i]; if (s->pending_dense) { cnt++; if (!same_layout(s, &d->slots[g0])) same_ws = 0; } }
-  if (cnt == 0) return;
-  bool travelled = false;
-  for (int i = g0; i < g0 + zb && i < d->nslots; i++) { Slot *s = &d->slots[i]; if (s->pending_dense && s->src == s->bgr && s->uploaded_early) travelled = true; }
-  if (travelled) RD_HIP(hipStreamSynchronize(d->st_upload));
-  if (cnt < zb || !same_ws) {
-    for (int i = g0; i < g0 + zb && i < d->nslots; i++) {
-      Slot *s = &d->slots[i];
-      if (!s->pending_dense) continue;
-      s->pending_dense = 0;
-      if (s->src == s->bgr && !s->uploaded_early) RD_HIP(hipMemcpyAsync(s->bgr, s->h_bgr, (size_t)s->ws * d->ih, hipMemcpyHostToDevice, s->st));
-      poly_enqueue_frame(d, s, s->ws);
-    }
-    return;
-  }
-  Slot *lead = &d->slots[g0];
-  hipStream_t st = group_stream(d, g0);
-  const int ws = lead->ws;
-  const uint8_t *srcs[RD_ZB_MAX];
-  const int pm = current_poly_mode(d);
-  for (int i = 0; i < zb; i++) {
-    Slot *s = &d->slots[g0 + i];
-    s->pending_dense = 0;
-    if (s->src == s->bgr && !s->uploaded_early) RD_HIP(hipMemcpyAsync(s->bgr, s->h_bgr, (size_t)ws * d->ih, hipMemcpyHostToDevice, st));
-    srcs[i] = s->src;
-    s->watch_begin = lead->ev_begin; s->watch_done = lead->ev_done;      // (one pair of events brackets the group)
-    s->group_n = zb; s->poly_mode = pm;
-  }
-  RD_HIP(hipEventRecord(lead->ev_begin, st));
-  if (lead->fmt == RD_PIX_BGR) rdk::bgr2plab_transposed(st, lead->plab0, lead->tr, srcs, d->iw, d->ih, ws, zb, d->slot_pitch);
-  else pix_front(d, lead, zb, st);
-  poly_run(d, lead, zb, st, pm);
-  RD_HIP(hipEventRecord(lead->ev_done, st));
-  rdrt::check_launch("polyline frames, group launch");
+static void slot_destroy_graphs(Slot *s) {
+  for (int g = 0; g < 2; g++) for (int k = 0; k < RD_NSEQ; k++) if (s->graphs[g][k]) { RD_HIP(hipGraphExecDestroy(s->graphs[g][k])); s->graphs[g][k] = NULL; }
 }
 
 extern "C" {
@@ -1314,19 +1217,10 @@ rd_detector *rd_detector_create(int device, int iw, int ih, int nslots, int nwor
   if (iw < 16 || ih < 16) exitf(-1, "rd_detector_create: frame %dx%d too small\n", iw, ih);
   if ((long long)iw * ih >= (1ll << 25)) exitf(-1, "rd_detector_create: frame %dx%d too large (pixel indices are kept below 2^25: hash keys and marked label words rely on the spare bits)\n", iw, ih);
   if (nslots < 1) nslots = 1;
-  RD_HIP(hipSetDevice(device));
-  rd_detector *d = (rd_detector *)calloc(1, sizeof(*d));
-  d->magic = MAGIC_RECT; d->device = device; d->iw = iw; d->ih = ih; d->N = iw * ih; d->nslots = nslots; d->nworkers = nworkers;
-  d->maxrec_dev = d->N * 16 / 56;
-  if (d->maxrec_dev > 65536) d->maxrec_dev = 65536;      // the slots' probe buffers; frames with more records are probed again into a buffer that grows (slot_rectangles)
-  { const int m = rd_env_int("RD_MAXREC_DEV", 0); if (m >= 16 && m < d->maxrec_dev) d->maxrec_dev = m; }      // (tests: exercise that path)
+  rd_detector *d = detector_new(RD_KIND_RECT, device, iw, ih, nslots, nworkers);
   d->nring = nslots + 1;
   d->prev_ring = dnew<int8_t>((size_t)d->N * d->nring);
   RD_HIP(hipMemset(d->prev_ring, 0, (size_t)d->N * d->nring));
-  d->use_graph = rd_env("RD_NO_GRAPH") ? 0 : 1;
-  d->graph_fork = RD_LAB_INT("RD_GRAPH_FORK", 0);
-  d->poly_mode = rd_env("RD_POLY_MULTILAUNCH") ? 0 : 1;      // (tests: the ~85-launch form for every frame)
-  d->force_redo = (rd_env("RD_POLY_FORCE_REDO") ? 1 : 0) | (rd_env("RD_ABSORB_FORCE_SLOW") ? 2 : 0);   // tests: every frame also takes the polyline / absorption fallback
   // candidate funnel + pose estimation on the device (rd_k_post.hip) instead of on one worker thread per frame slot: RD_DEVICE_POST=0|1 decides;
   // otherwise the host path - 0.3 ms of CPU time per 1080p frame, i.e. 0.6 of a core at 2000 frames/s: measured 2050 frames/s on 8 cores
   // as on 256, against 1830 for the device path - unless this process may run on one or two cores only
@@ -1356,10 +1250,6 @@ rd_detector *rd_detector_create(int device, int iw, int ih, int nslots, int nwor
   d->fixed_rounds = 0;
   if (rd_env("RD_REGION_ROUNDS_FIXED")) { const int r = rd_env_int("RD_REGION_ROUNDS_FIXED", 20); d->fixed_rounds = (r >= 8 && r <= 20 && !(r & 1)) ? r : 20; }
   d->rounds_budget = 20;
-  // The single-block polyline kernel holds 16 384 live chain pixels; a 1920x1080 frame of the synthetic streams has ~11 000, frames of 3 megapixels and
-  // more are beyond it as a rule: their streams start on the multi-launch form instead of overflowing - and being repeated - until the two-overflow rule
-  // below finds that out (3840x2160: 12 of the first 16 frames).  Smaller frames that overflow anyway are still caught by that rule.
-  d->poly_overflows = (long)iw * ih > 3000000L ? 1 : 0;
   d->t_edge = 500; d->t_strong = 2500;      // oclrect.c:277-284, 307-313
   if (rd_env("RD_TEST_THRESHOLDS")) {      // tests only: other thresholds, so that many strength sums stand exactly one below one (where the mask of the frame before decides, H1)
     int a = 0, b = 0;
@@ -1367,49 +1257,15 @@ rd_detector *rd_detector_create(int device, int iw, int ih, int nslots, int nwor
   }
   d->strong_by_frame = rd_env("RD_STRONG_BY_FRAME") ? 1 : 0;
   d->budget_cycle = rd_env_int("RD_BUDGET_CYCLE", 0);      // tests: the launch budget changes every so many frames (12, 14, .. 20, 12, ..)
-  pthread_mutex_init(&d->tan_mu, NULL); pthread_cond_init(&d->tan_cv, NULL);
-  pthread_mutex_init(&d->launch_mu, NULL);
-  d->slots = (Slot *)calloc((size_t)nslots, sizeof(Slot));
   // frames per set of sparse-stage launches: 4 from twelve frames in flight on - the deferral by one group below needs a third group of
   // slots to keep the streams fed, and without it a batch is a barrier per group (measured 10 % slower than no batching) - else every
   // frame on its own; RD_BATCH=1..4 overrides (tests: batching with any slot count)
   d->batch = nslots >= 24 ? 8 : (nslots >= 12 ? 4 : 1);      // (these stages are latency-bound chains of gathers: eight frames take a launch as long as four)
   if (rd_env("RD_BATCH")) { const int b = rd_env_int("RD_BATCH", 1); d->batch = b < 1 ? 1 : (b > RD_MAXB ? RD_MAXB : b); }
   if (d->fork_poly || d->batch > nslots) d->batch = d->fork_poly ? 1 : nslots;
-  d->frames = (rdk::PolyFrame *)calloc((size_t)nslots, sizeof(rdk::PolyFrame));
-  d->deferred_slot = -1;
   d->defer = (d->batch > 1 && nslots >= 3 * d->batch) ? 1 : 0;       // needs a third group of slots to keep the streams fed meanwhile
-  // One stream per frame: the frames beyond the fourth queue up behind earlier ones on the same four streams (slot i uses the
-  // streams of slot i mod 4) - a stream of its own would be time-sliced onto the same four hardware queues and stall frames
-  // that have nothing to do with each other, while a queued frame keeps its queue busy as soon as its predecessor is done
-  // (the host's turn-around between "frame polled" and "next frame enqueued" otherwise idles a quarter of the device).
   const int nstreams = RD_LAB_INT("RD_NSTREAMS", 4) < 1 ? 1 : (RD_LAB_INT("RD_NSTREAMS", 4) > 8 ? 8 : RD_LAB_INT("RD_NSTREAMS", 4));      // (measurements only - 3 / 5 / 6 streams: 2776-2786 / 2746-2753 / 2827-2847 frames/s against 2881-2889 with four, one box)
-  d->nstreams = nstreams < nslots ? nstreams : nslots;
-  // Group mode: four frames per launch from twelve frame slots on (three groups: one being filled, two in flight), two from six on, eight from 32 on
-  // (640x480: 9100 frames/s with 16 slots in groups of four, 11700 with 32 in groups of eight; 1080p: no difference);
-  // RD_ZBATCH=k overrides (k frames per launch, 2..8; 0 / 1: off).
-  d->zb = nslots >= 32 ? 8 : (nslots >= 12 ? 4 : (nslots >= 6 ? 2 : 1));      // (always at least three or four groups: one being filled, the others in flight on the four streams)
-  if ((long long)iw * ih > 1920ll * 1088) d->zb = 1;      // (launches of larger frames fill the device on their own: 3840x2160 measured 1 % slower in groups)
-  if (rd_env("RD_ZBATCH")) { const int z = rd_env_int("RD_ZBATCH", 1); d->zb = z < 1 ? 1 : (z > RD_ZB_MAX ? RD_ZB_MAX : z); }
-  if (d->fork_poly || d->zb > nslots || nstreams <= 0) d->zb = 1;
-  if (d->zb > 1) { d->batch = 1; d->defer = 0; }      // (a group's sparse stages follow its dense stages on the same stream)
-  if (d->zb > 1) {
-    Slot tmp; memset(&tmp, 0, sizeof(tmp));
-    PlaneAlloc A = { NULL, 0, 2 };
-    slot_planes(d, &tmp, A);
-    d->slot_pitch = A.at;
-    d->arena = dnew<char>((size_t)nslots * d->slot_pitch);
-  }
-  for (int i = 0; i < nslots; i++) {
-    Slot *s = &d->slots[i];
-    slot_alloc(d, s, (!d->fork_poly && nstreams > 0 && i >= nstreams) ? &d->slots[i % nstreams] : NULL);
-    s->owner = d;
-    pthread_mutex_init(&s->mu, NULL); pthread_cond_init(&s->cv, NULL);
-    if (nworkers > 0 && pthread_create(&s->th, NULL, slot_worker, s) != 0) exitf(-1, "rd_detector_create: cannot start worker thread\n");
-  }
-  d->last_polled_slot = -1;
-  rdk::quant_lut_init(d->slots[0].st);
-  RD_HIP(hipDeviceSynchronize());
+  detector_slots(d, nstreams);
   return d;
 }
 
@@ -1425,10 +1281,7 @@ void rd_detector_destroy(rd_detector *d) {
       pthread_join(s->th, NULL);
     }
     free(s->result); free(s->res_segs);
-    for (int k = 0; k < 3; k++) if (s->gexec[k]) RD_HIP(hipGraphExecDestroy(s->gexec[k]));
-    for (int k = 0; k < 3 * RD_NBUDGETS; k++) if (s->gexec2[k]) RD_HIP(hipGraphExecDestroy(s->gexec2[k]));
-    if (s->gz0) RD_HIP(hipGraphExecDestroy(s->gz0));
-    for (int k = 0; k < 3 * RD_NBUDGETS; k++) if (s->gz2[k]) RD_HIP(hipGraphExecDestroy(s->gz2[k]));
+    slot_destroy_graphs(s);
     slot_free(s, d->device);
   }
   if (d->st_upload) { RD_HIP(hipStreamSynchronize(d->st_upload)); unpool_stream(d->device, d->st_upload); }
@@ -1441,12 +1294,49 @@ void rd_detector_destroy(rd_detector *d) {
   free(d);
 }
 
-// a frame's way to the device: pieces copied into pinned memory (by the caller and whichever helper threads are awake), uploaded in order as they complete
-struct UploadJob { char *dst; const char *src; char *dev; size_t bytes, piece; hipStream_t st; bool nt; int n, uploaded; int ready[64]; };
-static void upload_copy_piece(void *ctx, int i) {
+// ---- hand-over of a frame (rd_detector_enqueue, rd_detector_enqueue_planes)
+// The planes a format uses, their row bytes and rows; and the layout of a host frame packed into a slot's buffers (row strides rounded up to 4 bytes, so that
+// the front kernel reads them a dword per lane; every format then still fits the 4 bytes per pixel of bgr / h_bgr).
+struct PixLayout { int np, row[3], rows[3], pitch[3]; size_t off[3], bytes; };
+static PixLayout pix_layout(int fmt, int iw, int ih) {
+  PixLayout L;
+  memset(&L, 0, sizeof(L));
+  const int bpp = fmt == RD_PIX_BGR || fmt == RD_PIX_RGB ? 3 : 4;
+  if (fmt <= RD_PIX_RGBA) { L.np = 1; L.row[0] = iw * bpp; L.rows[0] = ih; }
+  else if (fmt == RD_PIX_NV12) { L.np = 2; L.row[0] = L.row[1] = iw; L.rows[0] = ih; L.rows[1] = ih / 2; }
+  else { L.np = 3; L.row[0] = iw; L.rows[0] = ih; L.row[1] = L.row[2] = iw / 2; L.rows[1] = L.rows[2] = ih / 2; }
+  for (int k = 0; k < L.np; k++) { L.pitch[k] = (L.row[k] + 3) & ~3; L.off[k] = L.bytes; L.bytes += (size_t)L.pitch[k] * L.rows[k]; }
+  return L;
+}
+// a BGR frame of rd_detector_enqueue keeps the caller's row stride on its way through the slot's buffers: one plane of ws * ih bytes
+static PixLayout bgr_layout(int ws, int ih) {
+  PixLayout L;
+  memset(&L, 0, sizeof(L));
+  L.np = 1; L.row[0] = L.pitch[0] = ws; L.rows[0] = ih; L.bytes = (size_t)ws * ih;
+  return L;
+}
+
+// a pageable frame's way to the device: pieces (byte ranges of the packed layout) gathered from the caller's planes into pinned memory by the caller and whichever
+// helper threads are awake, uploaded in order as they complete
+struct UploadJob { PixLayout L; const uint8_t *src[3]; int spitch[3]; char *dst, *dev; size_t piece; hipStream_t st; int n, uploaded; int ready[16]; };
+static void pack_range(const UploadJob *j, size_t o, size_t end) {
+  for (int k = 0; k < j->L.np; k++) {
+    const size_t p0 = j->L.off[k], pp = (size_t)j->L.pitch[k];
+    const size_t a = o > p0 ? o : p0, b = end < p0 + pp * j->L.rows[k] ? end : p0 + pp * j->L.rows[k];
+    if (a >= b) continue;
+    if (j->spitch[k] == j->L.pitch[k] && j->L.row[k] == j->L.pitch[k]) { rd_copy_to_staging(j->dst + a, j->src[k] + (a - p0), b - a); continue; }      // (the caller's plane is laid out as the packed one - a BGR frame always: one copy)
+    for (size_t r = (a - p0) / pp, at = a; at < b; r++) {      // rows of plane k that meet [a, b)
+      const size_t rs = p0 + r * pp, re = rs + (size_t)j->L.row[k];
+      const size_t c0 = at > rs ? at : rs, c1 = b < re ? b : re;
+      if (c0 < c1) rd_copy_to_staging(j->dst + c0, j->src[k] + r * j->spitch[k] + (c0 - rs), c1 - c0);
+      at = rs + pp;
+    }
+  }
+}
+static void pack_copy_piece(void *ctx, int i) {
   UploadJob *u = (UploadJob *)ctx;
-  const size_t o = (size_t)i * u->piece, m = u->bytes - o < u->piece ? u->bytes - o : u->piece;
-  if (u->nt) rd_copy_to_staging(u->dst + o, u->src + o, m); else memcpy(u->dst + o, u->src + o, m);
+  const size_t o = (size_t)i * u->piece, m = u->L.bytes - o < u->piece ? u->L.bytes - o : u->piece;
+  pack_range(u, o, o + m);
   __atomic_store_n(&u->ready[i], 1, __ATOMIC_RELEASE);
 }
 static void upload_progress(void *ctx) {      // (caller's thread only)
@@ -1454,7 +1344,7 @@ static void upload_progress(void *ctx) {      // (caller's thread only)
   int e = u->uploaded;
   while (e < u->n && __atomic_load_n(&u->ready[e], __ATOMIC_ACQUIRE)) e++;
   if (e == u->uploaded) return;
-  const size_t o = (size_t)u->uploaded * u->piece, end = (size_t)e * u->piece < u->bytes ? (size_t)e * u->piece : u->bytes;
+  const size_t o = (size_t)u->uploaded * u->piece, end = (size_t)e * u->piece < u->L.bytes ? (size_t)e * u->piece : u->L.bytes;
   RD_HIP(hipMemcpyAsync(u->dev + o, u->dst + o, end - o, hipMemcpyHostToDevice, u->st));
   u->uploaded = e;
 }
@@ -1470,24 +1360,17 @@ static bool host_buffer_is_pinned(rd_detector *d, const void *frame) {
   return pinned;
 }
 
-// what follows the hand-over of a frame (rd_detector_enqueue, rd_detector_enqueue_planes): its launches - now, or with its group - and the caller's wait for the copy engine
-static long enqueue_launch(rd_detector *d, Slot *s, int ws, Slot *wait_upload, struct timespec ts0) {
+// what follows the hand-over of a frame: its launches - now, or with its group - and the caller's wait for the copy engine
+static long enqueue_launch(rd_detector *d, Slot *s, Slot *wait_upload, struct timespec ts0) {
+  const int si = (int)(s - d->slots);
   if (d->zb > 1) {      // group mode: launched together with the other frames of its group, once that is full (or a poll needs one of them)
-    const int si = (int)(s - d->slots);
     s->pending_dense = 1;
     // (the last group of slots may be short - nslots need not be a multiple of zb - and is launched when ITS last slot is filled: every group
     //  is launched the moment its last frame arrives, so frames reach the device in sequence order and at most one group is ever waiting)
-    if (si % d->zb == d->zb - 1 || si == d->nslots - 1) { if (d->kind == RD_KIND_POLY) poly_group_launch(d, si / d->zb * d->zb); else group_launch(d, si / d->zb * d->zb); }
-  } else if (d->kind == RD_KIND_POLY) {
-  poly_enqueue_frame(d, s, ws);
+    if (si % d->zb == d->zb - 1 || si == d->nslots - 1) group_launch(d, si / d->zb * d->zb);
   } else {
-  enqueue_frame(d, s, ws);
-  }
-  if (d->zb > 1) ;
-  else if (d->batch == 1) slot_submitted(d, s);
-  else {
-    const int si = (int)(s - d->slots);
-    if (si % d->batch == d->batch - 1 || si == d->nslots - 1) {      // the group is complete
+    launch_frames(d, s, 1, s->st);
+    if (d->batch > 1 && (si % d->batch == d->batch - 1 || si == d->nslots - 1)) {      // the batch is complete
       // Launched right away, the sparse stages would sit in their stream between this group's dense stages and the next one's, waiting
       // for the slowest of the group's four streams: a barrier per group (measured: 10 % slower than no batching).  One group later,
       // everything they wait for is long done and the stream they land on has the next group's dense work queued in front of them.
@@ -1503,128 +1386,93 @@ static long enqueue_launch(rd_detector *d, Slot *s, int ws, Slot *wait_upload, s
   return d->next_enqueue++;
 }
 
-long rd_detector_enqueue(rd_detector *d, const void *frame, int ws, int on_device) {
-  if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_enqueue: bad handle\n");
-  if (d->next_enqueue - d->next_poll >= d->nslots) exitf(-1, "rd_detector_enqueue: %d frames already in flight (poll first)\n", d->nslots);
-  if ((size_t)ws * d->ih > (size_t)d->N * 4) exitf(-1, "rd_detector_enqueue: row stride %d too large for a %dx%d frame\n", ws, d->iw, d->ih);
+// The next slot takes a frame - format, planes and row strides as the entry point `who` checked them; L: the layout a host frame is packed into - and launches it.
+// The BGR frames of rd_detector_enqueue and the frames of the other formats differ in three places, each a condition on fmt below; none of them has been measured the other way.
+static long hand_over(rd_detector *d, const char *who, int fmt, const void *const planes[3], const int pitches[3], const PixLayout &L, int on_device) {
+  if (d->next_enqueue - d->next_poll >= d->nslots) exitf(-1, "%s: %d frames already in flight (poll first)\n", who, d->nslots);
   RD_HIP(hipSetDevice(d->device));
   struct timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
   Slot *s = &d->slots[d->next_enqueue % d->nslots];
-  s->seq = d->next_enqueue; s->ws = ws; s->fmt = RD_PIX_BGR;
-  const size_t bytes = (size_t)ws * d->ih;
+  s->seq = d->next_enqueue; s->fmt = fmt;
+  for (int k = 0; k < 3; k++) { s->pl[k] = NULL; s->pitch[k] = 0; }
   Slot *wait_upload = NULL;
-  if (on_device == RD_FRAME_DEVICE) s->src = (const uint8_t *)frame;      // read where it lies (the caller keeps it valid until the frame's poll returned)
-  else if (on_device == RD_FRAME_HOST_PINNED) {
-    // The caller's buffer is page-locked and stays as it is until the frame's poll: the copy engine takes it from there.  (The reference copies every frame into its own
-    // pinned page first, oclrect.c:1256 - 6 MB per 1920x1080 frame by the caller's thread, 16 GB/s at full rate on the thread that also launches everything.)
-    if (!(frame >= d->pinned_lo && (const char *)frame + bytes <= (const char *)d->pinned_hi)) {      // (one look per buffer, not per frame: a capture loop reuses its pages)
-      hipPointerAttribute_t at;
-      if (hipPointerGetAttributes(&at, frame) != hipSuccess || at.type != hipMemoryTypeHost) { (void)hipGetLastError(); exitf(-1, "rd_detector_enqueue: RD_FRAME_HOST_PINNED needs pinned host memory (rd_host_alloc, allocatePinnedMemory, hipHostMalloc, hipHostRegister); %p is not\n", frame); }
-      d->pinned_lo = frame; d->pinned_hi = (const char *)frame + bytes;
-    }
-    // (The colour conversion reading the pinned buffer over PCIe itself, without the copy engine: 1985-2009 frames/s against 2656-2659 - the kernel then runs at the link's
-    //  rate, a millisecond per group, with its blocks resident all the while.  profiles/NOTES_r06.md.)
+  const bool group = d->zb > 1;
+  if (on_device == RD_FRAME_DEVICE) {      // read where they lie (the caller keeps them valid until the frame's poll returned)
+    for (int k = 0; k < L.np; k++) { s->pl[k] = (const uint8_t *)planes[k]; s->pitch[k] = pitches[k]; }
+  } else {      // host frames: through the slot's buffers, one plane after the other
+    for (int k = 0; k < L.np; k++) { s->pl[k] = s->bgr + L.off[k]; s->pitch[k] = L.pitch[k]; }
+    // Group mode: the frame travels NOW, on a stream of the detector's own (high-priority pool: a hardware queue nobody computes on), not when its group is launched:
+    // eight uploads in front of a group's kernels kept that group's stream - a quarter of the device's queues - waiting for the copy engine for 1.6 of its 10.8 ms; and
+    // an ordinary stream shares a hardware queue with a group's: 2786-2796 frames/s, the caller waiting 0.35 ms per frame.  No event: group_launch waits for the stream.
     hipStream_t ust = s->st;
-    s->uploaded_early = 0;
-    if (d->zb > 1) { if (!d->st_upload) d->st_upload = pooled_stream(d->device); ust = d->st_upload; }      // (group mode: on the detector's upload stream, from the high-priority pool; an ordinary stream shares a hardware queue with a group's: 2786-2796 frames/s, the caller waiting 0.35 ms per frame)
-    if (d->zb > 1) RD_HIP(hipStreamSynchronize(ust));      // (one transfer in the copy engine's queue at a time: the caller waits for the frame before - 0.1 ms where it used to copy for 0.16 - see group_launch)
-    RD_HIP(hipMemcpyAsync(s->bgr, frame, bytes, hipMemcpyHostToDevice, ust));
-    if (d->zb > 1) s->uploaded_early = 1;      // (no event here: group_launch records ONE behind the uploads of all its frames - see there)
-    s->src = s->bgr;
-    d->n_frames_pinned++;
-  }
-  else if (on_device != RD_FRAME_HOST) exitf(-1, "rd_detector_enqueue: on_device = %d (0: host memory, 1: device memory, 2: pinned host memory)\n", on_device);
-  else if (d->zb == 1 && host_buffer_is_pinned(d, frame)) {
-    // The reference's call shape (oclrect_enqueueTask / executeOnce) on a buffer that happens to be page-locked - allocatePinnedMemory of oclhelper.h hands such memory out
-    // (oclhelper.c:837-851, poly.cpp:68-69): the copy engine reads it in place, nothing is copied by the caller's thread, and the frame's kernels are launched behind the
-    // transfer at once.  The reference's contract - the caller may reuse the buffer as soon as the call returns (oclrect.c:1256 copies it) - is kept by returning only when
-    // the engine has read it: waited for at the END of this call (enqueue_done), after the frame's ~45 launches, by which time it has long happened (6 MB in 0.12 ms).
-    RD_HIP(hipMemcpyAsync(s->bgr, frame, bytes, hipMemcpyHostToDevice, s->st));
-    RD_HIP(hipEventRecord(s->ev_upload, s->st));
-    s->src = s->bgr;
-    wait_upload = s;
-    d->n_frames_pinned++;
-  }
-  else if (d->zb == 1) {
-    d->n_frames_copied++;
-    // a single frame: the copy into pinned memory and the upload in pieces, so that a piece travels while the next is being copied (6 MB at 1920x1080:
-    // the copy alone takes a fifth of a millisecond of the caller's latency).  With helper threads (armed here: the call that hands a frame over is followed by
-    // the poll that waits for one) the pieces are copied side by side and uploaded in order as they complete.
-    static const bool nt_copy = RD_LAB_INT("RD_NT_COPY", 1) != 0;
-    static const int npieces_env = RD_LAB_INT("RD_UPLOAD_PIECES", 0);
-    static const bool par_copy = RD_LAB_INT("RD_PARALLEL_COPY", 1) != 0;
-    const bool helpers = d->post_helpers > 0 && par_copy;
-    if (helpers) rd_post_helpers_arm();
-    int npieces = npieces_env > 0 ? npieces_env : (helpers ? 16 : 4);
-    if (npieces > 64) npieces = 64;
-    UploadJob u;
-    u.dst = (char *)s->h_bgr; u.src = (const char *)frame; u.dev = (char *)s->bgr; u.bytes = bytes; u.st = s->st; u.nt = nt_copy; u.uploaded = 0;
-    u.piece = ((bytes + npieces - 1) / npieces + 4095) & ~(size_t)4095;
-    u.n = (int)((bytes + u.piece - 1) / u.piece);
-    for (int i = 0; i < u.n; i++) u.ready[i] = 0;
-    rd_helpers_run(upload_copy_piece, &u, u.n, upload_progress);
-    upload_progress(&u);
-    if (u.uploaded != u.n) exitf(-1, "rd_detector_enqueue: internal error (pieces of the frame left behind)\n");
-    s->src = s->bgr;
-  } else {      // (group mode: the group's frames are uploaded together when it is launched)
-    d->n_frames_copied++;
-    static const bool nt_copy_g = RD_LAB_INT("RD_NT_COPY", 1) != 0;
-    if (nt_copy_g) rd_copy_to_staging(s->h_bgr, frame, bytes); else memcpy(s->h_bgr, frame, bytes);
-    s->src = s->bgr;
-    // The frame travels NOW, on a stream of the detector's own (high-priority pool: a hardware queue nobody computes on), not when its group is launched: eight uploads in
-    // front of a group's kernels kept that group's stream - a quarter of the device's queues - waiting for the copy engine for 1.6 of its 10.8 ms.  The group's stream
-    // waits for the event instead (group_launch).  RD_UPLOAD_EARLY=0: as before.
-    static const bool upload_early = RD_LAB_INT("RD_UPLOAD_EARLY", 1) != 0;
-    s->uploaded_early = 0;
-    if (upload_early) {
-      if (!d->st_upload) d->st_upload = pooled_stream(d->device);
-      RD_HIP(hipMemcpyAsync(s->bgr, s->h_bgr, bytes, hipMemcpyHostToDevice, d->st_upload));
-      s->uploaded_early = 1;      // (no event here: group_launch records ONE behind the uploads of all its frames)
-    }
-  }
-  return enqueue_launch(d, s, ws, wait_upload, ts0);
-}
-
-// ---- frames in other pixel formats (rd_detector_enqueue_planes)
-// The planes a format uses, their row bytes and rows; and the layout of a host frame packed into a slot's buffers (row strides rounded up to 4 bytes, so that
-// the front kernel reads them a dword per lane; every format then still fits the 4 bytes per pixel of bgr / h_bgr).
-struct PixLayout { int np, row[3], rows[3], pitch[3]; size_t off[3], bytes; };
-static PixLayout pix_layout(int fmt, int iw, int ih) {
-  PixLayout L;
-  memset(&L, 0, sizeof(L));
-  const int bpp = fmt == RD_PIX_BGR || fmt == RD_PIX_RGB ? 3 : 4;
-  if (fmt <= RD_PIX_RGBA) { L.np = 1; L.row[0] = iw * bpp; L.rows[0] = ih; }
-  else if (fmt == RD_PIX_NV12) { L.np = 2; L.row[0] = L.row[1] = iw; L.rows[0] = ih; L.rows[1] = ih / 2; }
-  else { L.np = 3; L.row[0] = iw; L.rows[0] = ih; L.row[1] = L.row[2] = iw / 2; L.rows[1] = L.rows[2] = ih / 2; }
-  for (int k = 0; k < L.np; k++) { L.pitch[k] = (L.row[k] + 3) & ~3; L.off[k] = L.bytes; L.bytes += (size_t)L.pitch[k] * L.rows[k]; }
-  return L;
-}
-
-// a host frame's pieces (byte ranges of the packed layout) gathered from the caller's planes by the caller and whichever helper threads are awake, uploaded in order
-// as they complete (upload_progress; the same piecewise hand-over as a BGR frame's)
-struct PackJob { UploadJob u; PixLayout L; const uint8_t *src[3]; int spitch[3]; };
-static void pack_range(const PackJob *j, size_t o, size_t end) {
-  for (int k = 0; k < j->L.np; k++) {
-    const size_t p0 = j->L.off[k], pp = (size_t)j->L.pitch[k];
-    const size_t a = o > p0 ? o : p0, b = end < p0 + pp * j->L.rows[k] ? end : p0 + pp * j->L.rows[k];
-    for (size_t r = a < b ? (a - p0) / pp : 0, at = a; at < b; r++) {      // rows of plane k that meet [a, b)
-      const size_t rs = p0 + r * pp, re = rs + (size_t)j->L.row[k];
-      const size_t c0 = at > rs ? at : rs, c1 = b < re ? b : re;
-      if (c0 < c1) {
-        if (j->u.nt) rd_copy_to_staging(j->u.dst + c0, j->src[k] + r * j->spitch[k] + (c0 - rs), c1 - c0);
-        else memcpy(j->u.dst + c0, j->src[k] + r * j->spitch[k] + (c0 - rs), c1 - c0);
+    if (group) { if (!d->st_upload) d->st_upload = pooled_stream(d->device); ust = d->st_upload; }
+    if (on_device == RD_FRAME_HOST_PINNED) {
+      // The caller's planes are page-locked and stay as they are until the frame's poll: the copy engine takes them from there.  (The reference copies every frame into its own
+      // pinned page first, oclrect.c:1256 - 6 MB per 1920x1080 frame by the caller's thread, 16 GB/s at full rate on the thread that also launches everything.)
+      for (int k = 0; k < L.np; k++) {
+        const void *lo = planes[k], *hi = (const char *)planes[k] + (size_t)pitches[k] * (L.rows[k] - 1) + L.row[k];
+        bool known = false;      // (one look per range, not per frame: a capture loop reuses its pages)
+        for (int e = 0; e < 4 && !known; e++) known = lo >= d->pinned[e][0] && hi <= d->pinned[e][1];
+        if (known) continue;
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, planes[k]) != hipSuccess || at.type != hipMemoryTypeHost) { (void)hipGetLastError(); exitf(-1, "%s: RD_FRAME_HOST_PINNED needs pinned host memory (rd_host_alloc, allocatePinnedMemory, hipHostMalloc, hipHostRegister); plane %d at %p is not\n", who, k, planes[k]); }
+        const unsigned e = d->pinned_next++ & 3;
+        d->pinned[e][0] = lo; d->pinned[e][1] = hi;
       }
-      at = rs + pp;
+      // (The colour conversion reading the pinned buffer over PCIe itself, without the copy engine: 1985-2009 frames/s against 2656-2659 - the kernel then runs at the link's
+      //  rate, a millisecond per group, with its blocks resident all the while.  profiles/NOTES_r06.md.)
+      if (group) RD_HIP(hipStreamSynchronize(ust));      // (one transfer in the copy engine's queue at a time: the caller waits for the frame before - 0.1 ms where it used to copy for 0.16 - see group_launch)
+      for (int k = 0; k < L.np; k++) {
+        if (pitches[k] == L.row[k] && L.row[k] == L.pitch[k]) RD_HIP(hipMemcpyAsync(s->bgr + L.off[k], planes[k], (size_t)L.row[k] * L.rows[k], hipMemcpyHostToDevice, ust));
+        else RD_HIP(hipMemcpy2DAsync(s->bgr + L.off[k], L.pitch[k], planes[k], pitches[k], L.row[k], L.rows[k], hipMemcpyHostToDevice, ust));
+      }
+      d->n_frames_pinned++;
+    } else if (!group && fmt == RD_PIX_BGR && host_buffer_is_pinned(d, planes[0])) {      // (only rd_detector_enqueue's frames ask)
+      // The reference's call shape (oclrect_enqueueTask / executeOnce) on a buffer that happens to be page-locked - allocatePinnedMemory of oclhelper.h hands such memory out
+      // (oclhelper.c:837-851, poly.cpp:68-69): the copy engine reads it in place, nothing is copied by the caller's thread, and the frame's kernels are launched behind the
+      // transfer at once.  The reference's contract - the caller may reuse the buffer as soon as the call returns (oclrect.c:1256 copies it) - is kept by returning only when
+      // the engine has read it: waited for at the END of this call (enqueue_launch), after the frame's ~45 launches, by which time it has long happened (6 MB in 0.12 ms).
+      RD_HIP(hipMemcpyAsync(s->bgr, planes[0], L.bytes, hipMemcpyHostToDevice, s->st));
+      RD_HIP(hipEventRecord(s->ev_upload, s->st));
+      wait_upload = s;
+      d->n_frames_pinned++;
+    } else {
+      d->n_frames_copied++;
+      UploadJob u;
+      u.L = L; u.dst = (char *)s->h_bgr; u.dev = (char *)s->bgr; u.st = ust; u.uploaded = 0;
+      for (int k = 0; k < 3; k++) { u.src[k] = (const uint8_t *)planes[k]; u.spitch[k] = pitches[k]; }
+      if (group) {      // the caller's thread packs, then the frame travels at once
+        pack_range(&u, 0, L.bytes);
+        if (fmt != RD_PIX_BGR) RD_HIP(hipStreamSynchronize(ust));      // (one transfer queued at a time, as the pinned frames'; a BGR frame's upload is queued behind the one before without this wait)
+        RD_HIP(hipMemcpyAsync(s->bgr, s->h_bgr, L.bytes, hipMemcpyHostToDevice, ust));
+      } else {
+        // a single frame: the copy into pinned memory and the upload in pieces, so that a piece travels while the next is being copied (6 MB at 1920x1080:
+        // the copy alone takes a fifth of a millisecond of the caller's latency).  With helper threads (armed here: the call that hands a frame over is followed by
+        // the poll that waits for one) the pieces are copied side by side and uploaded in order as they complete.
+        const bool helpers = d->post_helpers > 0;
+        if (helpers) rd_post_helpers_arm();
+        const int npieces = helpers ? 16 : 4;
+        u.piece = ((L.bytes + npieces - 1) / npieces + 4095) & ~(size_t)4095;
+        u.n = (int)((L.bytes + u.piece - 1) / u.piece);      // (<= npieces)
+        for (int i = 0; i < u.n; i++) u.ready[i] = 0;
+        rd_helpers_run(pack_copy_piece, &u, u.n, upload_progress);
+        upload_progress(&u);
+        if (u.uploaded != u.n) exitf(-1, "%s: internal error (pieces of the frame left behind)\n", who);
+      }
     }
   }
+  s->src = s->pl[0]; s->ws = s->pitch[0];
+  return enqueue_launch(d, s, wait_upload, ts0);
 }
-static void pack_copy_piece(void *ctx, int i) {
-  PackJob *j = (PackJob *)ctx;
-  const size_t o = (size_t)i * j->u.piece, m = j->u.bytes - o < j->u.piece ? j->u.bytes - o : j->u.piece;
-  pack_range(j, o, o + m);
-  __atomic_store_n(&j->u.ready[i], 1, __ATOMIC_RELEASE);
+
+long rd_detector_enqueue(rd_detector *d, const void *frame, int ws, int on_device) {
+  if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_enqueue: bad handle\n");
+  if ((size_t)ws * d->ih > (size_t)d->N * 4) exitf(-1, "rd_detector_enqueue: row stride %d too large for a %dx%d frame\n", ws, d->iw, d->ih);
+  if (on_device != RD_FRAME_HOST && on_device != RD_FRAME_DEVICE && on_device != RD_FRAME_HOST_PINNED) exitf(-1, "rd_detector_enqueue: on_device = %d (0: host memory, 1: device memory, 2: pinned host memory)\n", on_device);
+  const void *const planes[3] = { frame, NULL, NULL };
+  const int pitches[3] = { ws, 0, 0 };
+  return hand_over(d, "rd_detector_enqueue", RD_PIX_BGR, planes, pitches, bgr_layout(ws, d->ih), on_device);
 }
-static void pack_progress(void *ctx) { upload_progress(&((PackJob *)ctx)->u); }
 
 long rd_detector_enqueue_planes(rd_detector *d, int format, const void *const planes[3], const int pitches[3], int on_device) {
   if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_enqueue_planes: bad handle\n");
@@ -1635,68 +1483,13 @@ long rd_detector_enqueue_planes(rd_detector *d, int format, const void *const pl
   const PixLayout L = pix_layout(format, d->iw, d->ih);
   for (int k = 0; k < L.np; k++) if (!planes[k] || pitches[k] < L.row[k]) return -1;
   if (format == RD_PIX_BGR) return rd_detector_enqueue(d, planes[0], pitches[0], on_device);
-  if (d->next_enqueue - d->next_poll >= d->nslots) exitf(-1, "rd_detector_enqueue_planes: %d frames already in flight (poll first)\n", d->nslots);
-  RD_HIP(hipSetDevice(d->device));
-  struct timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
-  Slot *s = &d->slots[d->next_enqueue % d->nslots];
-  s->seq = d->next_enqueue; s->fmt = format;
-  for (int k = 0; k < 3; k++) { s->pl[k] = NULL; s->pitch[k] = 0; }
-  if (on_device == RD_FRAME_DEVICE) {      // read where they lie
-    for (int k = 0; k < L.np; k++) { s->pl[k] = (const uint8_t *)planes[k]; s->pitch[k] = pitches[k]; }
-  } else {      // host frames: packed into the slot's buffers, one plane after the other
-    for (int k = 0; k < L.np; k++) { s->pl[k] = s->bgr + L.off[k]; s->pitch[k] = L.pitch[k]; }
-    s->uploaded_early = 0;
-    hipStream_t ust = s->st;
-    if (d->zb > 1) {      // (group mode: on the detector's upload stream, one transfer queued at a time, no event: as rd_detector_enqueue's frames - see group_launch)
-      if (!d->st_upload) d->st_upload = pooled_stream(d->device);
-      ust = d->st_upload;
-      s->uploaded_early = 1;
-    }
-    if (on_device == RD_FRAME_HOST_PINNED) {      // every plane pinned; the copy engine gathers them
-      for (int k = 0; k < L.np; k++) {
-        const size_t span = (size_t)pitches[k] * (L.rows[k] - 1) + L.row[k];
-        const void *lo = planes[k], *hi = (const char *)planes[k] + span;
-        bool known = false;      // (one look per plane range, not per frame: a capture loop reuses its pages)
-        for (int e = 0; e < 4 && !known; e++) known = lo >= d->pinned_pl[e][0] && hi <= d->pinned_pl[e][1];
-        if (known) continue;
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, planes[k]) != hipSuccess || at.type != hipMemoryTypeHost) { (void)hipGetLastError(); exitf(-1, "rd_detector_enqueue_planes: RD_FRAME_HOST_PINNED needs pinned host memory (rd_host_alloc, allocatePinnedMemory, hipHostMalloc, hipHostRegister); plane %d at %p is not\n", k, planes[k]); }
-        const unsigned e = d->pinned_pl_next++ & 3;
-        d->pinned_pl[e][0] = lo; d->pinned_pl[e][1] = hi;
-      }
-      if (d->zb > 1) RD_HIP(hipStreamSynchronize(ust));
-      for (int k = 0; k < L.np; k++) {
-        if (pitches[k] == L.row[k] && L.row[k] == L.pitch[k]) RD_HIP(hipMemcpyAsync(s->bgr + L.off[k], planes[k], (size_t)L.row[k] * L.rows[k], hipMemcpyHostToDevice, ust));
-        else RD_HIP(hipMemcpy2DAsync(s->bgr + L.off[k], L.pitch[k], planes[k], pitches[k], L.row[k], L.rows[k], hipMemcpyHostToDevice, ust));
-      }
-      d->n_frames_pinned++;
-    } else {
-      static const bool nt_copy = RD_LAB_INT("RD_NT_COPY", 1) != 0;
-      PackJob j;
-      j.L = L;
-      for (int k = 0; k < 3; k++) { j.src[k] = (const uint8_t *)planes[k]; j.spitch[k] = pitches[k]; }
-      UploadJob &u = j.u;
-      u.dst = (char *)s->h_bgr; u.src = NULL; u.dev = (char *)s->bgr; u.bytes = L.bytes; u.st = ust; u.nt = nt_copy; u.uploaded = 0;
-      if (d->zb > 1) {      // (group mode: the caller's thread packs, then the frame travels at once)
-        pack_range(&j, 0, L.bytes);
-        RD_HIP(hipStreamSynchronize(ust));
-        RD_HIP(hipMemcpyAsync(s->bgr, s->h_bgr, L.bytes, hipMemcpyHostToDevice, ust));
-      } else {      // (a single frame: in pieces, as rd_detector_enqueue's)
-        const bool helpers = d->post_helpers > 0;
-        if (helpers) rd_post_helpers_arm();
-        const int npieces = helpers ? 16 : 4;
-        u.piece = ((L.bytes + npieces - 1) / npieces + 4095) & ~(size_t)4095;
-        u.n = (int)((L.bytes + u.piece - 1) / u.piece);
-        for (int i = 0; i < u.n; i++) u.ready[i] = 0;
-        rd_helpers_run(pack_copy_piece, &j, u.n, pack_progress);
-        pack_progress(&j);
-        if (u.uploaded != u.n) exitf(-1, "rd_detector_enqueue_planes: internal error (pieces of the frame left behind)\n");
-      }
-      d->n_frames_copied++;
-    }
-  }
-  s->src = s->pl[0]; s->ws = s->pitch[0];
-  return enqueue_launch(d, s, s->ws, NULL, ts0);
+  return hand_over(d, "rd_detector_enqueue_planes", format, planes, pitches, L, on_device);
+}
+
+// device time of a polled frame (counters 1 and 2): the interval its events bracket - a group's is shared by its frames: each counts its part
+static void count_device_time(rd_detector *d, const Slot *s) {
+  float ms = 0.0f;
+  if (hipEventElapsedTime(&ms, s->watch_begin, s->watch_done) == hipSuccess) { d->dev_us += (long)(ms * 1000.0f) / (s->group_n > 0 ? s->group_n : 1); d->dev_frames++; }
 }
 
 void *rd_detector_poll(rd_detector *d, double tanAOV) {
@@ -1741,7 +1534,7 @@ void *rd_detector_poll(rd_detector *d, double tanAOV) {
       if (++n % 100 == 0) { fprintf(stderr, "poll: wait %.1f us, finish %.1f us, rectangles %.1f us (average of 100)\n", a / 100, b / 100, c / 100); a = b = c = 0; }
     }
   }
-  { float ms = 0.0f; if (hipEventElapsedTime(&ms, s->watch_begin, s->watch_done) == hipSuccess) { d->dev_us += (long)(ms * 1000.0f) / (s->group_n > 0 ? s->group_n : 1); d->dev_frames++; } }      // (a group's interval is shared by its frames: counted once)
+  count_device_time(d, s);
   free(d->last_segs);
   d->last_segs = segs; d->last_nsegs = ns;
   d->last_polled_slot = si;
@@ -1766,7 +1559,7 @@ void rd_detector_drain(rd_detector *d) {
   if (d->batch > 1) for (int i = 0; i < d->nslots; i += d->batch) sparse_flush(d, i);
   if (d->zb > 1) for (long q = d->next_poll; q < d->next_enqueue; q++) {      // (sequence order)
     const int si = (int)(q % d->nslots);
-    if (d->slots[si].pending_dense) { if (d->kind == RD_KIND_POLY) poly_group_launch(d, si / d->zb * d->zb); else group_launch(d, si / d->zb * d->zb); }
+    if (d->slots[si].pending_dense) group_launch(d, si / d->zb * d->zb);
   }
   for (int i = 0; i < d->nslots; i++) RD_HIP(hipStreamSynchronize(d->slots[i].st));
 }
@@ -1809,6 +1602,27 @@ int rd_detector_last_segments(rd_detector *d, void *dst, int max_records) {
 }
 
 static size_t poly_debug_plane(rd_detector *d, Slot *s, const char *name, void *dst, size_t max_bytes);
+// A plane kept as bits on the device (ceil(iw / 64) words per row), handed out as an int plane.  junction: not the bits but the junction counts
+// (oclrect.cl:74-95: on-pixels of the 3x3 block, 1 -> 0, frame border 0) evaluated from them.
+static size_t bit_plane_as_ints(rd_detector *d, const void *bits, int junction, void *dst, size_t max_bytes) {
+  const size_t n = (size_t)d->N * 4 <= max_bytes ? (size_t)d->N : max_bytes / 4;
+  const int wpr = (d->iw + 63) / 64, iw = d->iw, ih = d->ih;
+  unsigned long long *tmp = (unsigned long long *)malloc((size_t)wpr * ih * 8 + 8);
+  if (!tmp) exitf(-1, "rd_detector_debug_plane: out of memory\n");
+  RD_HIP(hipMemcpy(tmp, bits, (size_t)wpr * ih * 8, hipMemcpyDeviceToHost));
+  auto bit = [&](int x, int y) { return (int)((tmp[(size_t)y * wpr + (x >> 6)] >> (x & 63)) & 1ull); };
+  for (size_t k = 0; k < n; k++) {
+    const int y = (int)(k / iw), x = (int)(k % iw);
+    int v = bit(x, y);
+    if (junction) {
+      if (v && x > 0 && y > 0 && x < iw - 1 && y < ih - 1) { int c = 0; for (int dy = -1; dy <= 1; dy++) for (int dx = -1; dx <= 1; dx++) c += bit(x + dx, y + dy); v = c == 1 ? 0 : c; }
+      else v = 0;
+    }
+    ((int *)dst)[k] = v;
+  }
+  free(tmp);
+  return n * 4;
+}
 size_t rd_detector_debug_plane(rd_detector *d, const char *name, void *dst, size_t max_bytes) {
   if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_debug_plane: bad handle\n");
   if (d->last_polled_slot < 0) return 0;
@@ -1836,24 +1650,8 @@ size_t rd_detector_debug_plane(rd_detector *d, const char *name, void *dst, size
       RD_HIP(hipStreamSynchronize(s->st));
       if (!strcmp(name, "strong") || !strcmp(name, "mergemask") || !strcmp(name, "junction")) {
         // kept as bit planes on the device (what the polyline stage traces / what the region stage reads); handed out as the int planes of
-        // oclrect.c:307-321 - the junction counts (oclrect.cl:74-95: on-pixels of the 3x3 block, 1 -> 0, frame border 0) evaluated here from the strong mask
-        const size_t n = N * 4 <= max_bytes ? N : max_bytes / 4;
-        const int wpr = (d->iw + 63) / 64, iw = d->iw, ih = d->ih;
-        unsigned long long *tmp = (unsigned long long *)malloc((size_t)wpr * ih * 8 + 8);
-        if (!tmp) exitf(-1, "rd_detector_debug_plane: out of memory\n");
-        RD_HIP(hipMemcpy(tmp, tab[i].p, (size_t)wpr * ih * 8, hipMemcpyDeviceToHost));
-        auto bit = [&](int x, int y) { return (int)((tmp[(size_t)y * wpr + (x >> 6)] >> (x & 63)) & 1ull); };
-        for (size_t k = 0; k < n; k++) {
-          const int y = (int)(k / iw), x = (int)(k % iw);
-          int v = bit(x, y);
-          if (!strcmp(name, "junction")) {
-            if (v && x > 0 && y > 0 && x < iw - 1 && y < ih - 1) { int c = 0; for (int dy = -1; dy <= 1; dy++) for (int dx = -1; dx <= 1; dx++) c += bit(x + dx, y + dy); v = c == 1 ? 0 : c; }
-            else v = 0;
-          }
-          ((int *)dst)[k] = v;
-        }
-        free(tmp);
-        return n * 4;
+        // oclrect.c:307-321 - the junction counts from the strong mask
+        return bit_plane_as_ints(d, tab[i].p, !strcmp(name, "junction"), dst, max_bytes);
       }
       if (!strcmp(name, "mask0")) {         // not stored on the frame path: the mask of positive responses (oclrect.c:262-264), from the suppressed strength
         const size_t n = N * 4 <= max_bytes ? N : max_bytes / 4;
@@ -1890,46 +1688,11 @@ rd_detector *rd_polyline_detector_create(int device, int iw, int ih, int nslots,
   if (iw < 16 || ih < 16 || (long long)iw * ih >= (1ll << 25) || nslots < 1 || device < 0 || strength_thre < 0 || !(minerror > 0.0f) || size_thre < 0) return NULL;
   if (rd_device_count() <= 0) exitf(-1, "rd_polyline_detector_create: no HIP device available - this library has no CPU path\n");
   if (device >= rd_device_count()) return NULL;
-  RD_HIP(hipSetDevice(device));
-  rd_detector *d = (rd_detector *)calloc(1, sizeof(*d));
-  d->magic = MAGIC_RECT; d->kind = RD_KIND_POLY;
-  d->device = device; d->iw = iw; d->ih = ih; d->N = iw * ih; d->nslots = nslots; d->nworkers = 0;
+  rd_detector *d = detector_new(RD_KIND_POLY, device, iw, ih, nslots, 0);
   d->p_thre = strength_thre; d->p_minerror = minerror; d->p_size = size_thre;
   d->handoff_rec = RD_POLY_HANDOFF_DEFAULT;
   { const int h = rd_env_int("RD_POLY_HANDOFF", 0); if (h >= 2) d->handoff_rec = h; }      // (tests: a small block, so that ordinary frames take the long-list path)
-  d->maxrec_dev = d->N * 16 / 56;
-  if (d->maxrec_dev > 65536) d->maxrec_dev = 65536;
-  d->use_graph = rd_env("RD_NO_GRAPH") ? 0 : 1;
-  d->poly_mode = rd_env("RD_POLY_MULTILAUNCH") ? 0 : 1;
-  d->force_redo = rd_env("RD_POLY_FORCE_REDO") ? 1 : 0;
-  d->poly_overflows = (long)iw * ih > 3000000L ? 1 : 0;      // (as the rect kind: 3840x2160 starts on the multi-launch form)
-  d->batch = 1; d->defer = 0; d->deferred_slot = -1; d->fork_poly = 0; d->device_post = 0;
-  pthread_mutex_init(&d->tan_mu, NULL); pthread_cond_init(&d->tan_cv, NULL);
-  pthread_mutex_init(&d->launch_mu, NULL);
-  d->slots = (Slot *)calloc((size_t)nslots, sizeof(Slot));
-  d->frames = (rdk::PolyFrame *)calloc((size_t)nslots, sizeof(rdk::PolyFrame));
-  // streams and group launches as the rect kind (rd_detector_create): four streams, groups of 2 / 4 / 8 frames from 6 / 12 / 32 slots on, none above 1920x1088
-  const int nstreams = 4;
-  d->nstreams = nstreams < nslots ? nstreams : nslots;
-  d->zb = nslots >= 32 ? 8 : (nslots >= 12 ? 4 : (nslots >= 6 ? 2 : 1));
-  if ((long long)iw * ih > 1920ll * 1088) d->zb = 1;
-  if (rd_env("RD_ZBATCH")) { const int z = rd_env_int("RD_ZBATCH", 1); d->zb = z < 1 ? 1 : (z > RD_ZB_MAX ? RD_ZB_MAX : z); }
-  if (d->zb > nslots) d->zb = 1;
-  if (d->zb > 1) {
-    Slot tmp; memset(&tmp, 0, sizeof(tmp));
-    PlaneAlloc A = { NULL, 0, 2 };
-    slot_planes(d, &tmp, A);
-    d->slot_pitch = A.at;
-    d->arena = dnew<char>((size_t)nslots * d->slot_pitch);
-  }
-  for (int i = 0; i < nslots; i++) {
-    Slot *s = &d->slots[i];
-    slot_alloc(d, s, i >= nstreams ? &d->slots[i % nstreams] : NULL);
-    s->owner = d;
-    pthread_mutex_init(&s->mu, NULL); pthread_cond_init(&s->cv, NULL);
-  }
-  d->last_polled_slot = -1;
-  RD_HIP(hipDeviceSynchronize());
+  detector_slots(d, 4);      // (streams and group launches as the rect kind's; no second stream per frame, no batches, no rectangles: fork_poly, defer and device_post stay 0)
   return d;
 }
 
@@ -1941,7 +1704,7 @@ void *rd_detector_poll_segments(rd_detector *d, int32_t *ids_out) {
   const int si = (int)(d->next_poll % d->nslots);
   Slot *s = &d->slots[si];
   const size_t N = (size_t)d->N;
-  if (s->pending_dense) poly_group_launch(d, si / d->zb * d->zb);      // (an incomplete group: the caller wants a result before handing over more frames)
+  if (s->pending_dense) group_launch(d, si / d->zb * d->zb);      // (an incomplete group: the caller wants a result before handing over more frames)
   RD_HIP(hipEventSynchronize(s->watch_done));
   // the single-block polyline kernel gave up on this frame (on-chip tables too small): the stage again in multi-launch form, on the slot's own stream (the
   // frame is finished; its slot is not reused before this poll returns); two such frames in a row send the stream's later frames to the multi-launch form
@@ -1965,7 +1728,7 @@ void *rd_detector_poll_segments(rd_detector *d, int32_t *ids_out) {
     RD_HIP(hipMemcpyAsync(ids_out, s->lsid, N * 4, hipMemcpyDeviceToHost, s->st_redo));
     RD_HIP(hipStreamSynchronize(s->st_redo));
   }
-  { float ms = 0.0f; if (hipEventElapsedTime(&ms, s->watch_begin, s->watch_done) == hipSuccess) { d->dev_us += (long)(ms * 1000.0f) / (s->group_n > 0 ? s->group_n : 1); d->dev_frames++; } }
+  count_device_time(d, s);
   d->last_polled_slot = si;
   d->next_poll++;
   return out;
@@ -1984,15 +1747,7 @@ static size_t poly_debug_plane(rd_detector *d, Slot *s, const char *name, void *
     if (strcmp(tab[i].n, name)) continue;
     if (!strcmp(name, "lsid")) { rdk::polyline_ids(s->st, s->frame, 1, (int)N); rdrt::check_launch("polyline ids"); }
     RD_HIP(hipStreamSynchronize(s->st));
-    if (!strcmp(name, "polymask")) {      // a bit plane on the device: handed out as the int plane of poly.cpp:121
-      const size_t n = N * 4 <= max_bytes ? N : max_bytes / 4;
-      unsigned long long *tmp = (unsigned long long *)malloc((size_t)wpr * d->ih * 8 + 8);
-      if (!tmp) exitf(-1, "rd_detector_debug_plane: out of memory\n");
-      RD_HIP(hipMemcpy(tmp, tab[i].p, (size_t)wpr * d->ih * 8, hipMemcpyDeviceToHost));
-      for (size_t k = 0; k < n; k++) { const int y = (int)(k / d->iw), x = (int)(k % d->iw); ((int *)dst)[k] = (int)((tmp[(size_t)y * wpr + (x >> 6)] >> (x & 63)) & 1ull); }
-      free(tmp);
-      return n * 4;
-    }
+    if (!strcmp(name, "polymask")) return bit_plane_as_ints(d, tab[i].p, 0, dst, max_bytes);      // (poly.cpp:121)
     const size_t b = tab[i].bytes < max_bytes ? tab[i].bytes : max_bytes;
     RD_HIP(hipMemcpy(dst, tab[i].p, b, hipMemcpyDeviceToHost));
     return b;
