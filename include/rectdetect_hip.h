@@ -148,6 +148,75 @@ void *rd_postprocess_planes(const void *segs, const int32_t *boundary, const int
  * independent restatement of oclrect.c:1066-1083 */
 void rd_probe_pixels(float x0, float y0, float x1, float y1, int iw, int ih, int32_t *out);
 
+/* ---- rectified patches: what is INSIDE a quad, as an upright image of fixed size (rd_k_rectify.hip, rd_rectify.hip).
+ * The reference only draws outlines (rect.cpp, vidrect.cpp), so the arithmetic is defined here - exactly, so that an independent restatement (tests/rectify.py,
+ * numpy float64) reproduces every byte.
+ *
+ * A quad is four corners (x0,y0) (x1,y1) (x2,y2) (x3,y3) as doubles in the coordinates of rect_t::c2 (pixel centres at integers), in PATCH ORDER: they are where
+ * the corners (0,0) (1,0) (1,1) (0,1) of the unit square land.  A patch is pw x ph pixels of 3 bytes B, G, R, rows back to back; patch k of a job starts at
+ * out + k * pw * ph * 3.
+ *
+ * Coefficients - once per quad, on the host, IEEE double, exactly these operations, no contraction (rd_rectify_coefficients):
+ *   dx1 = x1-x2;  dx2 = x3-x2;  sx = ((x0-x1)+x2)-x3                      (dy1, dy2, sy the same from y)
+ *   den = dx1*dy2 - dx2*dy1
+ *   g = (sx*dy2 - dx2*sy)/den;   h = (dx1*sy - sx*dy1)/den
+ *   a = (x1-x0) + g*x1;  b = (x3-x0) + h*x3;  c = x0
+ *   d = (y1-y0) + g*y1;  e = (y3-y0) + h*y3;  f = y0                      coef[8] = { a, b, c, d, e, f, g, h }
+ * (the projective map of the unit square onto the quad: x = (a*s + b*t + c) / (g*s + h*t + 1), y = (d*s + e*t + f) / (g*s + h*t + 1)).
+ * A quad is VALID (status 1) when its eight values are finite and the four cross products, i = 0..3 with indices mod 4,
+ *   (x[i+1]-x[i]) * (y[i+2]-y[i+1]) - (y[i+1]-y[i]) * (x[i+2]-x[i+1])
+ * are all > 0 or all < 0 - strictly convex, either orientation - and the eight coefficients came out finite (they do unless the corners are
+ * so large that a product overflows).  An invalid quad has status 0, coefficients 0 and an all-zero patch.
+ *
+ * Patch pixel (i, j) - on the device, in double, uncontracted, in this order:
+ *   s = (i + 0.5) / pw;  t = (j + 0.5) / ph;  w = (g*s + h*t) + 1.0
+ *   x = ((a*s + b*t) + c) / w;   y = ((d*s + e*t) + f) / w
+ *   xi = floor(x * 256.0) clamped to [0, (iw-1)*256] and then taken as an integer      (yi the same with ih; the clamp is made in double: anything not above 0 - a NaN too - gives 0)
+ *   x0 = xi >> 8;  fx = xi & 255;  x1 = min(x0+1, iw-1)                                (y0, fy, y1 the same)
+ * and per channel, in int32, with p(x, y) the channel's byte of source pixel (x, y):
+ *   top = p(x0,y0)*(256-fx) + p(x1,y0)*fx;   bot = p(x0,y1)*(256-fx) + p(x1,y1)*fx
+ *   out = (top*(256-fy) + bot*fy + 32768) >> 16
+ * p is the (B, G, R) of the source pixel under the conversion contract above: for NV12 and I420 each of the four taps is converted first (BT.601 fixed point,
+ * 2x2 nearest chroma) and blended afterwards, so the patch from a frame in any format equals, bit for bit, the patch from the BGR frame the contract gives for it.
+ * Why double: two correctly rounded divisions per pixel cost nothing next to the detector ("Rectified patches"), and they are what lets numpy agree in every bit. */
+
+/* the quads of n rectangles as the detector returns them (rects: n records of 176 bytes, WITHOUT the header element: pass ret + 1) in patch order: for each,
+ * c2[0], c2[3], c2[2], c2[1] -> quads_out[8 * k ..].  The detector's corners run counter-clockwise on screen (y down); in this order s runs clockwise from
+ * c2[0] and patches are not mirrored.  Another start corner or a mirror image: permute the corners. */
+void rd_rect_quads(const void *rects, int n, double *quads_out);
+/* |c3[0]-c3[1]| / |c3[1]-c3[2]| of one rectangle, each length sqrt((dx*dx + dy*dy) + dz*dz): the aspect ratio of the estimated pose (the reference's own test
+ * of it: oclrect.c:641).  c3[i] is the pose of corner c2[i], and with rd_rect_quads' order a patch's rows (t) run along c2[0] -> c2[1] and its columns (s) along
+ * c2[0] -> c2[3], which is parallel to c3[1] - c3[2]: the value is HEIGHT / WIDTH of a patch made with rd_rect_quads (ph = pw * aspect keeps the pose's shape;
+ * 1 / aspect is width / height).  It is the ESTIMATED shape in space, not the ratio of the quad's edges on screen: under perspective, and for rectangles whose
+ * pose fit is poor, the two can differ widely. */
+double rd_rect_aspect(const void *rect);
+/* host only: coefficients and status of one quad as above - what a job uploads */
+void rd_rectify_coefficients(const double quad[8], double coef[8], int *status);
+
+/* A rectifier makes patches of pw x ph pixels, up to max_quads per job, up to njobs jobs in flight, on one stream of its own.  NULL on bad arguments
+ * (pw, ph, max_quads or njobs < 1, pw or ph > 16384, no such device). */
+typedef struct rd_rectifier rd_rectifier;
+rd_rectifier *rd_rectifier_create(int device, int pw, int ph, int max_quads, int njobs);
+void rd_rectifier_destroy(rd_rectifier *r);      /* waits for the jobs in flight */
+
+/* One job: n patches from one iw x ih frame in pixel format `format` (RD_PIX_*; planes / pitches as for rd_detector_enqueue_planes).
+ * on_device: where the frame lies - RD_FRAME_HOST (copied into the rectifier's own device buffer, which grows on demand, before the call returns),
+ *   RD_FRAME_DEVICE (read in place) or RD_FRAME_HOST_PINNED (the copy engine reads it in place; memory that is not pinned is fatal); device and pinned frames
+ *   stay valid and unchanged until the job's rd_rectifier_wait returned.
+ * out / out_kind: where the n patches go - RD_FRAME_DEVICE (the kernel writes there) or RD_FRAME_HOST_PINNED (the copy engine does); valid until the job's wait.
+ * Returns the job's sequence number, or -1 with nothing enqueued for an argument error: an unknown format, on_device or out_kind, iw or ih < 1 or > 65536, a NULL plane the
+ * format uses, a pitch smaller than its plane's row, NV12 / I420 with an odd iw or ih, n < 0, n > max_quads, n > 0 with quads or out NULL, `out` not memory of the
+ * kind out_kind names (pageable memory; only the kind of the memory at `out` is asked about - that it holds n * pw * ph * 3 bytes is the caller's contract).  A call with njobs jobs already in flight is fatal, as it is for the detector. */
+long rd_rectifier_enqueue(rd_rectifier *r, int format, const void *const planes[3], const int pitches[3], int iw, int ih, int on_device,
+                          const double *quads, int n, void *out, int out_kind);
+/* the oldest job: blocks until its patches are where it was told to put them, returns its n and writes the n status bytes (1 valid, 0 invalid: zero patch) to
+ * status_out when that is not NULL.  -1: no job in flight. */
+int rd_rectifier_wait(rd_rectifier *r, uint8_t *status_out);
+/* One job from the frame of the most recently polled slot of d (either kind of detector): its planes, pitches and format as they were handed over.  A host frame
+ * is rectified from the copy the detector uploaded - no second transfer - which lasts until the next enqueue on d: wait for the job first.  Device and pinned
+ * frames: the caller keeps the buffer until the job's wait.  Returns as rd_rectifier_enqueue; -1 also when nothing has been polled yet or d and r are on different devices. */
+long rd_detector_rectify_polled(rd_detector *d, rd_rectifier *r, const double *quads, int n, void *out, int out_kind);
+
 /* ---- synthetic frames (csrc/rd_synth.c) */
 int rd_synth_num_quads(int iw, int ih);
 void rd_synth_frame(uint8_t *bgr, int iw, int ih, int ws, uint64_t seed, int t, int noise);

@@ -10,6 +10,7 @@ Mirrors of the reference programs' call sequences:
   * :class:`RectDetector` - rect.cpp / vidrect.cpp (``oclrect_executeOnce`` / ``enqueueTask`` / ``pollTask``)
   * :class:`Detector` - the ``rd_detector`` extension (device-resident frames, several frames in flight)
   * :class:`PolylineDetector` - its polyline kind: poly.cpp / vidpoly.cpp per frame, several frames in flight
+  * :class:`Rectifier` - the ``rd_rectifier`` extension: what is inside detected quads as upright patches of fixed size
 """
 import ctypes
 import os
@@ -79,6 +80,15 @@ def _declare(L):
         "rd_post_helpers_configure": (None, [ci]),
         "rd_post_helpers_arm": (None, []),
         "rd_post_helpers": (ci, []),
+        # rectified patches (rd_rectify.hip)
+        "rd_rect_quads": (None, [vp, ci, vp]),
+        "rd_rect_aspect": (cd, [vp]),
+        "rd_rectify_coefficients": (None, [vp, vp, ctypes.POINTER(ci)]),
+        "rd_rectifier_create": (vp, [ci, ci, ci, ci, ci]),
+        "rd_rectifier_destroy": (None, [vp]),
+        "rd_rectifier_enqueue": (ctypes.c_long, [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ci, ci, vp, ci, vp, ci]),
+        "rd_rectifier_wait": (ci, [vp, vp]),
+        "rd_detector_rectify_polled": (ctypes.c_long, [vp, vp, vp, ci, vp, ci]),
         "rd_synth_frame": (None, [vp, ci, ci, ci, ctypes.c_uint64, ci, ci]),
         "rd_synth_num_quads": (ci, [ci, ci]),
         # reference API (oclhelper.h / raw cl*)
@@ -270,9 +280,10 @@ class RectDetector:
         L.dispose_oclimgutil(self.iu)
 
 
-def _enqueue_planes(h, fmt, planes, pitches, on_device, pinned):
-    """rd_detector_enqueue_planes for both detector kinds.  Host frames: numpy arrays (packed formats one HxWxC image; NV12 (Y, UV); I420 (Y, U, V)),
-    pitches from their strides (copied before the call returns).  on_device / pinned: plane ADDRESSES, with `pitches` required.  ValueError on an argument error."""
+def _plane_args(planes, pitches, on_device, pinned):
+    """the plane pointers, pitches and frame kind of the C entry points that take frames in any pixel format, plus the pitches as a list and the host arrays to
+    keep alive.  Host frames: numpy arrays (packed formats one HxWxC image; NV12 (Y, UV); I420 (Y, U, V)), pitches from their strides (copied before the call
+    returns).  on_device / pinned: plane ADDRESSES, with `pitches` required."""
     if not isinstance(planes, (list, tuple)):
         planes = (planes,)
     planes = list(planes)[:3]
@@ -292,9 +303,28 @@ def _enqueue_planes(h, fmt, planes, pitches, on_device, pinned):
         pitch = [a.strides[0] for a in arrs] if pitches is None else list(pitches)
     ptrs += [None] * (3 - len(ptrs))
     pitch += [0] * (3 - len(pitch))
-    r = lib().rd_detector_enqueue_planes(h, int(fmt), (ctypes.c_void_p * 3)(*ptrs), (ctypes.c_int * 3)(*pitch), 1 if on_device else (2 if pinned else 0))
+    return (ctypes.c_void_p * 3)(*ptrs), (ctypes.c_int * 3)(*pitch), 1 if on_device else (2 if pinned else 0), pitch, arrs if not (on_device or pinned) else None
+
+
+def _enqueue_planes(h, fmt, planes, pitches, on_device, pinned):
+    """rd_detector_enqueue_planes for both detector kinds (planes and pitches: _plane_args).  ValueError on an argument error."""
+    ptrs, pitch_c, kind, pitch, _ = _plane_args(planes, pitches, on_device, pinned)
+    r = lib().rd_detector_enqueue_planes(h, int(fmt), ptrs, pitch_c, kind)
     if r == -1:
         raise ValueError("rd_detector_enqueue_planes: invalid arguments (format %r, pitches %r)" % (fmt, pitch))
+    return r
+
+
+def _quads_arg(quads):
+    q = np.ascontiguousarray(quads, dtype=np.float64).reshape(-1, 8)
+    return q, len(q)
+
+
+def _rectify_polled(h, rectifier, quads, out, out_pinned):
+    q, n = _quads_arg(quads)
+    r = lib().rd_detector_rectify_polled(h, rectifier.h, q.ctypes.data, n, int(out) if out else None, 2 if out_pinned else 1)
+    if r == -1:
+        raise ValueError("rd_detector_rectify_polled: invalid arguments (nothing polled yet, %d quads, out %r)" % (n, out))
     return r
 
 
@@ -326,6 +356,12 @@ class Detector:
 
     def poll(self, tan_aov):
         return _take_rects(lib().rd_detector_poll(self.h, float(tan_aov)))
+
+    def rectify_polled(self, rectifier, quads, out, out_pinned=False):
+        """patches of `quads` (n x 8 or n x 4 x 2 doubles, patch order) from the frame of the most recently polled slot into `out` - the ADDRESS of device memory or,
+        with out_pinned, of pinned host memory - as one job of `rectifier` (take it with rectifier.wait()); a host frame is read from the detector's own copy,
+        which lasts until the next enqueue here.  ValueError on an argument error (nothing enqueued)."""
+        return _rectify_polled(self.h, rectifier, quads, out, out_pinned)
 
     def drain(self):
         lib().rd_detector_drain(self.h)
@@ -407,6 +443,10 @@ class PolylineDetector:
         _libc.free(ptr)
         return segs, out
 
+    def rectify_polled(self, rectifier, quads, out, out_pinned=False):
+        """as Detector.rectify_polled"""
+        return _rectify_polled(self.h, rectifier, quads, out, out_pinned)
+
     def drain(self):
         lib().rd_detector_drain(self.h)
 
@@ -423,6 +463,78 @@ class PolylineDetector:
     def close(self):
         if self.h:
             lib().rd_detector_destroy(self.h)
+            self.h = None
+
+
+def rect_quads(rects):
+    """the quads (n x 4 x 2 doubles) of a RECT_DTYPE array in patch order (rd_rect_quads: c2[0], c2[3], c2[2], c2[1] - s runs clockwise on screen from c2[0])"""
+    a = np.ascontiguousarray(rects, dtype=RECT_DTYPE).reshape(-1)
+    out = np.zeros((len(a), 4, 2), np.float64)
+    lib().rd_rect_quads(a.ctypes.data, len(a), out.ctypes.data)
+    return out
+
+
+def rect_aspect(rect):
+    """|c3[0]-c3[1]| / |c3[1]-c3[2]| of one rectangle (rd_rect_aspect): HEIGHT / WIDTH of its estimated pose in the orientation of rect_quads (ph = pw * aspect), for picking a patch shape"""
+    a = np.ascontiguousarray(rect, dtype=RECT_DTYPE).reshape(-1)[:1]
+    return float(lib().rd_rect_aspect(a.ctypes.data))
+
+
+def rectify_coefficients(quad):
+    """(coefficients a..h as 8 doubles, status) of one quad - what a job uploads (rd_rectify_coefficients; host only)"""
+    q = np.ascontiguousarray(quad, dtype=np.float64).reshape(8)
+    coef, status = np.zeros(8, np.float64), ctypes.c_int(0)
+    lib().rd_rectify_coefficients(q.ctypes.data, coef.ctypes.data, ctypes.byref(status))
+    return coef, status.value
+
+
+class Rectifier:
+    """The rd_rectifier extension: pw x ph BGR patches of up to max_quads quads per job, njobs jobs in flight (the contract: include/rectdetect_hip.h)."""
+
+    def __init__(self, pw, ph, max_quads=64, njobs=2, device=0):
+        L = lib()
+        if L.rd_device_count() <= 0:
+            raise RuntimeError("rectdetect_amd: no HIP device visible - there is no CPU fallback")
+        self.pw, self.ph, self.max_quads, self.njobs = pw, ph, max_quads, njobs
+        self.h = L.rd_rectifier_create(device, pw, ph, max_quads, njobs)
+        if not self.h:
+            raise ValueError("rd_rectifier_create: invalid arguments (%r)" % ((device, pw, ph, max_quads, njobs),))
+
+    def enqueue(self, fmt, planes, pitches, iw, ih, quads, out, on_device=False, pinned=False, out_pinned=False):
+        """one job: patches of `quads` (n x 8 or n x 4 x 2 doubles, patch order) from an iw x ih frame in format fmt (PIX_*) into `out`, the ADDRESS of device memory or,
+        with out_pinned, of pinned host memory.  planes / pitches as Detector.enqueue_planes: numpy planes (copied before the call returns; pitches may be None), or with
+        on_device / pinned their addresses, read in place until the job's wait().  Returns the job's sequence number; ValueError on an argument error (nothing enqueued)."""
+        ptrs, pitch_c, kind, pitch, _ = _plane_args(planes, pitches, on_device, pinned)
+        q, n = _quads_arg(quads)
+        r = lib().rd_rectifier_enqueue(self.h, int(fmt), ptrs, pitch_c, int(iw), int(ih), kind, q.ctypes.data, n, int(out) if out else None, 2 if out_pinned else 1)
+        if r == -1:
+            raise ValueError("rd_rectifier_enqueue: invalid arguments (format %r, pitches %r, %dx%d, %d quads, out %r)" % (fmt, pitch, iw, ih, n, out))
+        return r
+
+    def wait(self):
+        """blocks until the oldest job is done: its status array (uint8 per quad: 1 valid, 0 invalid - an all-zero patch)"""
+        status = np.zeros(self.max_quads, np.uint8)
+        n = lib().rd_rectifier_wait(self.h, status.ctypes.data)
+        if n < 0:
+            raise RuntimeError("rd_rectifier_wait: no job in flight")
+        return status[:n].copy()
+
+    def rectify(self, frame_bgr, quads):
+        """convenience: the (n, ph, pw, 3) patches of `quads` from a numpy BGR image, through pinned memory (one job, waited for)"""
+        a = np.asarray(frame_bgr, dtype=np.uint8)
+        q, n = _quads_arg(quads)
+        nbytes = max(n, 1) * self.ph * self.pw * 3
+        p = lib().rd_host_alloc(nbytes)
+        try:
+            self.enqueue(PIX_BGR, a, None, a.shape[1], a.shape[0], q, p, out_pinned=True)
+            self.wait()
+            return np.frombuffer((ctypes.c_uint8 * nbytes).from_address(p), np.uint8)[:n * self.ph * self.pw * 3].reshape(n, self.ph, self.pw, 3).copy()
+        finally:
+            lib().rd_host_free(p)
+
+    def close(self):
+        if self.h:
+            lib().rd_rectifier_destroy(self.h)
             self.h = None
 
 

@@ -1542,6 +1542,17 @@ void *rd_detector_poll(rd_detector *d, double tanAOV) {
   return r;
 }
 
+// Rectified patches (rd_rectify.hip) from the frame of the most recently polled slot: its format, planes and row strides as hand_over left them - device pointers
+// in every case (a host or pinned frame: the copy in the slot's own buffer, which the next frame handed to this slot overwrites).  The poll has waited for the frame's
+// last kernel, so the rectifier's stream may read at once.  Nothing of the slot is written.
+long rd_detector_rectify_polled(rd_detector *d, rd_rectifier *r, const double *quads, int n, void *out, int out_kind) {
+  if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_rectify_polled: bad handle\n");
+  if (d->last_polled_slot < 0 || rdrt::rectifier_device(r) != d->device) return -1;
+  const Slot *s = &d->slots[d->last_polled_slot];
+  const void *const planes[3] = { s->pl[0], s->pl[1], s->pl[2] };
+  return rd_rectifier_enqueue(r, s->fmt, planes, s->pitch, d->iw, d->ih, RD_FRAME_DEVICE, quads, n, out, out_kind);
+}
+
 // The reference hands the aperture over with the poll, i.e. after the frame (oclrect_pollTask); whatever runs ahead of the poll - the
 // worker threads' post-process, the rectangles on the device - uses the last one seen.  A caller that knows it beforehand says so here,
 // and the first frames of a stream are treated like all later ones.

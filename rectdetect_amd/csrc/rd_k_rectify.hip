@@ -1,0 +1,119 @@
+// rectdetect-mi355x: rectified patches for gfx950 - the inside of each quad of a job as an upright pw x ph BGR image (perspective warp, bilinear taps
+// in 8.8 fixed point).  The arithmetic is the contract in include/rectdetect_hip.h ("rectified patches"); nothing here may reorder or contract it
+// (-ffp-contract=off, see rd_device.h).
+//
+// Launch shape: one launch per job, quad = blockIdx.z.  A block is ONE wave of 8 x 8 threads and a thread makes 4 neighbouring pixels of a patch row, so
+// a wave covers 32 x 8 patch pixels: a near-square footprint in the source under any rotation of the quad (its taps share cache lines in both directions), and
+// its stores are 96 contiguous bytes per row.  The kernel uses no LDS and no barrier, so a larger block would buy nothing - while a job is small (ten 128 x 128
+// patches are 640 waves) and latency-bound on its gathers: one-wave blocks let the dispatcher spread it over all 256 CUs.  DESIGN.md, "Rectified patches".
+#include <stdio.h>
+#include <stdlib.h>
+#include "rd_device.h"
+#include "rd_kernels.h"
+#include "rectdetect_hip.h"
+
+namespace {
+
+struct RectifySrc { const uint8_t *pl[3]; int pitch[3]; int iw, ih; };
+
+// BT.601 limited range, OpenCV's fixed point (the conversion contract in rectdetect_hip.h; rd_k_front.hip has the same lines for the detector's front end)
+__device__ __forceinline__ void yuv_bgr(int Y, int U, int V, int &b, int &g, int &r) {
+  const int u = U - 128, v = V - 128, yy = max(Y - 16, 0) * 1220542;
+  r = min(max((yy + 1673527 * v + (1 << 19)) >> 20, 0), 255);
+  g = min(max((yy - 852492 * v - 409993 * u + (1 << 19)) >> 20, 0), 255);
+  b = min(max((yy + 2116026 * u + (1 << 19)) >> 20, 0), 255);
+}
+
+// (B, G, R) of source pixel (x, y), 0 <= x < iw, 0 <= y < ih: bytes from the caller's pitch
+template <int FMT> __device__ __forceinline__ void tap(const RectifySrc &S, int x, int y, int (&c)[3]) {
+  if (FMT <= RD_PIX_RGBA) {
+    const int bpp = (FMT == RD_PIX_BGR || FMT == RD_PIX_RGB) ? 3 : 4;
+    const uint8_t *q = S.pl[0] + (size_t)y * S.pitch[0] + (size_t)x * bpp;
+    const int v0 = q[0], v1 = q[1], v2 = q[2];
+    if (FMT == RD_PIX_BGR || FMT == RD_PIX_BGRA) { c[0] = v0; c[1] = v1; c[2] = v2; }
+    else { c[0] = v2; c[1] = v1; c[2] = v0; }
+  } else {
+    const int Y = S.pl[0][(size_t)y * S.pitch[0] + x];
+    int U, V;
+    if (FMT == RD_PIX_NV12) {
+      const uint8_t *q = S.pl[1] + (size_t)(y >> 1) * S.pitch[1] + (size_t)(x >> 1) * 2;
+      U = q[0]; V = q[1];
+    } else {
+      U = S.pl[1][(size_t)(y >> 1) * S.pitch[1] + (x >> 1)];
+      V = S.pl[2][(size_t)(y >> 1) * S.pitch[2] + (x >> 1)];
+    }
+    yuv_bgr(Y, U, V, c[0], c[1], c[2]);
+  }
+}
+
+// floor(v * 256) clamped to [0, hi] in double (anything not above 0, a NaN too, gives 0), then an integer
+__device__ __forceinline__ int fix8(double v, double hi) {
+  double q = floor(v * 256.0);
+  q = q > 0.0 ? q : 0.0;
+  q = q < hi ? q : hi;
+  return (int)q;
+}
+
+template <int FMT> __device__ __forceinline__ void patch_pixel(const RectifySrc &S, const rdk::RectifyQuad &Q, int i, int j, int pw, int ph, uint8_t (&o)[3]) {
+  const double s = ((double)i + 0.5) / (double)pw, t = ((double)j + 0.5) / (double)ph;
+  const double w = (Q.c[6] * s + Q.c[7] * t) + 1.0;
+  const double x = ((Q.c[0] * s + Q.c[1] * t) + Q.c[2]) / w;
+  const double y = ((Q.c[3] * s + Q.c[4] * t) + Q.c[5]) / w;
+  const int xi = fix8(x, (double)(S.iw - 1) * 256.0), yi = fix8(y, (double)(S.ih - 1) * 256.0);
+  const int x0 = xi >> 8, fx = xi & 255, x1 = min(x0 + 1, S.iw - 1);
+  const int y0 = yi >> 8, fy = yi & 255, y1 = min(y0 + 1, S.ih - 1);
+  int p00[3], p10[3], p01[3], p11[3];
+  tap<FMT>(S, x0, y0, p00); tap<FMT>(S, x1, y0, p10); tap<FMT>(S, x0, y1, p01); tap<FMT>(S, x1, y1, p11);
+#pragma unroll
+  for (int c = 0; c < 3; c++) {
+    const int top = p00[c] * (256 - fx) + p10[c] * fx;
+    const int bot = p01[c] * (256 - fx) + p11[c] * fx;
+    o[c] = (uint8_t)((top * (256 - fy) + bot * fy + 32768) >> 16);
+  }
+}
+
+template <int FMT> __global__ __launch_bounds__(64) void k_rectify(uint8_t *out, RectifySrc S, const rdk::RectifyQuad *quads, int pw, int ph) {
+  const int i0 = (blockIdx.x * 8 + threadIdx.x) * 4, j = blockIdx.y * 8 + threadIdx.y;
+  if (i0 >= pw || j >= ph) return;
+  const rdk::RectifyQuad Q = quads[blockIdx.z];
+  uint8_t *dst = out + ((size_t)blockIdx.z * ph + j) * ((size_t)pw * 3) + (size_t)i0 * 3;
+  const int m = min(4, pw - i0);      // pixels of this thread (fewer than 4: the row's tail)
+  uint8_t o[4][3];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    o[k][0] = o[k][1] = o[k][2] = 0;      // (an invalid quad: zeros from the same launch)
+    if (Q.status && k < m) patch_pixel<FMT>(S, Q, i0 + k, j, pw, ph, o[k]);
+  }
+  if (m == 4 && ((uintptr_t)dst & 3) == 0) {      // 12 bytes as three aligned dwords (always, when pw is a multiple of 4 and `out` is dword-aligned)
+    uint32_t *d4 = (uint32_t *)dst;
+    d4[0] = o[0][0] | (o[0][1] << 8) | (o[0][2] << 16) | ((uint32_t)o[1][0] << 24);
+    d4[1] = o[1][1] | (o[1][2] << 8) | (o[2][0] << 16) | ((uint32_t)o[2][1] << 24);
+    d4[2] = o[2][2] | (o[3][0] << 8) | (o[3][1] << 16) | ((uint32_t)o[3][2] << 24);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; k++) if (k < m) { dst[3 * k] = o[k][0]; dst[3 * k + 1] = o[k][1]; dst[3 * k + 2] = o[k][2]; }
+  }
+}
+
+}  // namespace
+
+namespace rdk {
+
+void rectify(hipStream_t s, uint8_t *out, int fmt, const uint8_t *const planes[3], const int pitch[3], int iw, int ih, const RectifyQuad *quads, int n, int pw, int ph) {
+  if (n <= 0) return;
+  RectifySrc S;
+  for (int k = 0; k < 3; k++) { S.pl[k] = planes[k]; S.pitch[k] = pitch[k]; }
+  S.iw = iw; S.ih = ih;
+  const dim3 block(8, 8), grid((pw + 31) / 32, (ph + 7) / 8, n);
+  switch (fmt) {
+    case RD_PIX_BGR: hipLaunchKernelGGL(k_rectify<RD_PIX_BGR>, grid, block, 0, s, out, S, quads, pw, ph); break;
+    case RD_PIX_RGB: hipLaunchKernelGGL(k_rectify<RD_PIX_RGB>, grid, block, 0, s, out, S, quads, pw, ph); break;
+    case RD_PIX_BGRA: hipLaunchKernelGGL(k_rectify<RD_PIX_BGRA>, grid, block, 0, s, out, S, quads, pw, ph); break;
+    case RD_PIX_RGBA: hipLaunchKernelGGL(k_rectify<RD_PIX_RGBA>, grid, block, 0, s, out, S, quads, pw, ph); break;
+    case RD_PIX_NV12: hipLaunchKernelGGL(k_rectify<RD_PIX_NV12>, grid, block, 0, s, out, S, quads, pw, ph); break;
+    case RD_PIX_I420: hipLaunchKernelGGL(k_rectify<RD_PIX_I420>, grid, block, 0, s, out, S, quads, pw, ph); break;
+    default: fprintf(stderr, "rdk::rectify: unknown pixel format %d\n", fmt); abort();      // (the entry points refuse it first)
+  }
+}
+
+}  // namespace rdk

@@ -141,4 +141,10 @@ void polyline_handoff(hipStream_t s, const PolyFrame *frames, int nb, int record
 // materialises the dense id planes frames[z].ids from the compact state
 void polyline_ids(hipStream_t s, const PolyFrame *frames, int nb, int n);
 
+// ---- rd_k_rectify.hip: rectified patches (the contract: rectdetect_hip.h, "rectified patches")
+// what a job uploads per quad: the coefficients a, b, c, d, e, f, g, h of rd_rectify_coefficients and the quad's status (0: an all-zero patch)
+struct RectifyQuad { double c[8]; int status; int pad; };
+// n patches of pw x ph BGR pixels, patch k at out + k * pw * ph * 3, from one iw x ih frame in format fmt (RD_PIX_*; planes / pitch as the caller's), one launch (quad = blockIdx.z)
+void rectify(hipStream_t s, uint8_t *out, int fmt, const uint8_t *const planes[3], const int pitch[3], int iw, int ih, const RectifyQuad *quads, int n, int pw, int ph);
+
 }  // namespace rdk
