@@ -62,44 +62,59 @@ __global__ __launch_bounds__(256) void k_junction_bits(u64 *__restrict__ bits, c
 //   towards larger coordinates when
 //       c > n-1, or (centre on an edge ? !E[c] : !E[c] & E[c+1]).
 // Cells outside the frame are staged as zero, which makes the reference's `c < n-1` and `has side cell` tests redundant.
-// A pixel then reads its five relevant stop bits per direction and counts the leading clear ones.
+// The COUNTS are word operations as well: one lane per tile row (wave 0 along x, wave 1 along y) forms the five "still running after k cells" words
+// c1 >= c2 >= ... >= c5 of each direction for the row's 64 pixels; the words are monotone, so the count's three bits are (c1 & ~c2) | (c3 & ~c4) | c5, c2 & ~c4 and c4.
+// The twelve bit planes of a row (bit k of the ext word, column by column) go to LDS in 16-column pieces, plane k in the low and plane k + 6 in the high half
+// of a word; a pixel reads the six words of its piece, turns each so that its two bits land on bits k and 16 + k, and has its ext word in 17 vector instructions
+// (before: every pixel rebuilt three shifted 64-bit windows and gathered ten stop bits one by one - about 100).
 #ifndef BE_ROWS
-#define BE_ROWS 32
+#define BE_ROWS 32            // (tests/test_gpu_small_dense.py places its fixtures and its tile-corner condition by this height: keep BE_ROWS there equal)
 #endif
 #define BE_NR (BE_ROWS + 11)          // rows y0-5 .. y0+BE_ROWS+5
+static_assert(BE_ROWS % 4 == 0 && BE_ROWS <= 64, "rows by four waves; one lane per tile row");
+// columns x0 + d .. x0 + d + 63 of a row held as A (columns x0-8 ..) and B (columns x0+56 ..), -4 <= d <= 4
+__device__ __forceinline__ unsigned long long be_cols(unsigned long long A, unsigned long long B, int d) { return (A >> (8 + d)) | (B << (56 - d)); }
+// counts 0..5 of 64 pixels as three bit planes: stop[k] = the k-th cell of the scan stops it
+__device__ __forceinline__ void be_count(const unsigned long long (&stop)[5], unsigned long long &b0, unsigned long long &b1, unsigned long long &b2, unsigned long long &any) {
+  const unsigned long long c1 = ~stop[0], c2 = c1 & ~stop[1], c3 = c2 & ~stop[2], c4 = c3 & ~stop[3], c5 = c4 & ~stop[4];
+  b0 = (c1 & ~c2) | (c3 & ~c4) | c5; b1 = c2 & ~c4; b2 = c4; any = c1;
+}
+// a word of the planes' LDS image: written as halves by two waves, read whole
+union be_word { uint32_t w; uint16_t h[2]; };
 __global__ __launch_bounds__(256) void k_blblur_extents(uint16_t *__restrict__ ext, const int8_t *__restrict__ edge, int iw, int ih, size_t zs) {
   RD_ZSHIFT(zs, ext, edge);
   typedef unsigned long long u64;
-  __shared__ u64 EA[BE_NR + 1], EB[BE_NR + 1];   // mask != 0 for columns x0-8 .. x0+55 (A) and x0+56 .. x0+71 (B)
-  __shared__ u64 HLa[BE_NR], HLb[BE_NR], HRa[BE_NR], HRb[BE_NR];   // along x: stop bits towards smaller / larger x (centre not on an edge)
-  __shared__ u64 VL[BE_NR], VR[BE_NR], VE[BE_NR];                  // along y, tile columns only (bit = column - x0)
+  __shared__ u64 EA[BE_NR], EB[BE_NR];                 // mask != 0 for columns x0-8 .. x0+55 (A) and x0+56 .. x0+71 (B)
+  __shared__ __attribute__((aligned(16))) be_word PW[BE_ROWS][4][6];               // [tile row][16 columns][k]: h[0] plane k (along x), h[1] plane k + 6 (along y)
   const int x0 = blockIdx.x * 64, y0 = blockIdx.y * BE_ROWS;
-  const int tx = threadIdx.x, ty = rd_ty(), tid = ty * 64 + tx;
+  const int tx = threadIdx.x, ty = rd_ty();
   {
+    // rows by waves (a scalar row base, a scalar row test), columns by lanes (the column tests made once): two clamped loads and two compares per row and lane
     constexpr int IT = (BE_NR + 3) / 4;
     int8_t va[IT], vb[IT];
-    bool oka[IT], okb[IT];
     const int xa = x0 - 8 + tx, xb = x0 + 56 + tx;
+    const bool cola = xa >= 0 && xa < iw, colb = tx < 16 && xb < iw;
+    const unsigned ca = cola ? (unsigned)xa : 0u, cb = colb ? (unsigned)xb : 0u;
 #pragma unroll
     for (int i = 0; i < IT; i++) {          // all loads first (see stage_cells)
       const int yy = y0 - 5 + ty + 4 * i;
       const bool rowin = ty + 4 * i < BE_NR && yy >= 0 && yy < ih;
-      oka[i] = rowin && xa >= 0 && xa < iw;
-      okb[i] = rowin && tx < 16 && xb < iw;
-      va[i] = edge[oka[i] ? yy * iw + xa : 0];
-      vb[i] = edge[okb[i] ? yy * iw + xb : 0];
+      const unsigned rb = rowin ? (unsigned)(yy * iw) : 0u;
+      va[i] = atu(edge, rb + ca);
+      vb[i] = atu(edge, rb + cb);
     }
 #pragma unroll
     for (int i = 0; i < IT; i++) {
-      const int r = ty + 4 * i;
-      const u64 ba = __ballot(oka[i] && va[i] != 0), bb = __ballot(okb[i] && vb[i] != 0);
+      const int r = ty + 4 * i, yy = y0 - 5 + r;
+      const bool rowin = r < BE_NR && yy >= 0 && yy < ih;
+      const u64 ba = __builtin_amdgcn_ballot_w64(rowin && cola && va[i] != 0), bb = __builtin_amdgcn_ballot_w64(rowin && colb && vb[i] != 0);      // (the compare's own lane mask)
       if (tx == 0 && r < BE_NR) { EA[r] = ba; EB[r] = bb; }
     }
   }
-  if (tid == 0) { EA[BE_NR] = 0; EB[BE_NR] = 0; }
   __syncthreads();
-  if (tid < BE_NR) {
-    const int r = tid, yy = y0 - 5 + r;
+  // lane = tile row tx (staged row tx + 5, frame row yy): every staged row it reads, tx .. tx + 10, exists
+  if (ty == 0 && tx < BE_ROWS) {             // along x
+    const int r = tx + 5;
     const u64 A = EA[r], B = EB[r], SA = EA[r + 1], SB = EB[r + 1];
     const u64 PA = A << 1, PB = (B << 1) | (A >> 63);            // E[c-1]
     const u64 NA = (A >> 1) | (B << 63), NB = B >> 1;            // E[c+1]
@@ -109,47 +124,65 @@ __global__ __launch_bounds__(256) void k_blblur_extents(uint16_t *__restrict__ e
     const int fa = iw - x0 + 8, fb = iw - x0 - 56;               // first bit index beyond the frame
     if (fa < 64) ra |= ~0ull << fa;
     if (fb <= 0) rb = ~0ull; else if (fb < 64) rb |= ~0ull << fb;
-    HLa[r] = la; HLb[r] = lb; HRa[r] = ra; HRb[r] = rb;
-    const u64 Et = (A >> 8) | (B << 56), En = (A >> 9) | (B << 55);                 // columns x0.., x0+1..
-    const u64 Ep = r > 0 ? (EA[r - 1] >> 8) | (EB[r - 1] << 56) : 0ull;             // row above
-    const u64 Es = (SA >> 8) | (SB << 56);                                           // row below
-    u64 vl = (Et & ~Ep) | (~Et & Ep & En);
-    if (yy == 0) vl = 0;
-    if (yy < 0) vl = ~0ull;
-    u64 vr = ~Et & Es;
-    if (yy >= ih) vr = ~0ull;
-    VL[r] = vl; VR[r] = vr; VE[r] = Et;
+    const u64 Et = be_cols(A, B, 0);                              // centre on an edge: the scan towards larger x runs while E is set
+    u64 sl[5], sr[5];
+#pragma unroll
+    for (int d = 0; d < 5; d++) {            // column x - d towards smaller, x + d towards larger x
+      sl[d] = be_cols(la, lb, -d);
+      sr[d] = (Et & ~be_cols(A, B, d)) | (~Et & be_cols(ra, rb, d));
+    }
+    u64 p[6], anyl, anyr;
+    be_count(sl, p[0], p[1], p[2], anyl);
+    be_count(sr, p[3], p[4], p[5], anyr);
+    p[3] |= ~anyl & ~anyr;                   // no run at all: the centre alone, written as 0 samples towards smaller and 1 towards larger x
+#pragma unroll
+    for (int k = 0; k < 6; k++)
+#pragma unroll
+      for (int q = 0; q < 4; q++) PW[tx][q][k].h[0] = (uint16_t)(p[k] >> (16 * q));
+  }
+  if (ty == 1 && tx < BE_ROWS) {             // along y: tile columns only (bit = column - x0)
+    const int r = tx + 5, yy = y0 + tx;
+    u64 E[11];                               // rows r-5 .. r+5
+#pragma unroll
+    for (int k = 0; k < 11; k++) E[k] = be_cols(EA[r - 5 + k], EB[r - 5 + k], 0);
+    u64 sl[5], sr[5];
+#pragma unroll
+    for (int d = 0; d < 5; d++) {            // row yy - d towards smaller, yy + d towards larger y
+      const u64 Ec = E[5 - d], Ep = E[4 - d], En = be_cols(EA[r - d], EB[r - d], 1);
+      u64 vl = (Ec & ~Ep) | (~Ec & Ep & En);
+      if (yy - d == 0) vl = 0;               // row 0 never stops the scan itself; rows < 0 do
+      if (yy - d < 0) vl = ~0ull;
+      sl[d] = vl;
+      u64 vr = (E[5] & ~E[5 + d]) | (~E[5] & ~E[5 + d] & E[6 + d]);      // centre on an edge: runs while E is set
+      if (yy + d >= ih) vr = ~0ull;
+      sr[d] = vr;
+    }
+    u64 p[6], anyl, anyr;
+    be_count(sl, p[0], p[1], p[2], anyl);
+    be_count(sr, p[3], p[4], p[5], anyr);
+    p[3] |= ~anyl & ~anyr;
+#pragma unroll
+    for (int k = 0; k < 6; k++)
+#pragma unroll
+      for (int q = 0; q < 4; q++) PW[tx][q][k].h[1] = (uint16_t)(p[k] >> (16 * q));
   }
   __syncthreads();
   const int x = x0 + tx;
   if (x >= iw) return;
-  for (int rr = ty; rr < BE_ROWS; rr += 4) {
-    const int y = y0 + rr;
-    if (y >= ih) break;
-    const int r = rr + 5;
-    // 64-bit windows starting at column x - 8: the pixel is bit 8
-    const int sh = tx, rs = (64 - tx) & 63;
-    const u64 keep = tx == 0 ? 0ull : ~0ull;
-    const u64 we = (EA[r] >> sh) | ((EB[r] << rs) & keep);
-    const u64 wl = (HLa[r] >> sh) | ((HLb[r] << rs) & keep);
-    const u64 wr1 = (HRa[r] >> sh) | ((HRb[r] << rs) & keep);
-    const bool oe = (we >> 8) & 1;
-    const u64 wr = oe ? ~we : wr1;
-    const unsigned tl = (unsigned)(wl >> 4) & 31u;                 // bit 4: the pixel's own column ... bit 0: four columns before
-    const int nl = __clz((int)tl) - 27;
-    const int nr = __ffs((int)(((unsigned)(wr >> 8) & 31u) | 32u)) - 1;
-    unsigned tv = 0, uv = 32u;
+  // bits k and 16 + k of word k of the pixel's piece, turned into place: bit (tx & 15) -> bit k, bit 16 + (tx & 15) -> bit 16 + k
+  const int piece = tx >> 4, turn = tx & 15;
+  uint32_t w[BE_ROWS / 4][6];
 #pragma unroll
-    for (int d = 0; d < 5; d++) {
-      tv |= (unsigned)((VL[r - d] >> tx) & 1ull) << (4 - d);
-      const u64 w = oe ? ~VE[r + d] : VR[r + d];
-      uv |= (unsigned)((w >> tx) & 1ull) << d;
-    }
-    const int nlv = __clz((int)tv) - 27, nrv = __ffs((int)uv) - 1;
-    // (a pixel without any run keeps its value: written as "the centre alone" - 0 samples towards smaller, 1 towards larger coordinates - which the passes'
-    //  sum / count reproduces exactly, so that they need no special case)
-    const int nrh = (nl | nr) ? nr : 1, nrvv = (nlv | nrv) ? nrv : 1;
-    ext[y * iw + x] = (uint16_t)((unsigned)(nl | (nrh << 3)) | ((unsigned)(nlv | (nrvv << 3)) << 6));
+  for (int i = 0; i < BE_ROWS / 4; i++)
+#pragma unroll
+    for (int k = 0; k < 6; k++) w[i][k] = PW[ty + 4 * i][piece][k].w;
+#pragma unroll
+  for (int i = 0; i < BE_ROWS / 4; i++) {
+    const int y = y0 + ty + 4 * i;
+    uint32_t t = 0;
+#pragma unroll
+    for (int k = 0; k < 6; k++) t |= __builtin_rotateright32(w[i][k], (unsigned)(turn - k) & 31u) & (0x10001u << k);
+    if (y < ih) atu(ext, (unsigned)(y * iw + x)) = (uint16_t)((t & 63u) | ((t >> 16) << 6));
   }
 }
 
@@ -360,100 +393,116 @@ __global__ void k_quant24_lut() {
 }
 
 // rc:218-244: pixels with a non-zero NMS response take the colour of the Lab-nearest 3x3 neighbour without one.
-// One block per 64 x DS_ROWS tile: the tile and a 1-cell halo of both inputs are staged in LDS (colours already quantised,
-// the response reduced to flags) with all loads of a thread in flight together; the affected pixels - a few per cent, on thin
-// lines that cross a third of all waves - are collected in an LDS list and worked off with all lanes busy, from LDS only.
+// One block per 64 x DS_ROWS tile, staged like the other tile kernels: wave w takes rows w, w + 4, ... of the tile and its 1-cell halo, lanes are columns 0..63
+// (a scalar row base plus the lane's offset; the row test is scalar, the column test made once per lane), the two halo columns are one cell per thread, and every
+// load of a thread is requested before the first is used.  The wave that staged a pixel also writes it: the 96 % without a response go from registers to the
+// output through the quantisation tables and to LDS only as somebody's neighbour; "has a response" is a compare whose lane mask serves as the store's
+// predicate, the candidate flag and the list's ballot alike.  The affected pixels - a few per cent, on thin lines that cross a third of all waves - are collected
+// in LDS (a list per wave: no atomic counter) and worked off with all lanes busy, from LDS only.
+// (Before: 66-wide rows of cells dealt to the threads in turn - a division and a modulo by 66, four bounds tests and a clamped address per cell, three flag
+//  bits by compares and selects, every output pixel read back from LDS - 193 vector instructions per 64 pixels; 64 x 16 tiles, so that the 10 KB of tables
+//  were copied once per 1024 pixels.)
 #ifndef DS_ROWS
-#define DS_ROWS 16
+#define DS_ROWS 30            // (1080 = 36 x 30; DS_ROWS + 2 rows by four waves; tests/test_gpu_small_dense.py places its fixtures and its tile-corner condition by this height: keep DS_ROWS there equal)
 #endif
 #define DS_P 66
+#define DS_R (DS_ROWS + 2)    // staged rows
+#define DS_RW (DS_R / 4)      // ... of a wave
+static_assert(DS_R % 4 == 0 && 2 * DS_R <= 256 && DS_R <= 64, "rows by four waves; one halo cell per thread; a list entry is row << 6 | column in 16 bits");
 // QN > 0: the input is quantised to QN levels per field on the fly (rc:207-216 fused in: no separate pass over the plane)
 template <int QN>
 __global__ __launch_bounds__(256) void k_despeckle(uint32_t *__restrict__ out, const uint32_t *__restrict__ in, const float *__restrict__ edge, int iw, int ih, size_t zs, int gdim) {
   const rd_tile rd_b = rd_block_tile(gdim);
   if (rd_b.x < 0) return;
   RD_ZSHIFTZ(rd_b.z, zs, out, in, edge);
-  constexpr int NC = (DS_ROWS + 2) * DS_P, IT = (NC + 255) / 256;
-  __shared__ uint32_t tq[IT * 256];      // (padded to whole rounds of the block: the staging below is straight-line code - no `cell exists` branch for the compiler to sink a load into)
-  __shared__ uint8_t tf[IT * 256];        // bit 0: replaced as a centre (!(e < 1e-6)), bit 1: skipped as a neighbour (e >= 1e-6), bit 2: outside the frame
-  __shared__ int list[64 * DS_ROWS];
-  __shared__ int nlist;
+  __shared__ uint32_t tq[DS_R * DS_P];      // quantised colours: row s = frame row y0 - 1 + s, cell c = column x0 - 1 + c
+  __shared__ uint8_t tf[DS_R * DS_P];       // non-zero: no candidate (outside the frame, or e >= 1e-6: has a response itself)
+  __shared__ uint16_t list[4][64 * DS_RW];  // a wave's pixels to replace (!(e < 1e-6)): row << 6 | tile column
+  __shared__ int nlist[4];
   __shared__ uint32_t qlut[QN == 24 ? 2560 : 1];      // g_quant24, two entries per word
-  const int tx = threadIdx.x, tid = rd_ty() * 64 + tx;
+  const int tx = threadIdx.x, wv = rd_ty(), tid = wv * 64 + tx;
   const int x0 = rd_b.x * 64, y0 = rd_b.y * DS_ROWS;
-  if (tid == 0) nlist = 0;
+  const bool colin = x0 + tx < iw;
+  const unsigned cx = (unsigned)(x0 + (colin ? tx : 0));
+  uint32_t v[DS_RW + 1];
+  float e[DS_RW + 1];
+#pragma unroll
+  for (int k = 0; k < DS_RW; k++) {      // (clamped rows and columns: every load is unconditional, the value is dropped afterwards)
+    const int y = y0 - 1 + wv + 4 * k, yc = y < 0 ? 0 : (y >= ih ? ih - 1 : y);
+    const unsigned a = (unsigned)(yc * iw) + cx;
+    v[k] = atu(in, a);
+    e[k] = atu(edge, a);
+  }
+  const int hs = tid >> 1, hc = (tid & 1) * (DS_P - 1);      // the halo: row tid / 2, cell 0 or 65
+  const int hx = x0 - 1 + hc, hy = y0 - 1 + hs;
+  const bool hok = hs < DS_R && hx >= 0 && hx < iw && hy >= 0 && hy < ih;
   {
-    // the tile's cells and the quantisation tables are requested together (the cells were loaded a pair at a time before, each pair behind the previous
-    // one's stores - the compiler had sunk every load into the branch that used it: five trips to memory one after the other, after the tables' one)
-    uint32_t v[IT];
-    float e[IT];
-    bool ok[IT];
+    const unsigned a = hok ? (unsigned)(hy * iw + hx) : 0u;
+    v[DS_RW] = atu(in, a);
+    e[DS_RW] = atu(edge, a);
+  }
+  if (QN == 24) {      // the tables are requested together with the cells
+    uint32_t w[10];
 #pragma unroll
-    for (int i = 0; i < IT; i++) {
-      const int t = tid + 256 * i;
-      const int xx = x0 - 1 + t % DS_P, yy = y0 - 1 + t / DS_P;
-      ok[i] = t < NC && xx >= 0 && xx < iw && yy >= 0 && yy < ih;
-      const int a = ok[i] ? yy * iw + xx : 0;
-      v[i] = in[a];
-      e[i] = edge[a];
-    }
+    for (int i = 0; i < 10; i++) w[i] = atu((const uint32_t *)g_quant24, (unsigned)(tid + 256 * i));
+#pragma unroll
+    for (int i = 0; i < 10; i++) qlut[tid + 256 * i] = w[i];
+    __syncthreads();
+  }
+  auto quant = [&](uint32_t c) -> uint32_t {
     if (QN == 24) {
-      uint32_t w[10];
-#pragma unroll
-      for (int i = 0; i < 10; i++) w[i] = ((const uint32_t *)g_quant24)[tid + 256 * i];
-#pragma unroll
-      for (int i = 0; i < 10; i++) qlut[tid + 256 * i] = w[i];
-      __syncthreads();
+      const uint16_t *q16 = (const uint16_t *)qlut;
+      return (uint32_t)q16[c & 4095u] | ((uint32_t)q16[4096 + ((c >> 12) & 1023u)] << 12) | ((uint32_t)q16[4096 + (c >> 22)] << 22);
     }
+    return QN > 0 ? quantize_plab(c, QN, QN, QN) : c;
+  };
 #pragma unroll
-    for (int i = 0; i < IT; i++) {
-      const int t = tid + 256 * i;
-      uint32_t qv = v[i];
-      if (QN == 24) {
-        const uint16_t *q16 = (const uint16_t *)qlut;
-        qv = (uint32_t)q16[qv & 4095u] | ((uint32_t)q16[4096 + ((qv >> 12) & 1023u)] << 12) | ((uint32_t)q16[4096 + (qv >> 22)] << 22);
-      } else if (QN > 0) qv = quantize_plab(qv, QN, QN, QN);
-      tq[t] = ok[i] ? qv : 0u;
-      tf[t] = ok[i] ? (uint8_t)((!(e[i] < 1e-6f) ? 1 : 0) | (e[i] >= 1e-6f ? 2 : 0)) : (uint8_t)4;
-    }
-  }
-  __syncthreads();
-  for (int r = rd_ty(); r < DS_ROWS; r += 4) {
-    const int x = x0 + tx, y = y0 + r;
-    const int i = (r + 1) * DS_P + tx + 1;
-    bool hot = false;
-    if (x < iw && y < ih) {
-      hot = tf[i] & 1;
-      if (!hot) out[y * iw + x] = tq[i];
-    }
-    const unsigned long long m = __ballot(hot);
+  for (int k = 0; k <= DS_RW; k++) v[k] = quant(v[k]);      // (all lookups of a thread together)
+  int nhot = 0;
+#pragma unroll
+  for (int k = 0; k < DS_RW; k++) {
+    const int s = wv + 4 * k, y = y0 - 1 + s;
+    const bool ok = colin && y >= 0 && y < ih, mine = ok && s >= 1 && s <= DS_ROWS;
+    const uint32_t qv = v[k];
+    const bool hot = !(e[k] < 1e-6f), skip = e[k] >= 1e-6f;      // (NaN: replaced as a centre, not skipped as a neighbour)
+    const int i = s * DS_P + tx + 1;
+    tq[i] = qv;
+    tf[i] = ok && !skip ? 0 : 1;
+    if (mine && !hot) atu(out, (unsigned)(y * iw + x0 + tx)) = qv;
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(mine && hot);
     if (m) {
-      const int leader = __ffsll((long long)m) - 1;
-      int o = 0;
-      if (tx == leader) o = atomicAdd(&nlist, __popcll(m));
-      o = __shfl(o, leader);
-      if (hot) list[o + __popcll(m & ((1ull << tx) - 1))] = i;
+      if (mine && hot) list[wv][nhot + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u))] = (uint16_t)((s << 6) | tx);
+      nhot += __popcll(m);
     }
   }
+  if (hs < DS_R) {
+    const int i = hs * DS_P + hc;
+    tq[i] = v[DS_RW];
+    tf[i] = hok && !(e[DS_RW] >= 1e-6f) ? 0 : 1;
+  }
+  if (tx == 0) nlist[wv] = nhot;
   __syncthreads();
-  const int n = nlist;
+  const int n1 = nlist[0], n2 = n1 + nlist[1], n3 = n2 + nlist[2], n = n3 + nlist[3];
   for (int j = tid; j < n; j += 256) {
-    const int i = list[j];
+    const int w = (j >= n1) + (j >= n2) + (j >= n3);
+    const int en = list[w][j - (w == 0 ? 0 : (w == 1 ? n1 : (w == 2 ? n2 : n3)))];
+    const int s = en >> 6, c = en & 63;
+    const int i = s * DS_P + c + 1;
     uint32_t r = tq[i];
     float dist = 1e+10f, l0, a0, b0;
     unpack_lab(r, l0, a0, b0);
 #pragma unroll
     for (int k = 0; k < 9; k++) {
       const int q = i + (k / 3 - 1) * DS_P + k % 3 - 1;
-      if (tf[q] & 6) continue;          // outside the frame, or has a response itself
+      if (tf[q]) continue;              // outside the frame, or has a response itself
       float l1, a1, b1;
-      const uint32_t v = tq[q];
-      unpack_lab(v, l1, a1, b1);
+      const uint32_t v1 = tq[q];
+      unpack_lab(v1, l1, a1, b1);
       const float dx = l1 - l0, dy = a1 - a0, dz = b1 - b0;
       const float d = sqrtf(dx * dx + dy * dy + dz * dz);
-      if (d < dist) { r = v; dist = d; }
+      if (d < dist) { r = v1; dist = d; }
     }
-    out[(y0 + i / DS_P - 1) * iw + x0 + i % DS_P - 1] = r;
+    atu(out, (unsigned)((y0 + s - 1) * iw + x0 + c)) = r;
   }
 }
 
