@@ -2,7 +2,10 @@
  * in flight: a real video without OpenCV (ffmpeg -i in.mp4 -pix_fmt yuv420p -f yuv4mpegpipe out.y4m; "-" reads standard input).  8-bit samples only: C420,
  * C420jpeg, C420paldv, C420mpeg2 or no C tag; C420p10 / C420p12 and the other chroma layouts are refused.
  *
- *   rdy4m <file.y4m | -> [device number] [angle of view in degrees] [frames in flight]
+ *   rdy4m <file.y4m | -> [device number] [angle of view in degrees] [frames in flight] [half]
+ *
+ * half: detect at half the stream's size (rd_detector_enqueue_scaled, scale 2: the detector is W/2 x H/2 and averages 2x2 as it reads the full-size planes) -
+ * a 3840x2160 stream at the rate of a 1920x1080 one.
  *
  * Prints the number of rectangles per frame, in the shape of rdvid, and the frame rate once per second. */
 #include <math.h>
@@ -42,18 +45,20 @@ static int read_frame(FILE *f, uint8_t *buf, size_t bytes) {
 }
 
 int main(int argc, char **argv) {
-  if (argc < 2) { fprintf(stderr, "Usage : %s <file.y4m | -> [device] [aov] [frames in flight]\n", argv[0]); return 1; }
+  if (argc < 2) { fprintf(stderr, "Usage : %s <file.y4m | -> [device] [aov] [frames in flight] [half]\n", argv[0]); return 1; }
   FILE *f = strcmp(argv[1], "-") == 0 ? stdin : fopen(argv[1], "rb");
   if (!f) { perror(argv[1]); return 1; }
   const int did = argc >= 3 ? atoi(argv[2]) : 0;
   const double aov = argc >= 4 ? atof(argv[3]) : 72.0;
   const int nslots = argc >= 5 ? atoi(argv[4]) : 4;
+  const int scale = argc >= 6 && strcmp(argv[5], "half") == 0 ? 2 : 1;
+  if (argc >= 6 && scale == 1) { fprintf(stderr, "rdy4m: unknown option %s\n", argv[5]); return 1; }
   const double tanAOV = tan(aov / 2 / 180.0 * M_PI);
   int iw, ih;
   if (read_header(f, &iw, &ih)) return 1;
   const size_t ny = (size_t)iw * ih, nc = ny / 4;
 
-  rd_detector *d = rd_detector_create(did, iw, ih, nslots, 0);
+  rd_detector *d = rd_detector_create(did, iw / scale, ih / scale, nslots, 0);
   uint8_t *buf = (uint8_t *)malloc(ny + 2 * nc);      /* host frames are copied before the call returns: one buffer will do */
   double tm = now_ms();
   int pending = 0, polled = 0, last = 0, n = 0;
@@ -61,7 +66,7 @@ int main(int argc, char **argv) {
     if (more && pending < nslots && (more = read_frame(f, buf, ny + 2 * nc))) {
       const void *planes[3] = { buf, buf + ny, buf + ny + nc };
       const int pitches[3] = { iw, iw / 2, iw / 2 };
-      if (rd_detector_enqueue_planes(d, RD_PIX_I420, planes, pitches, RD_FRAME_HOST) < 0) { fprintf(stderr, "rdy4m: frame refused\n"); return 1; }
+      if (rd_detector_enqueue_scaled(d, RD_PIX_I420, planes, pitches, scale, RD_FRAME_HOST) < 0) { fprintf(stderr, "rdy4m: frame refused\n"); return 1; }
       pending++; n++;
       continue;
     }

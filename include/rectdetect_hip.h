@@ -89,6 +89,30 @@ long rd_detector_enqueue(rd_detector *d, const void *frame, int ws, int on_devic
 #define RD_PIX_I420 5   /* plane 0: Y, iw x ih; plane 1: U, plane 2: V, each iw/2 x ih/2 */
 long rd_detector_enqueue_planes(rd_detector *d, int format, const void *const planes[3], const int pitches[3], int on_device);
 
+/* Enqueue one frame that is LARGER than the detector: detection at half the camera's size, with the 2x2 box downscale done by the front kernel as it reads.
+ * scale 1: exactly rd_detector_enqueue_planes(d, format, planes, pitches, on_device).
+ * scale 2: the source frame is 2*iw x 2*ih pixels in `format` - all six RD_PIX_* formats, BGR included; planes and pitches laid out as for
+ *   rd_detector_enqueue_planes at the SOURCE size.  Such a source is even in both directions, so NV12 and I420 are accepted for odd iw or ih of the detector too.
+ *   With p_c(X, Y) the channel c (B, G, R) of source pixel (X, Y) under the conversion contract above, detector pixel (x, y) is, in int32,
+ *     out_c(x, y) = (p_c(2x, 2y) + p_c(2x+1, 2y) + p_c(2x, 2y+1) + p_c(2x+1, 2y+1) + 2) >> 2
+ *   NV12 and I420: each of the four source pixels is converted first - its own Y, the U and V the four share - and the four (B, G, R) are averaged afterwards (the
+ *   order the rectifier uses for its taps).  The result for such a frame - every plane, every list - is bit-identical to the result of rd_detector_enqueue on the
+ *   BGR frame this formula gives.  (Believed equal to what OpenCV's cv::resize(..., INTER_AREA) gives at exactly half size; not checked.)
+ * Any other scale: -1.
+ * Frame kinds, their lifetime rules and both detector kinds as for rd_detector_enqueue_planes; format and scale may change from frame to frame.  A device frame is read
+ * in place.  A host or pinned frame at scale 2 needs up to 16 bytes per detector pixel on the device: a slot gets a pair of staging buffers of that size with the
+ * first such frame it takes (rd_detector_counter 33); a detector that never takes one allocates nothing more.
+ * Returns the frame's sequence number, or -1 for an argument error, in which case nothing was enqueued: an unknown format, on_device or scale, a NULL plane the
+ * format uses, a pitch smaller than the SOURCE plane's row.  A bad handle and a call with nslots frames already in flight are fatal.
+ *
+ * rd_detector_rectify_polled (below) on a slot whose frame came in at scale 2 takes `quads` in DETECTOR coordinates - what rd_rect_quads gives for that frame's
+ * rectangles - and cuts the patches out of the full-size SOURCE: each corner is mapped on the host, in double, uncontracted,
+ *     X = x * 2.0 + 0.5;   Y = y * 2.0 + 0.5
+ * (pixel centres sit at integers, so detector pixel x covers source pixels 2x and 2x+1 and its centre lies at 2x + 0.5), and the job runs on the source planes
+ * with the source's width and height: the patch equals what rd_rectifier_enqueue gives for the full-size frame and the mapped quads.  A caller with a rectifier
+ * job of their own maps the corners the same way. */
+long rd_detector_enqueue_scaled(rd_detector *d, int format, const void *const planes[3], const int pitches[3], int scale, int on_device);
+
 /* Result of the oldest frame not yet polled: malloc'd array of rect_t-compatible records (176 bytes each, element 0
  * holds nItems), owned by the caller.  Blocks until that frame is done. */
 void *rd_detector_poll(rd_detector *d, double tanAOV);
@@ -117,7 +141,9 @@ int rd_detector_last_segments(rd_detector *d, void *dst, int max_records);
  * 15 = frames per group launch; 16 / 17 = groups whose strong masks took one launch / one launch per frame; 18 = frames that travelled straight from the caller's pinned
  * memory (RD_FRAME_HOST_PINNED), 19 = host frames copied into the detector's own pinned staging first (RD_FRAME_HOST);
  * 30 = polyline kind: frames whose segment list was longer than the block handed to pinned host memory at the end of the frame and was fetched by the poll;
- * 31 = device bytes of one slot's planes (both kinds; the polyline stage's compact scratch, the same for both, not included); 32 = records of that block (header included).
+ * 31 = device bytes of one slot's planes (both kinds; the polyline stage's compact scratch, the same for both, not included); 32 = records of that block (header included);
+ * 33 = device bytes of the scaled-source staging a slot owns once it has taken a host or pinned frame at scale 2 (rd_detector_enqueue_scaled; as many bytes again of
+ * pinned host memory go with it), 0 until a slot has - counter 31 does not include them.
  * The polyline kind keeps 0, 1, 2, 3, 15, 18, 19 as above (0: frames repeated in multi-launch form); the region, post-process and strong-mask counters stay 0 there. */
 long rd_detector_counter(rd_detector *d, int which);
 
@@ -214,7 +240,8 @@ long rd_rectifier_enqueue(rd_rectifier *r, int format, const void *const planes[
 int rd_rectifier_wait(rd_rectifier *r, uint8_t *status_out);
 /* One job from the frame of the most recently polled slot of d (either kind of detector): its planes, pitches and format as they were handed over.  A host frame
  * is rectified from the copy the detector uploaded - no second transfer - which lasts until the next enqueue on d: wait for the job first.  Device and pinned
- * frames: the caller keeps the buffer until the job's wait.  Returns as rd_rectifier_enqueue; -1 also when nothing has been polled yet or d and r are on different devices. */
+ * frames: the caller keeps the buffer until the job's wait.  A frame that came in at scale 2 (rd_detector_enqueue_scaled): quads in detector coordinates, patches from
+ * the full-size source, see there.  Returns as rd_rectifier_enqueue; -1 also when nothing has been polled yet or d and r are on different devices. */
 long rd_detector_rectify_polled(rd_detector *d, rd_rectifier *r, const double *quads, int n, void *out, int out_kind);
 
 /* ---- synthetic frames (csrc/rd_synth.c) */

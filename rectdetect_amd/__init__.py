@@ -69,6 +69,7 @@ def _declare(L):
         "rd_detector_poll_segments": (vp, [vp, vp]),
         "rd_detector_enqueue": (ctypes.c_long, [vp, vp, ci, ci]),
         "rd_detector_enqueue_planes": (ctypes.c_long, [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci]),
+        "rd_detector_enqueue_scaled": (ctypes.c_long, [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ci]),
         "rd_detector_poll": (vp, [vp, cd]),
         "rd_detector_drain": (None, [vp]),
         "rd_detector_set_aperture": (None, [vp, cd]),
@@ -315,6 +316,34 @@ def _enqueue_planes(h, fmt, planes, pitches, on_device, pinned):
     return r
 
 
+def _source_shapes(fmt, sw, sh):
+    """(rows, row bytes) of the planes of an sw x sh frame in format fmt"""
+    if fmt in (PIX_BGR, PIX_RGB):
+        return [(sh, sw * 3)]
+    if fmt in (PIX_BGRA, PIX_RGBA):
+        return [(sh, sw * 4)]
+    if fmt == PIX_NV12:
+        return [(sh, sw), (sh // 2, sw)]
+    if fmt == PIX_I420:
+        return [(sh, sw), (sh // 2, sw // 2), (sh // 2, sw // 2)]
+    raise ValueError("enqueue_scaled: unknown pixel format %r" % (fmt,))
+
+
+def _enqueue_scaled(h, iw, ih, fmt, planes, pitches, scale, on_device, pinned):
+    """rd_detector_enqueue_scaled for both detector kinds: planes and pitches as _plane_args, of a frame of scale*iw x scale*ih pixels.  Host planes are checked
+    against that SOURCE size.  ValueError on an argument error (nothing enqueued)."""
+    ptrs, pitch_c, kind, pitch, arrs = _plane_args(planes, pitches, on_device, pinned)
+    if arrs is not None and scale in (1, 2):
+        want = _source_shapes(fmt, scale * iw, scale * ih)
+        got = [(a.shape[0], a.size // a.shape[0]) for a in arrs]
+        if got[:len(want)] != want:
+            raise ValueError("enqueue_scaled: a %dx%d %s source has planes of (rows, row bytes) %r, not %r" % (scale * iw, scale * ih, PIX_NAMES[fmt], want, got))
+    r = lib().rd_detector_enqueue_scaled(h, int(fmt), ptrs, pitch_c, int(scale), kind)
+    if r == -1:
+        raise ValueError("rd_detector_enqueue_scaled: invalid arguments (format %r, scale %r, pitches %r)" % (fmt, scale, pitch))
+    return r
+
+
 def _quads_arg(quads):
     q = np.ascontiguousarray(quads, dtype=np.float64).reshape(-1, 8)
     return q, len(q)
@@ -353,6 +382,11 @@ class Detector:
         """a frame in pixel format `fmt` (PIX_*): numpy planes (HxWxC; NV12 (Y, UV); I420 (Y, U, V)), copied before the call returns - or, with on_device / pinned,
         the planes' addresses and their `pitches`, read in place until the frame's poll returned.  ValueError on an argument error (nothing enqueued)."""
         return _enqueue_planes(self.h, fmt, planes, pitches, on_device, pinned)
+
+    def enqueue_scaled(self, fmt, planes, pitches=None, on_device=False, pinned=False, scale=2):
+        """as enqueue_planes, for a source frame of scale*iw x scale*ih pixels (scale 2: every detector pixel the 2x2 box average of the conversion contract's BGR;
+        scale 1: enqueue_planes).  rectify_polled on such a frame takes quads in detector coordinates and reads the full-size source."""
+        return _enqueue_scaled(self.h, self.iw, self.ih, fmt, planes, pitches, scale, on_device, pinned)
 
     def poll(self, tan_aov):
         return _take_rects(lib().rd_detector_poll(self.h, float(tan_aov)))
@@ -431,6 +465,10 @@ class PolylineDetector:
     def enqueue_planes(self, fmt, planes, pitches=None, on_device=False, pinned=False):
         """as Detector.enqueue_planes"""
         return _enqueue_planes(self.h, fmt, planes, pitches, on_device, pinned)
+
+    def enqueue_scaled(self, fmt, planes, pitches=None, on_device=False, pinned=False, scale=2):
+        """as Detector.enqueue_scaled"""
+        return _enqueue_scaled(self.h, self.iw, self.ih, fmt, planes, pitches, scale, on_device, pinned)
 
     def poll(self, ids=False):
         """(segments[LS_DTYPE] with the header record, per-pixel segment ids or None) of the oldest frame not yet polled"""

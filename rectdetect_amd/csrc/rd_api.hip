@@ -330,6 +330,10 @@ struct Slot {
   // the frame's pixel format (RD_PIX_*), its planes and their row strides (hand_over); src = pl[0] and ws = pitch[0]; a host frame's planes are packed into bgr
   int fmt;
   const uint8_t *pl[3]; int pitch[3];
+  // rd_detector_enqueue_scaled: 1, or 2 - the planes hold a frame of 2 iw x 2 ih pixels, which the front kernel averages 2x2 as it reads.  A host frame of that size
+  // (up to 16 bytes per detector pixel) does not fit bgr / h_bgr: it travels through a pair of staging buffers of its own, which a slot gets with its first such frame
+  int scale;
+  uint8_t *sc_bgr; void *sc_h; size_t sc_bytes;
   // Captured launch sequences: [0] this slot's frame on its own, [1] the group this slot leads (group mode); by sequence - 0: the dense stages up to the first
   // labelling, 1 + 2 * round budget index + polyline mode: everything after the strong masks (the polyline kind's one sequence: 1 + polyline mode).  None reads the
   // frame (the colour conversion runs in front of them, outside), so a change of format or row stride re-captures nothing.
@@ -580,6 +584,8 @@ static void slot_free(Slot *s, int device) {
   }
   rdk::poly_scratch_destroy(s->ps);
   RD_HIP(hipHostFree(s->h_bgr)); RD_HIP(hipHostFree(s->h_pack));
+  if (s->sc_bgr) RD_HIP(hipFree(s->sc_bgr));
+  if (s->sc_h) RD_HIP(hipHostFree(s->sc_h));
   dfree(s->post_scratch); if (s->h_post) RD_HIP(hipHostFree(s->h_post));
   RD_HIP(hipEventDestroy(s->ev_begin)); RD_HIP(hipEventDestroy(s->ev_done)); RD_HIP(hipEventDestroy(s->ev_strong));
   RD_HIP(hipEventDestroy(s->ev_fork)); RD_HIP(hipEventDestroy(s->ev_mm)); RD_HIP(hipEventDestroy(s->ev_join)); RD_HIP(hipEventDestroy(s->ev_redo)); RD_HIP(hipEventDestroy(s->ev_dense)); RD_HIP(hipEventDestroy(s->ev_upload));
@@ -879,7 +885,11 @@ static void launch_frames(rd_detector *d, Slot *s, int nz, hipStream_t st) {
   RD_HIP(hipEventRecord(s->ev_begin, st));
   for (int i = 0; i < nz; i++) { s[i].pending_dense = 0; s[i].watch_begin = s->ev_begin; s[i].watch_done = s->ev_done; s[i].group_n = nz; }
   // the colour conversion, outside the captured sequences: its source changes from frame to frame
-  if (s->fmt != RD_PIX_BGR) {      // (rd_detector_enqueue_planes: the frames share format and pitches)
+  if (s->scale == 2) {      // (rd_detector_enqueue_scaled: the frames share format, scale and pitches)
+    const uint8_t *planes[RD_ZB_MAX][3];
+    for (int i = 0; i < nz; i++) for (int k = 0; k < 3; k++) planes[i][k] = s[i].pl[k];
+    rdk::pix2plab_half_transposed(st, s->fmt, s->plab0, s->tr, planes, s->pitch, d->iw, d->ih, nz, nz > 1 ? d->slot_pitch : 0);
+  } else if (s->fmt != RD_PIX_BGR) {      // (rd_detector_enqueue_planes: the frames share format and pitches)
     const uint8_t *planes[RD_ZB_MAX][3];
     for (int i = 0; i < nz; i++) for (int k = 0; k < 3; k++) planes[i][k] = s[i].pl[k];
     rdk::pix2plab_transposed(st, s->fmt, s->plab0, s->tr, planes, s->pitch, d->iw, d->ih, nz, nz > 1 ? d->slot_pitch : 0);
@@ -896,9 +906,9 @@ static void launch_frames(rd_detector *d, Slot *s, int nz, hipStream_t st) {
   if (d->batch == 1) for (int i = 0; i < nz; i++) slot_submitted(d, &s[i]);
 }
 
-// may two frames of a group share one front launch?  (one format, one set of row strides)
+// may two frames of a group share one front launch?  (one format, one scale, one set of row strides)
 static bool same_layout(const Slot *a, const Slot *b) {
-  if (a->fmt != b->fmt || a->ws != b->ws) return false;
+  if (a->fmt != b->fmt || a->scale != b->scale || a->ws != b->ws) return false;
   return a->fmt == RD_PIX_BGR || (a->pitch[1] == b->pitch[1] && a->pitch[2] == b->pitch[2]);
 }
 
@@ -915,7 +925,7 @@ static void group_launch(rd_detector *d, int g0) {
     if (!s->pending_dense) continue;
     cnt++;
     same = same && same_layout(s, &d->slots[g0]);
-    travelled = travelled || s->src == s->bgr;
+    travelled = travelled || s->src == s->bgr || (s->sc_bgr && s->src == s->sc_bgr);
   }
   if (cnt == 0) return;
   // Host frames travelled when they were handed over, one after the other on the detector's upload stream (hand_over).  The launching thread waits for that
@@ -1388,19 +1398,28 @@ static long enqueue_launch(rd_detector *d, Slot *s, Slot *wait_upload, struct ti
 
 // The next slot takes a frame - format, planes and row strides as the entry point `who` checked them; L: the layout a host frame is packed into - and launches it.
 // The BGR frames of rd_detector_enqueue and the frames of the other formats differ in three places, each a condition on fmt below; none of them has been measured the other way.
-static long hand_over(rd_detector *d, const char *who, int fmt, const void *const planes[3], const int pitches[3], const PixLayout &L, int on_device) {
+// scale 2 (rd_detector_enqueue_scaled): planes, pitches and L describe the source frame of 2 iw x 2 ih pixels; a host frame then travels through the slot's
+// scaled-source staging (sc_h / sc_bgr, allocated here with the slot's first such frame - the slot is idle: its last frame has been polled) on the same paths.
+static long hand_over(rd_detector *d, const char *who, int fmt, const void *const planes[3], const int pitches[3], const PixLayout &L, int on_device, int scale = 1) {
   if (d->next_enqueue - d->next_poll >= d->nslots) exitf(-1, "%s: %d frames already in flight (poll first)\n", who, d->nslots);
   RD_HIP(hipSetDevice(d->device));
   struct timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
   Slot *s = &d->slots[d->next_enqueue % d->nslots];
-  s->seq = d->next_enqueue; s->fmt = fmt;
+  s->seq = d->next_enqueue; s->fmt = fmt; s->scale = scale;
   for (int k = 0; k < 3; k++) { s->pl[k] = NULL; s->pitch[k] = 0; }
+  if (scale == 2 && on_device != RD_FRAME_DEVICE && !s->sc_bgr) {
+    s->sc_bytes = pix_layout(RD_PIX_BGRA, 2 * d->iw, 2 * d->ih).bytes;      // (16 bytes per detector pixel: the largest of the six layouts)
+    RD_HIP(hipMalloc((void **)&s->sc_bgr, s->sc_bytes));
+    RD_HIP(hipHostMalloc(&s->sc_h, s->sc_bytes, hipHostMallocDefault));
+  }
+  uint8_t *const dbuf = scale == 2 ? s->sc_bgr : s->bgr;      // a host frame's way: pinned staging hbuf (pageable frames only), device copy dbuf
+  void *const hbuf = scale == 2 ? s->sc_h : s->h_bgr;
   Slot *wait_upload = NULL;
   const bool group = d->zb > 1;
   if (on_device == RD_FRAME_DEVICE) {      // read where they lie (the caller keeps them valid until the frame's poll returned)
     for (int k = 0; k < L.np; k++) { s->pl[k] = (const uint8_t *)planes[k]; s->pitch[k] = pitches[k]; }
   } else {      // host frames: through the slot's buffers, one plane after the other
-    for (int k = 0; k < L.np; k++) { s->pl[k] = s->bgr + L.off[k]; s->pitch[k] = L.pitch[k]; }
+    for (int k = 0; k < L.np; k++) { s->pl[k] = dbuf + L.off[k]; s->pitch[k] = L.pitch[k]; }
     // Group mode: the frame travels NOW, on a stream of the detector's own (high-priority pool: a hardware queue nobody computes on), not when its group is launched:
     // eight uploads in front of a group's kernels kept that group's stream - a quarter of the device's queues - waiting for the copy engine for 1.6 of its 10.8 ms; and
     // an ordinary stream shares a hardware queue with a group's: 2786-2796 frames/s, the caller waiting 0.35 ms per frame.  No event: group_launch waits for the stream.
@@ -1423,11 +1442,11 @@ static long hand_over(rd_detector *d, const char *who, int fmt, const void *cons
       //  rate, a millisecond per group, with its blocks resident all the while.  profiles/NOTES_r06.md.)
       if (group) RD_HIP(hipStreamSynchronize(ust));      // (one transfer in the copy engine's queue at a time: the caller waits for the frame before - 0.1 ms where it used to copy for 0.16 - see group_launch)
       for (int k = 0; k < L.np; k++) {
-        if (pitches[k] == L.row[k] && L.row[k] == L.pitch[k]) RD_HIP(hipMemcpyAsync(s->bgr + L.off[k], planes[k], (size_t)L.row[k] * L.rows[k], hipMemcpyHostToDevice, ust));
-        else RD_HIP(hipMemcpy2DAsync(s->bgr + L.off[k], L.pitch[k], planes[k], pitches[k], L.row[k], L.rows[k], hipMemcpyHostToDevice, ust));
+        if (pitches[k] == L.row[k] && L.row[k] == L.pitch[k]) RD_HIP(hipMemcpyAsync(dbuf + L.off[k], planes[k], (size_t)L.row[k] * L.rows[k], hipMemcpyHostToDevice, ust));
+        else RD_HIP(hipMemcpy2DAsync(dbuf + L.off[k], L.pitch[k], planes[k], pitches[k], L.row[k], L.rows[k], hipMemcpyHostToDevice, ust));
       }
       d->n_frames_pinned++;
-    } else if (!group && fmt == RD_PIX_BGR && host_buffer_is_pinned(d, planes[0])) {      // (only rd_detector_enqueue's frames ask)
+    } else if (!group && fmt == RD_PIX_BGR && scale == 1 && host_buffer_is_pinned(d, planes[0])) {      // (only rd_detector_enqueue's frames ask)
       // The reference's call shape (oclrect_enqueueTask / executeOnce) on a buffer that happens to be page-locked - allocatePinnedMemory of oclhelper.h hands such memory out
       // (oclhelper.c:837-851, poly.cpp:68-69): the copy engine reads it in place, nothing is copied by the caller's thread, and the frame's kernels are launched behind the
       // transfer at once.  The reference's contract - the caller may reuse the buffer as soon as the call returns (oclrect.c:1256 copies it) - is kept by returning only when
@@ -1439,12 +1458,12 @@ static long hand_over(rd_detector *d, const char *who, int fmt, const void *cons
     } else {
       d->n_frames_copied++;
       UploadJob u;
-      u.L = L; u.dst = (char *)s->h_bgr; u.dev = (char *)s->bgr; u.st = ust; u.uploaded = 0;
+      u.L = L; u.dst = (char *)hbuf; u.dev = (char *)dbuf; u.st = ust; u.uploaded = 0;
       for (int k = 0; k < 3; k++) { u.src[k] = (const uint8_t *)planes[k]; u.spitch[k] = pitches[k]; }
       if (group) {      // the caller's thread packs, then the frame travels at once
         pack_range(&u, 0, L.bytes);
-        if (fmt != RD_PIX_BGR) RD_HIP(hipStreamSynchronize(ust));      // (one transfer queued at a time, as the pinned frames'; a BGR frame's upload is queued behind the one before without this wait)
-        RD_HIP(hipMemcpyAsync(s->bgr, s->h_bgr, L.bytes, hipMemcpyHostToDevice, ust));
+        if (fmt != RD_PIX_BGR || scale != 1) RD_HIP(hipStreamSynchronize(ust));      // (one transfer queued at a time, as the pinned frames'; a BGR frame's upload is queued behind the one before without this wait)
+        RD_HIP(hipMemcpyAsync(dbuf, hbuf, L.bytes, hipMemcpyHostToDevice, ust));
       } else {
         // a single frame: the copy into pinned memory and the upload in pieces, so that a piece travels while the next is being copied (6 MB at 1920x1080:
         // the copy alone takes a fifth of a millisecond of the caller's latency).  With helper threads (armed here: the call that hands a frame over is followed by
@@ -1484,6 +1503,18 @@ long rd_detector_enqueue_planes(rd_detector *d, int format, const void *const pl
   for (int k = 0; k < L.np; k++) if (!planes[k] || pitches[k] < L.row[k]) return -1;
   if (format == RD_PIX_BGR) return rd_detector_enqueue(d, planes[0], pitches[0], on_device);
   return hand_over(d, "rd_detector_enqueue_planes", format, planes, pitches, L, on_device);
+}
+
+long rd_detector_enqueue_scaled(rd_detector *d, int format, const void *const planes[3], const int pitches[3], int scale, int on_device) {
+  if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_enqueue_scaled: bad handle\n");
+  if (scale == 1) return rd_detector_enqueue_planes(d, format, planes, pitches, on_device);
+  // argument errors: -1, nothing enqueued
+  if (scale != 2) return -1;
+  if (format < RD_PIX_BGR || format > RD_PIX_I420 || !planes || !pitches) return -1;
+  if (on_device != RD_FRAME_HOST && on_device != RD_FRAME_DEVICE && on_device != RD_FRAME_HOST_PINNED) return -1;
+  const PixLayout L = pix_layout(format, 2 * d->iw, 2 * d->ih);      // (the source frame: even in both directions, whatever iw and ih are)
+  for (int k = 0; k < L.np; k++) if (!planes[k] || pitches[k] < L.row[k]) return -1;
+  return hand_over(d, "rd_detector_enqueue_scaled", format, planes, pitches, L, on_device, 2);
 }
 
 // device time of a polled frame (counters 1 and 2): the interval its events bracket - a group's is shared by its frames: each counts its part
@@ -1550,7 +1581,17 @@ long rd_detector_rectify_polled(rd_detector *d, rd_rectifier *r, const double *q
   if (d->last_polled_slot < 0 || rdrt::rectifier_device(r) != d->device) return -1;
   const Slot *s = &d->slots[d->last_polled_slot];
   const void *const planes[3] = { s->pl[0], s->pl[1], s->pl[2] };
-  return rd_rectifier_enqueue(r, s->fmt, planes, s->pitch, d->iw, d->ih, RD_FRAME_DEVICE, quads, n, out, out_kind);
+  if (s->scale == 2 && quads && n > 0 && n <= rdrt::rectifier_max_quads(r)) {
+    // a frame that came in at scale 2: the quads are in detector coordinates, the planes hold the source - each corner mapped to source coordinates (pixel centres
+    // at integers: detector pixel x covers source pixels 2x and 2x+1, centre 2x + 0.5), the job run on the source planes with the source's size
+    double *m = (double *)malloc((size_t)n * 8 * sizeof(double));
+    if (!m) exitf(-1, "rd_detector_rectify_polled: out of memory\n");
+    for (size_t i = 0; i < (size_t)n * 8; i++) m[i] = quads[i] * 2.0 + 0.5;
+    const long q = rd_rectifier_enqueue(r, s->fmt, planes, s->pitch, 2 * d->iw, 2 * d->ih, RD_FRAME_DEVICE, m, n, out, out_kind);
+    free(m);      // (the job holds the coefficients: rd_rectifier_enqueue evaluates them before it returns)
+    return q;
+  }
+  return rd_rectifier_enqueue(r, s->fmt, planes, s->pitch, s->scale == 2 ? 2 * d->iw : d->iw, s->scale == 2 ? 2 * d->ih : d->ih, RD_FRAME_DEVICE, quads, n, out, out_kind);
 }
 
 // The reference hands the aperture over with the poll, i.e. after the frame (oclrect_pollTask); whatever runs ahead of the poll - the
@@ -1601,6 +1642,7 @@ long rd_detector_counter(rd_detector *d, int which) {
     return (long)d->slot_bytes;
   }
   if (which == 32) return d->kind == RD_KIND_POLY ? d->handoff_rec : RD_MAXREC;
+  if (which == 33) { size_t b = 0; for (int i = 0; i < d->nslots; i++) if (d->slots[i].sc_bgr && d->slots[i].sc_bytes > b) b = d->slots[i].sc_bytes; return (long)b; }
   return which == 0 ? __atomic_load_n(&d->n_redo, __ATOMIC_RELAXED) : -1;
 }
 

@@ -51,4 +51,5 @@ cl_event finish_op(cl_command_queue q, const cl_event *events);
 void check_launch(const char *what);
 int current_device();
 int rectifier_device(const rd_rectifier *r);      // rd_rectify.hip: the device a rectifier lives on (-1: not a rectifier)
+int rectifier_max_quads(const rd_rectifier *r);   // rd_rectify.hip: the most quads one of its jobs takes (-1: not a rectifier)
 }  // namespace rdrt

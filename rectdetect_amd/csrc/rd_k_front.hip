@@ -230,6 +230,118 @@ __global__ __launch_bounds__(256) void k_pix2plab_t(uint32_t *__restrict__ out, 
   }
 }
 
+// ------------------------------------------------------------------------------------------------ half-size detection
+// k_pix2plab_t for a source frame of 2 iw x 2 ih pixels in any of the six formats (rd_detector_enqueue_scaled, scale 2): detector pixel (x, y) is the 2x2 box
+// average of source pixels (2x, 2y) .. (2x+1, 2y+1), per channel of the contract's (B, G, R), (sum + 2) >> 2 - NV12 and I420 convert each of the four first.
+// The same outputs, tile, grid and lane ownership as k_pix2plab_t (4 consecutive detector pixels of 4 rows per lane), so a lane reads 8 consecutive source
+// pixels of 2 rows per output row: HW<FMT> words per source row, or Y of both rows plus the one chroma row they share.  Wide loads under the same `wide` flag
+// (every address and pitch a multiple of 4), bytes otherwise and for groups that run past the row end; a group of m detector pixels has all of its 2m source
+// pixels inside the source row, and both source rows of a detector row exist, because the source is exactly twice the detector's size.
+template <int FMT> struct HalfW { static constexpr int row = (FMT == RD_PIX_BGR || FMT == RD_PIX_RGB) ? 6 : ((FMT == RD_PIX_BGRA || FMT == RD_PIX_RGBA) ? 8 : 2), n = FMT >= RD_PIX_NV12 ? 6 : 2 * row; };
+
+// the raw words of detector pixels x..x+3 of detector row y (m of them inside the row): packed formats: source row 2y, then source row 2y+1; NV12: Y of 2y (2 words),
+// Y of 2y+1, then U0 V0 .. U3 V3; I420: Y, Y, then U0..U3, V0..V3
+template <int FMT> __device__ __forceinline__ void pix_load_half(uint32_t (&w)[HalfW<FMT>::n], const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, const int (&pitch)[3], int x, int y, int m, bool wide) {
+  constexpr int RW = HalfW<FMT>::row;
+  const bool full = wide && m == 4;
+  if (FMT <= RD_PIX_RGBA) {
+    constexpr int bpp = (FMT == RD_PIX_BGR || FMT == RD_PIX_RGB) ? 3 : 4;
+    const uint8_t *q = p0 + (size_t)(2 * y) * pitch[0] + (size_t)(2 * x) * bpp;
+#pragma unroll
+    for (int r = 0; r < 2; r++, q += pitch[0]) {
+      if (full) {
+        if (bpp == 4) { const uint4 a = ((const uint4 *)q)[0], b = ((const uint4 *)q)[1]; w[RW * r] = a.x; w[RW * r + 1] = a.y; w[RW * r + 2] = a.z; w[RW * r + 3] = a.w; w[RW * r + 4] = b.x; w[RW * r + 5] = b.y; w[RW * r + 6] = b.z; w[RW * r + 7] = b.w; }
+        else { const uint2 a = ((const uint2 *)q)[0], b = ((const uint2 *)q)[1], c = ((const uint2 *)q)[2]; w[RW * r] = a.x; w[RW * r + 1] = a.y; w[RW * r + 2] = b.x; w[RW * r + 3] = b.y; w[RW * r + 4] = c.x; w[RW * r + 5] = c.y; }
+      } else {
+#pragma unroll
+        for (int k = 0; k < RW; k++) w[RW * r + k] = ld_bytes(q + 4 * k, 2 * m * bpp - 4 * k);
+      }
+    }
+  } else {
+    const uint8_t *q = p0 + (size_t)(2 * y) * pitch[0] + 2 * x;
+#pragma unroll
+    for (int r = 0; r < 2; r++, q += pitch[0]) {
+      if (full) { const uint2 a = *(const uint2 *)q; w[2 * r] = a.x; w[2 * r + 1] = a.y; }
+      else { w[2 * r] = ld_bytes(q, 2 * m); w[2 * r + 1] = ld_bytes(q + 4, 2 * m - 4); }
+    }
+    if (FMT == RD_PIX_NV12) {      // source chroma row (2y) >> 1 = y, bytes 2x .. 2x + 2m - 1
+      const uint8_t *uv = p1 + (size_t)y * pitch[1] + 2 * x;
+      if (full) { const uint2 a = *(const uint2 *)uv; w[4] = a.x; w[5] = a.y; }
+      else { w[4] = ld_bytes(uv, 2 * m); w[5] = ld_bytes(uv + 4, 2 * m - 4); }
+    } else {
+      const uint8_t *u = p1 + (size_t)y * pitch[1] + x, *v = p2 + (size_t)y * pitch[2] + x;
+      if (full) { w[4] = *(const uint32_t *)u; w[5] = *(const uint32_t *)v; }
+      else { w[4] = ld_bytes(u, m); w[5] = ld_bytes(v, m); }
+    }
+  }
+}
+
+// detector pixel j (0..3) of a group's raw words -> the box average's b, g, r
+template <int FMT> __device__ __forceinline__ void pix_bgr_half(const uint32_t (&w)[HalfW<FMT>::n], int j, int &b, int &g, int &r) {
+  constexpr int RW = HalfW<FMT>::row;
+  const auto byte = [&](int i) { return (int)((w[i >> 2] >> (8 * (i & 3))) & 255u); };
+  b = g = r = 2;
+#pragma unroll
+  for (int t = 0; t < 4; t++) {      // source pixel 2j + (t & 1) of source row t >> 1
+    const int sx = 2 * j + (t & 1), sr = t >> 1;
+    int pb, pg, pr;
+    if (FMT <= RD_PIX_RGBA) {
+      constexpr int bpp = (FMT == RD_PIX_BGR || FMT == RD_PIX_RGB) ? 3 : 4;
+      const int i = 4 * RW * sr + bpp * sx;
+      if (FMT == RD_PIX_BGR || FMT == RD_PIX_BGRA) { pb = byte(i); pg = byte(i + 1); pr = byte(i + 2); }
+      else { pr = byte(i); pg = byte(i + 1); pb = byte(i + 2); }
+    } else if (FMT == RD_PIX_NV12) yuv_bgr(byte(8 * sr + sx), byte(16 + 2 * j), byte(17 + 2 * j), pb, pg, pr);
+    else yuv_bgr(byte(8 * sr + sx), byte(16 + j), byte(20 + j), pb, pg, pr);
+    b += pb; g += pg; r += pr;
+  }
+  b >>= 2; g >>= 2; r >>= 2;
+}
+
+template <int FMT>
+__global__ __launch_bounds__(256) void k_pix2plab_half_t(uint32_t *__restrict__ out, P3 dst, PixZ src, int iw, int ih, size_t zs) {
+  const int z = blockIdx.z;
+  const uint8_t *__restrict__ p0 = src.p[0][z], *__restrict__ p1 = src.p[1][z], *__restrict__ p2 = src.p[2][z];
+  RD_ZSHIFT(zs, out, dst.p[0], dst.p[1], dst.p[2]);
+  __shared__ unsigned short s_s2l[RD_LUT_S2L_N], s_cf[RD_LUT_CF_N], s_cf2[RD_LUT_CF_N];
+  __shared__ unsigned short tile[3][64][66];
+  const int tid = rd_ty() * 64 + threadIdx.x;
+  const int x0 = blockIdx.x * 64, y0 = blockIdx.y * 64;
+  const int cx = (tid & 15) * 4, r0 = tid >> 4;    // the lane's detector pixels: columns x0 + cx .. + 3 of rows y0 + r0 + 16 k
+  const int x = x0 + cx, m = min(iw - x, 4);
+  // every word of the lane's 64 source pixels requested before the tables are staged (as k_pix2plab_t does)
+  uint32_t w[4][HalfW<FMT>::n] = {};
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int y = y0 + r0 + 16 * k;
+    if (m > 0 && y < ih) pix_load_half<FMT>(w[k], p0, p1, p2, src.pitch, x, y, m, src.wide != 0);
+  }
+  for (int i = tid; i < RD_LUT_S2L_N; i += 256) s_s2l[i] = rd_lut_s2l[i];
+  for (int i = tid; i < RD_LUT_CF_N; i += 256) { s_cf[i] = rd_lut_cfunc[i]; s_cf2[i] = rd_lut_cfunc2[i]; }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const int r = r0 + 16 * k, y = y0 + r;
+    if (m <= 0 || y >= ih) continue;
+    uint32_t v[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      int b, g, rr;
+      pix_bgr_half<FMT>(w[k], j, b, g, rr);
+      v[j] = plab_of(s_s2l, s_cf, s_cf2, b, g, rr);
+      tile[0][r][cx + j] = (unsigned short)(v[j] & 4095u); tile[1][r][cx + j] = (unsigned short)((v[j] >> 12) & 1023u); tile[2][r][cx + j] = (unsigned short)((v[j] >> 22) & 1023u);
+    }
+    uint32_t *o = out + (size_t)y * iw + x;
+    if (m == 4 && (iw & 3) == 0) *(uint4 *)o = make_uint4(v[0], v[1], v[2], v[3]);
+    else for (int j = 0; j < m; j++) o[j] = v[j];
+  }
+  __syncthreads();
+  for (int r = rd_ty(); r < 64; r += 4) {
+    const int ox = y0 + threadIdx.x, oy = x0 + r;   // output planes are ih wide, iw tall
+    if (ox < ih && oy < iw)
+      for (int k = 0; k < 3; k++) ((unsigned short *)dst.p[k])[(size_t)oy * ih + ox] = tile[k][threadIdx.x][r];
+  }
+}
+
 // four independent elements per thread and iteration: these kernels are pure memory streams, and one 4-byte load in
 // flight per lane leaves most of the HBM pipeline idle
 template <typename LD, typename ST> __device__ __forceinline__ void ew4(int n, LD ld, ST st) {
@@ -996,6 +1108,26 @@ void pix2plab_transposed(hipStream_t s, int fmt, uint32_t *out, float *const dst
     case RD_PIX_RGBA: hipLaunchKernelGGL(k_pix2plab_t<RD_PIX_RGBA>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
     case RD_PIX_NV12: hipLaunchKernelGGL(k_pix2plab_t<RD_PIX_NV12>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
     case RD_PIX_I420: hipLaunchKernelGGL(k_pix2plab_t<RD_PIX_I420>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
+    default: abort();
+  }
+}
+void pix2plab_half_transposed(hipStream_t s, int fmt, uint32_t *out, float *const dst[3], const uint8_t *const (*planes)[3], const int pitch[3], int iw, int ih, int nz, size_t zs) {
+  P3 d = { { dst[0], dst[1], dst[2] } };
+  PixZ z;
+  z.wide = 1;
+  for (int k = 0; k < 3; k++) {
+    z.pitch[k] = pitch[k];
+    if (pitch[k] & 3) z.wide = 0;
+    for (int i = 0; i < RD_ZB_MAX; i++) { z.p[k][i] = planes[i < nz ? i : 0][k]; if ((uintptr_t)z.p[k][i] & 3) z.wide = 0; }
+  }
+  const dim3 grid(cdiv(iw, 64), cdiv(ih, 64), nz);
+  switch (fmt) {
+    case RD_PIX_BGR: hipLaunchKernelGGL(k_pix2plab_half_t<RD_PIX_BGR>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
+    case RD_PIX_RGB: hipLaunchKernelGGL(k_pix2plab_half_t<RD_PIX_RGB>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
+    case RD_PIX_BGRA: hipLaunchKernelGGL(k_pix2plab_half_t<RD_PIX_BGRA>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
+    case RD_PIX_RGBA: hipLaunchKernelGGL(k_pix2plab_half_t<RD_PIX_RGBA>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
+    case RD_PIX_NV12: hipLaunchKernelGGL(k_pix2plab_half_t<RD_PIX_NV12>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
+    case RD_PIX_I420: hipLaunchKernelGGL(k_pix2plab_half_t<RD_PIX_I420>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
     default: abort();
   }
 }

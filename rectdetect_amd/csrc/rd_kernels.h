@@ -30,6 +30,9 @@ void bgr2plab_transposed(hipStream_t s, uint32_t *out, float *const dst[3], cons
 // the same outputs from a frame in one of the other pixel formats (fmt: RD_PIX_RGB .. RD_PIX_I420 of rectdetect_hip.h): planes[z][k] = plane k of frame z,
 // pitch[k] its row stride in bytes (one set for the nz frames)
 void pix2plab_transposed(hipStream_t s, int fmt, uint32_t *out, float *const dst[3], const uint8_t *const (*planes)[3], const int pitch[3], int iw, int ih, int nz, size_t zs);
+// the same outputs from source frames of 2 iw x 2 ih pixels (fmt: RD_PIX_BGR .. RD_PIX_I420; planes and pitch at the source size): every iw x ih pixel the 2x2 box
+// average of the contract's (B, G, R), (sum + 2) >> 2 (rd_detector_enqueue_scaled)
+void pix2plab_half_transposed(hipStream_t s, int fmt, uint32_t *out, float *const dst[3], const uint8_t *const (*planes)[3], const int pitch[3], int iw, int ih, int nz, size_t zs);
 void unpack_plab(hipStream_t s, float *L, float *a, float *b, const uint32_t *in, int n);
 void pack_plab(hipStream_t s, uint32_t *out, const float *L, const float *a, const float *b, int n);
 // transposes of `np` float planes (src planes W x H row-major -> dst planes H x W); src may be packed Lab (np = 3)

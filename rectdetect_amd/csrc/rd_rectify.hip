@@ -55,6 +55,7 @@ struct rd_rectifier {
 
 namespace rdrt {
 int rectifier_device(const rd_rectifier *r) { return r && r->magic == MAGIC_RECTIFIER ? r->device : -1; }
+int rectifier_max_quads(const rd_rectifier *r) { return r && r->magic == MAGIC_RECTIFIER ? r->max_quads : -1; }
 }
 
 extern "C" {
