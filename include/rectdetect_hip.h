@@ -149,7 +149,11 @@ long rd_detector_counter(rd_detector *d, int which);
 
 /* ---- Environment.  Everything is read when a detector is created (rd_detector_create / init_oclrect) and never again; an empty value counts as unset.
  *   for users:   RD_DEVICE_POST=0|1      candidate funnel + pose estimation on the device (rd_k_post.hip) instead of the host threads (default: host, unless the process may
- *                                        use no more than two cores)
+ *                                        use no more than two cores).  The device holds fixed tables; a frame beyond any of them is flagged there and post-processed
+ *                                        on the host instead (counter 12 instead of 11), which has no such bounds (rd_post.c grows its work space): more than 8192 distinct boundary ids under the probes,
+ *                                        2048 components with four or more segments, 1024 candidates (such components + polyline heads), 65536 (segment, component)
+ *                                        pairs of those components, 160 segments in one candidate, or a convex hull whose construction goes deeper than 48 nested
+ *                                        calls or needs more than 16 * 160 pool entries (rd_post_device_limits; each edge has a test in tests/test_gpu_post_device.py)
  *                RD_POST_HELPERS=n       helper threads that share a frame's pose estimations with the polling thread, reference-API shape only (default by core count, 0 = none)
  *                RD_NO_GRAPH=1           plain launches instead of captured hipGraphs
  *   test hooks:  RD_ZBATCH=k / RD_BATCH=k (frames per group launch / per set of sparse-stage launches), RD_REGION_ROUNDS_FIXED=8..20 and RD_BUDGET_CYCLE=n (launch budget of
@@ -173,6 +177,20 @@ void *rd_postprocess_planes(const void *segs, const int32_t *boundary, const int
 /* test tap: the 15 probe pixels of a segment as the sampling kernel computes them (x, y pairs; (-1, -1): outside the frame) - compared with the oracle's
  * independent restatement of oclrect.c:1066-1083 */
 void rd_probe_pixels(float x0, float y0, float x1, float y1, int iw, int ih, int32_t *out);
+/* test tap: rd_postprocess_planes' twin on the device post-process (rd_k_post.hip), so that its capacity edges can be tested on crafted inputs.  Uploads the
+ * list, the boundary plane and the vote table to `device`, takes the probes there (the frame path's sampling kernel) and runs the device post-process once, on a
+ * stream, scratch and result block of its own, then frees everything.  The plane holds a component id per pixel: fatal in a -DRD_BOUNDARY_FLATTEN=0 tuning
+ * build, whose sampling kernel follows the plane's values as links.  Returns the list exactly as a poll assembles it from the result block - the valid
+ * candidates' records in candidate order, element 0 the header, malloc'd, owned by the caller - or NULL when the device flagged an overflow (the frame path
+ * then hands the frame to the host post-process).  Either way info[0] = candidates counted (capped at the candidate capacity), info[1] = the overflow word,
+ * info[2..7] = 0.  Needs a GPU (fatal without one); not called by the frame path. */
+void *rd_postprocess_planes_device(int device, const void *segs, const int32_t *boundary, const int32_t *table, int iw, int ih, double tanAOV, int32_t info[8]);
+/* the fixed capacities of the device post-process (see RD_DEVICE_POST under "Environment"): out[0] hash slots for distinct boundary ids under the probes, [1] components
+ * with at least four segments, [2] candidates per frame (such components + polyline heads), [3] (segment, component) pairs of those components, [4] segments
+ * per candidate, [5] waves per frame of the solving kernel (a candidate count above it only makes waves take several), [6] depth of the hull's explicit stack, [7] entries of
+ * the hull's pool (the index lists of its pending calls).
+ * Runs without a GPU. */
+void rd_post_device_limits(int32_t out[8]);
 
 /* ---- rectified patches: what is INSIDE a quad, as an upright image of fixed size (rd_k_rectify.hip, rd_rectify.hip).
  * The reference only draws outlines (rect.cpp, vidrect.cpp), so the arithmetic is defined here - exactly, so that an independent restatement (tests/rectify.py,

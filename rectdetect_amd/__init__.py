@@ -77,6 +77,9 @@ def _declare(L):
         "rd_detector_last_segments": (ci, [vp, vp, ci]),
         "rd_detector_debug_plane": (cz, [vp, ctypes.c_char_p, vp, cz]),
         "rd_postprocess_planes": (vp, [vp, vp, vp, ci, ci, cd]),
+        "rd_postprocess_planes_device": (vp, [ci, vp, vp, vp, ci, ci, cd, vp]),
+        "rd_post_device_limits": (None, [vp]),
+        "rd_probe_pixels": (None, [cf, cf, cf, cf, ci, ci, vp]),
         "rd_post_run": (vp, [vp, ci, vp, ci, ci, cd]),
         "rd_post_helpers_configure": (None, [ci]),
         "rd_post_helpers_arm": (None, []),
@@ -582,3 +585,24 @@ def postprocess_planes(segs, boundary, table, iw, ih, tan_aov):
     boundary = np.ascontiguousarray(boundary, dtype=np.int32)
     table = np.ascontiguousarray(table, dtype=np.int32)
     return _take_rects(lib().rd_postprocess_planes(segs.ctypes.data, boundary.ctypes.data, table.ctypes.data, iw, ih, float(tan_aov)))
+
+
+POST_LIMIT_NAMES = ("POST_HT", "POST_MAXG", "POST_MAXC", "POST_MEMBERS", "POST_CAP", "POST_WAVES", "RDP_HULL_DEPTH", "RDP_HULL_POOL")
+
+
+def post_device_limits():
+    """The fixed capacities of the device post-process (rd_post_device_limits) by name; runs without a GPU."""
+    out = np.zeros(8, np.int32)
+    lib().rd_post_device_limits(out.ctypes.data)
+    return dict(zip(POST_LIMIT_NAMES, (int(v) for v in out)))
+
+
+def postprocess_planes_device(segs, boundary, table, iw, ih, tan_aov, device=0):
+    """Device post-process alone (rd_k_post.hip) on full planes: (rectangles, info).  rectangles is the list as a poll assembles it, or None when the device
+    flagged an overflow; info[0] = candidates counted, info[1] = the overflow word.  Needs a GPU."""
+    segs = np.ascontiguousarray(segs)
+    boundary = np.ascontiguousarray(boundary, dtype=np.int32)
+    table = np.ascontiguousarray(table, dtype=np.int32)
+    info = np.zeros(8, np.int32)
+    ptr = lib().rd_postprocess_planes_device(int(device), segs.ctypes.data, boundary.ctypes.data, table.ctypes.data, iw, ih, float(tan_aov), info.ctypes.data)
+    return (_take_rects(ptr) if ptr else None), info

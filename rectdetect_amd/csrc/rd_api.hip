@@ -1062,6 +1062,20 @@ static void slot_fetch(Slot *s, void *dst, const void *src, size_t bytes) {
   RD_HIP(hipStreamSynchronize(s->st_redo));
 }
 
+// the list a poll returns from a result block of the device post-process (rd_k_post.hip: PolyFrame::post_out) that did not overflow: the
+// valid candidates' records in candidate order, element 0 the header.  (Also what the test tap rd_postprocess_planes_device returns.)
+static rect_t *post_block_rectangles(const int *h_post) {
+  const int nc = h_post[0];
+  const char *recs = (const char *)(h_post + 8 + RD_POST_MAXC);
+  int nv = 0;
+  for (int c = 0; c < nc; c++) nv += h_post[8 + c] != 0;
+  rect_t *ret = (rect_t *)calloc((size_t)nv + 1, sizeof(rect_t));
+  int at = 1;
+  for (int c = 0; c < nc; c++) if (h_post[8 + c] != 0) memcpy(&ret[at++], recs + (size_t)c * sizeof(rect_t), sizeof(rect_t));
+  ret[0].nItems = nv + 1;
+  return ret;
+}
+
 // host post-process of a slot whose device work is complete: rectangles for the given aperture + a copy of the segment list
 // (can run again for another aperture: touches nothing on the device but, for frames with very many segments, two copies)
 static void *slot_rectangles(rd_detector *d, Slot *s, double tanAOV, void **segs_out, int *nsegs_out) {
@@ -1069,14 +1083,7 @@ static void *slot_rectangles(rd_detector *d, Slot *s, double tanAOV, void **segs
   // the rectangles the device computed (rd_k_post.hip), if this frame has them for this aperture and nothing overflowed there:
   // the valid candidates' records in candidate order (= the reference's list order)
   if (s->post_mode && s->post_tan == tanAOV && s->h_post[1] == 0 && n + 1 <= d->maxrec_dev) {
-    const int nc = s->h_post[0];
-    const char *recs = (const char *)(s->h_post + 8 + RD_POST_MAXC);
-    int nv = 0;
-    for (int c = 0; c < nc; c++) nv += s->h_post[8 + c] != 0;
-    rect_t *ret = (rect_t *)calloc((size_t)nv + 1, sizeof(rect_t));
-    int at = 1;
-    for (int c = 0; c < nc; c++) if (s->h_post[8 + c] != 0) memcpy(&ret[at++], recs + (size_t)c * sizeof(rect_t), sizeof(rect_t));
-    ret[0].nItems = nv + 1;
+    rect_t *ret = post_block_rectangles(s->h_post);
     // the segment list handed to rd_detector_last_segments: all n records, as on the host path - the pinned block holds the first
     // RD_MAXREC of them, a frame with more fetches the list from the device
     void *copy0 = malloc((size_t)(n + 1) * 56);
@@ -1841,6 +1848,49 @@ void oclrect_enqueueTask(struct oclrect_t *t, uint8_t *imgData, int ws) {
 rect_t *oclrect_pollTask(struct oclrect_t *t, const double tanAOV) {
   if (!t || t->magic != MAGIC_RECT) exitf(-1, "oclrect_pollTask: bad handle\n");
   return (rect_t *)rd_detector_poll(t->det, tanAOV);
+}
+
+// ---- test taps of the device post-process (neither is on the frame path)
+void rd_post_device_limits(int32_t out[8]) { rdk::post_limits(out); }
+
+// rd_postprocess_planes' device twin: the caller's list, boundary plane and vote table through k_sample_segments and the three launches of
+// rdk::post_device, once, on a stream, scratch and result block of its own; the result block is packed by the code a poll uses.
+// The caller's plane holds a component id per pixel, as the default build's frame path leaves it.  A -DRD_BOUNDARY_FLATTEN=0 build reads
+// the plane as a forest of pixel indices and would follow the caller's ids as links: the tap refuses to run there.
+void *rd_postprocess_planes_device(int device, const void *segs, const int32_t *boundary, const int32_t *table, int iw, int ih, double tanAOV, int32_t info[8]) {
+  if (!RD_BOUNDARY_FLATTEN) exitf(-1, "rd_postprocess_planes_device: needs a build with RD_BOUNDARY_FLATTEN=1 (the plane holds ids, not links)\n");
+  RD_HIP(hipSetDevice(device));
+  int n = ((const int *)segs)[0];
+  if (n < 0) n = 0;
+  const size_t N = (size_t)iw * ih;
+  const int nentry = iw * ih * 4 / 5;
+  char *d_ls = dnew<char>((size_t)(n + 1) * 56);
+  int *d_boundary = dnew<int>(N), *d_table = dnew<int>((size_t)nentry * 5), *d_probes = dnew<int>((size_t)(n + 1) * 15 * 6);
+  int *d_scratch = dnew<int>(rdk::post_scratch_ints());
+  int *h_post = NULL, *h_post_dev = NULL;
+  const size_t out_bytes = rdk::post_out_ints() * sizeof(int);
+  RD_HIP(hipHostMalloc((void **)&h_post, out_bytes, hipHostMallocDefault)); memset(h_post, 0, out_bytes);
+  RD_HIP(hipHostGetDevicePointer((void **)&h_post_dev, h_post, 0));
+  hipStream_t st = NULL;
+  RD_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  RD_HIP(hipMemcpyAsync(d_ls, segs, (size_t)(n + 1) * 56, hipMemcpyHostToDevice, st));
+  RD_HIP(hipMemcpyAsync(d_boundary, boundary, N * sizeof(int), hipMemcpyHostToDevice, st));
+  RD_HIP(hipMemcpyAsync(d_table, table, (size_t)nentry * 5 * sizeof(int), hipMemcpyHostToDevice, st));
+  RD_HIP(hipMemsetAsync(d_probes, 0, (size_t)(n + 1) * 15 * 6 * sizeof(int), st));
+  rdk::PolyFrame f;
+  memset(&f, 0, sizeof(f));
+  f.lslist = d_ls; f.boundary = d_boundary; f.table = d_table; f.probes = d_probes; f.pack = NULL;
+  f.post_scratch = d_scratch; f.post_out = h_post_dev;
+  rdk::sample_segments(st, &f, 1, n + 1, iw, ih, nentry, 0);
+  rdk::post_device(st, &f, 1, n + 1, iw, ih, tanAOV);
+  rdrt::check_launch("rd_postprocess_planes_device");
+  RD_HIP(hipStreamSynchronize(st));
+  if (info) { for (int i = 0; i < 8; i++) info[i] = 0; info[0] = h_post[0]; info[1] = h_post[1]; }
+  void *ret = h_post[1] == 0 ? (void *)post_block_rectangles(h_post) : NULL;
+  RD_HIP(hipStreamDestroy(st));
+  RD_HIP(hipHostFree(h_post));
+  dfree(d_scratch); dfree(d_probes); dfree(d_table); dfree(d_boundary); dfree(d_ls);
+  return ret;
 }
 
 }  // extern "C"

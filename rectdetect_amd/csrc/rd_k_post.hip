@@ -190,19 +190,25 @@ __global__ __launch_bounds__(64) void k_post_solve(const PolyFrames FRS, int max
   int *outb = FRM.post_out;                      // [0] candidates, [1] overflow, [2] tan (2 ints), [8 + c] validity, rects behind
   rdp_rect *rects = (rdp_rect *)(outb + 8 + POST_MAXC);
   const int lane = threadIdx.x;
-  const int ncand = ctr[1];
-  int n = *(const int *)ls;
-  if (n > max_records - 1) n = max_records - 1;
   __shared__ rdp_rays R;
   __shared__ double t0[2][4];
-  __shared__ int s_ok, s_first, s_over;
+  __shared__ int s_ok, s_first, s_over, s_skip;
   __shared__ rdp_p2 s_centre;
   // the funnel's work space (35 KB) lives in LDS: lane 0 walks through it one access after the other, a trip to global memory each
   // time made the kernel three times as long
   __shared__ __align__(16) unsigned char wmem[RDP_WORK_BYTES(POST_CAP)];
   rdp_work w;
   rdp_work_place(&w, wmem, POST_CAP);
-  if (lane == 0) s_over = 0;
+  if (lane == 0) { s_over = 0; s_skip = ctr[2]; }
+  __syncthreads();
+  // a frame whose candidate stage overflowed has no member lists (step (d) was skipped: mem[] holds what an earlier frame left) and goes to
+  // the host path anyway: nothing of it is looked at here, neither cand[], mem[], probes nor ls.  One read per block, so the whole wave takes the
+  // same way.  ctr[2] is also the word a block of this launch sets at its end when its own work space ran out (below): a block that starts after
+  // that skips its candidates for that reason.  That loses nothing either: the flag is final, the host discards the block whatever it holds.
+  if (s_skip != 0) return;
+  const int ncand = ctr[1];
+  int n = *(const int *)ls;
+  if (n > max_records - 1) n = max_records - 1;
   for (int c = blockIdx.x; c < ncand; c += gridDim.x) {
     const int type = cand[c * 4], key = cand[c * 4 + 1];
     if (lane == 0) {
@@ -215,9 +221,11 @@ __global__ __launch_bounds__(64) void k_post_solve(const PolyFrames FRS, int max
         for (int j = 0; j < cnt && !w.overflow; j++) {
           int lsid = 0x7fffffff;                   // members in ascending order: the smallest one above the previous
           for (int q = 0; q < cnt; q++) { const int v = mem[off + q]; if (v > last && v < lsid) lsid = v; }
+          if (lsid == 0x7fffffff) break;           // (no member above the previous one: the list holds fewer than it announced)
           last = lsid;
           const int *e = nullptr;
           for (int k = 0; k < 15; k++) { const int *pr = probes + (size_t)(lsid * 15 + k) * 6; if (pr[0] == key) { e = pr + 1; break; } }
+          if (e == nullptr) { w.overflow = 1; break; }      // (a member none of whose probes carries the key: dropped, the host path takes the frame)
           rdp_seg whole;
           whole.e0 = rdp_pt(ls[lsid].x0, ls[lsid].y0); whole.e1 = rdp_pt(ls[lsid].x1, ls[lsid].y1);
           if (na >= POST_CAP) { w.overflow = 1; break; }
@@ -343,6 +351,11 @@ namespace rdk {
 
 size_t post_scratch_ints() { return (size_t)PS_END; }
 size_t post_out_ints() { return 8 + (size_t)POST_MAXC + (size_t)POST_MAXC * (sizeof(rdp_rect) / sizeof(int)); }
+// the fixed capacities above, for rd_post_device_limits (tests build inputs that sit on each of them)
+void post_limits(int out[8]) {
+  const int v[8] = { POST_HT, POST_MAXG, POST_MAXC, POST_MEMBERS, POST_CAP, POST_WAVES, RDP_HULL_DEPTH, RDP_POOL_INTS(POST_CAP) };
+  for (int i = 0; i < 8; i++) out[i] = v[i];
+}
 
 // rectangles of nb frames from their segment lists and probes (frames[z].probes / lslist as sample_segments left them) into frames[z].post_out
 void post_device(hipStream_t st, const PolyFrame *frames_host, int nb, int max_records, int iw, int ih, double tanAOV) {

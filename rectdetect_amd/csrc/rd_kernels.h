@@ -131,6 +131,7 @@ void sample_segments(hipStream_t s, const PolyFrame *frames, int nb, int max_rec
 // ---- rd_k_post.hip: segments + probes -> rectangles on the device (candidate funnel + pose estimation, one wave per candidate)
 size_t post_scratch_ints();      // ints of PolyFrame::post_scratch
 size_t post_out_ints();          // ints of PolyFrame::post_out
+void post_limits(int out[8]);    // POST_HT, POST_MAXG, POST_MAXC, POST_MEMBERS, POST_CAP, POST_WAVES, RDP_HULL_DEPTH, RDP_POOL_INTS(POST_CAP)
 void post_device(hipStream_t s, const PolyFrame *frames, int nb, int max_records, int iw, int ih, double tanAOV);
 
 // ---- rd_k_poly.hip: polyline stage on compacted chain pixels

@@ -337,6 +337,32 @@ void rd_copy_to_staging(void *dst, const void *src, size_t n) { memcpy(dst, src,
 
 /* ------------------------------------------------------------------ rh:1049-1226 */
 
+/* rdp_funnel without the limits of the fixed work space (rd_post_core.h): when the hull's stack or pool runs out, the candidate gets both four
+ * times as large from the heap and its segments as they came (`keep`: room for w->cap segments; the funnel sorts and shortens w->als), and the
+ * funnel runs again.  A hull of np points nests at most np calls deep and its pending calls hold fewer than np * np indices, so this ends.
+ * Camera frames do not get here: the first run uses the work space in place. */
+static int funnel_unbounded(rdp_work *w, rdp_seg *keep, int na, rdp_p2 *centre) {
+  int *pool = NULL, *pool0 = w->pool;
+  rdp_hull_frame *stack = NULL, *stack0 = w->stack;
+  const int npool0 = w->npool, depth0 = w->depth;
+  const size_t np = 2 * (size_t)na + 2;
+  memcpy(keep, w->als, sizeof(rdp_seg) * (size_t)na);
+  int ok = rdp_funnel(w, na, centre);
+  while (w->overflow) {
+    if ((size_t)w->depth > np && (size_t)w->npool > 4 * (size_t)w->cap + np * np) { ok = 0; break; }      /* (unreachable: see above) */
+    w->depth *= 4; w->npool *= 4;
+    free(pool); free(stack);
+    w->pool = pool = (int *)malloc(sizeof(int) * (size_t)w->npool);
+    w->stack = stack = (rdp_hull_frame *)malloc(sizeof(rdp_hull_frame) * (size_t)w->depth);
+    memcpy(w->als, keep, sizeof(rdp_seg) * (size_t)na);
+    w->overflow = 0;
+    ok = rdp_funnel(w, na, centre);
+  }
+  free(pool); free(stack);
+  w->pool = pool0; w->stack = stack0; w->npool = npool0; w->depth = depth0; w->overflow = 0;
+  return ok;
+}
+
 void *rd_post_run(const void *segs, int max_records, const int *probes, int iw, int ih, double tanAOV) {
   const linesegment_t *ls = (const linesegment_t *)segs;
   int n = ((const int *)segs)[0];
@@ -350,8 +376,9 @@ void *rd_post_run(const void *segs, int max_records, const int *probes, int iw, 
     memcpy(jobs[njobs].sides, w.out, sizeof(jobs[njobs].sides)); jobs[njobs].centre = centre; jobs[njobs].status = (st); njobs++; } while (0)
   /* work space of the funnel: a candidate never holds more segments than the frame has */
   rdp_work w;
-  void *wmem = malloc(RDP_WORK_BYTES(n + 4));
+  void *wmem = malloc(RDP_WORK_BYTES(n + 4) + sizeof(rdp_seg) * (size_t)(n + 4));
   rdp_work_place(&w, wmem, n + 4);
+  rdp_seg *keep = (rdp_seg *)((char *)wmem + RDP_WORK_BYTES(n + 4));
   rdp_p2 centre;
 
   /* pass 1: segments grouped by the boundary component they run along */
@@ -392,7 +419,7 @@ void *rd_post_run(const void *segs, int max_records, const int *probes, int iw, 
       w.als[na].e0 = rdp_pt(x0, y0); w.als[na].e1 = rdp_pt(x1, y1);
       na++;
     }
-    if (rdp_funnel(&w, na, &centre)) PUSH_CANDIDATE(0);
+    if (funnel_unbounded(&w, keep, na, &centre)) PUSH_CANDIDATE(0);
   }
   for (int gi = 0; gi < ngroups; gi++) { intlist *set = (intlist *)ArrayMap_get(groups, keys[gi]); free(set->v); free(set); }
   free(keys);
@@ -406,7 +433,7 @@ void *rd_post_run(const void *segs, int max_records, const int *probes, int iw, 
       const rdp_p2 e0 = rdp_pt(ls[j].x0, ls[j].y0), e1 = rdp_pt(ls[j].x1, ls[j].y1);
       if (rdp_d2(e0, e1) > 32.0 * 32.0) { w.als[na].e0 = e0; w.als[na].e1 = e1; na++; }
     }
-    if (rdp_funnel(&w, na, &centre)) PUSH_CANDIDATE(2);
+    if (funnel_unbounded(&w, keep, na, &centre)) PUSH_CANDIDATE(2);
   }
   free(wmem);
 

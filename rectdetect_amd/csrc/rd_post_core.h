@@ -26,16 +26,25 @@ typedef struct { double c2[4][2]; double c3[4][3]; double value; uint32_t status
 /* one pending call of the hull construction (see rdp_hull_side) */
 typedef struct { int s0, sn, l0, ln, mark, stage; rdp_p2 left, right, pf; } rdp_hull_frame;
 #define RDP_HULL_DEPTH 48
+#define RDP_POOL_INTS(cap) (16 * (cap))      /* index lists of the hull's pending calls */
 
-/* work space of one candidate: cap segments in `als` and `out`, 2*cap points, hull points, 16*cap pool ints and the hull's call stack */
+/* LIMITS OF THE WORK SPACE.  The reference's hull recurses and allocates without a bound; here a candidate whose hull nests `depth` calls
+ * deep, or whose pending calls hold more than `npool` indices, sets `overflow` and rdp_funnel returns 0 without a verdict.  It takes a hull
+ * one of whose sides peels off point by point - every farthest point next to an end of its chord - 48 times over, or a dozen times with 160
+ * segments in the candidate (tests/postcases.py: hull_deep, hull_pool).  On the device (rdp_work_place: RDP_HULL_DEPTH calls,
+ * RDP_POOL_INTS(POST_CAP) indices) that flags the frame, which the host path then takes.  The host (rd_post.c: funnel_unbounded) has nobody
+ * to hand over to: it gives the candidate a larger stack and pool and runs the funnel again, so its list is the reference's for such shapes too.
+ *
+ * work space of one candidate: cap segments in `als` and `out`, 2*cap points, hull points, 16*cap pool ints and the hull's call stack */
 typedef struct {
   rdp_seg *als, *out;
   rdp_p2 *pts, *hull;
   int *pool;
   rdp_hull_frame *stack;
   int cap, overflow;
+  int npool, depth;      /* entries of `pool`, frames of `stack` */
 } rdp_work;
-#define RDP_WORK_BYTES(cap) ((size_t)(cap) * (2 * sizeof(rdp_seg) + 4 * sizeof(rdp_p2) + 16 * sizeof(int)) + RDP_HULL_DEPTH * sizeof(rdp_hull_frame))
+#define RDP_WORK_BYTES(cap) ((size_t)(cap) * (2 * sizeof(rdp_seg) + 4 * sizeof(rdp_p2)) + RDP_POOL_INTS(cap) * sizeof(int) + RDP_HULL_DEPTH * sizeof(rdp_hull_frame))
 RD_HD void rdp_work_place(rdp_work *w, void *mem, int cap) {
   char *p = (char *)mem;
   w->stack = (rdp_hull_frame *)p; p += sizeof(rdp_hull_frame) * RDP_HULL_DEPTH;
@@ -45,6 +54,7 @@ RD_HD void rdp_work_place(rdp_work *w, void *mem, int cap) {
   w->hull = (rdp_p2 *)p; p += sizeof(rdp_p2) * (size_t)cap * 2;
   w->pool = (int *)p;
   w->cap = cap; w->overflow = 0;
+  w->npool = RDP_POOL_INTS(cap); w->depth = RDP_HULL_DEPTH;
 }
 
 /* ------------------------------------------------------------------ 2-D geometry (rh:389-425) */
@@ -65,8 +75,12 @@ RD_HD int rdp_probe_pixel(float fx0, float fy0, float fx1, float fy1, int k, int
   const double f = (k / 5 + 0.5) / 3;
   const int off = k % 5 - 2;
   const double cx = (a.x + e.x * f) + -u.y * off, cy = (a.y + e.y * f) + u.x * off;
-  *sx = (int)(cx + 0.5); *sy = (int)(cy + 0.5);
-  return !(*sx < 0 || *sx >= iw || *sy < 0 || *sy >= ih);
+  /* (int) truncates: the pixel is inside for -1 < c + 0.5 < size.  Compared as doubles, so that end points far outside the frame (or not
+   * numbers at all) are outside by definition and never reach a cast whose result is undefined. */
+  const double px = cx + 0.5, py = cy + 0.5;
+  if (!(px > -1.0 && px < (double)iw && py > -1.0 && py < (double)ih)) { *sx = -1; *sy = -1; return 0; }
+  *sx = (int)px; *sy = (int)py;
+  return 1;
 }
 
 /* foot of the perpendicular from p on the LINE through v, w (rh:400-406) */
@@ -235,7 +249,7 @@ RD_HD int rdp_hull_side(rdp_work *w, int npts, int nh, int s0, int sn, rdp_p2 le
       const rdp_p2 pf = w->pts[w->pool[f->s0 + far_i]];
       const rdp_p2 nr = rdp_pt(pf.y - f->right.y, f->right.x - pf.x);
       const rdp_p2 nl = rdp_pt(f->left.y - pf.y, pf.x - f->left.x);
-      if (*pool_top + 2 * f->sn > 16 * w->cap || sp + 1 >= RDP_HULL_DEPTH) { w->overflow = 1; return nh; }
+      if (*pool_top + 2 * f->sn > w->npool || sp + 1 >= w->depth) { w->overflow = 1; return nh; }
       const int r0 = *pool_top;
       int rn = 0;
       for (int i = 0; i < f->sn; i++) { if (i == far_i) continue; const int q = w->pool[f->s0 + i]; if (rdp_dot(rdp_sub(w->pts[q], pf), nr) > 0) w->pool[r0 + rn++] = q; }

@@ -895,7 +895,8 @@ def test_device_postprocess_equals_host_postprocess(nslots):
     """RD_DEVICE_POST=1: candidate funnel + pose estimation on the device (rd_k_post.hip: one wave per candidate, double precision,
     same source for the arithmetic as the host path) - rectangle lists bit-identical to the host post-process, on stream frames,
     on the busy frames (up to 66 rectangles, 1500 segments) and with the sparse stages batched; frames the device cannot take
-    (no aperture known yet: the reference passes it with the poll; capacity overflow) fall back to the host path and are counted."""
+    (no aperture known yet: the reference passes it with the poll; capacity overflow) fall back to the host path and are counted.
+    (No frame here reaches a capacity: every capacity edge is tested on inputs made for it in tests/test_gpu_post_device.py.)"""
     g = golden("hard_rect")
     jobs = [(640, 480, [synth.frame(synth.SEED0 + 31, 640, 480, t) for t in range(9)])]
     jobs.append((640, 480, [synth.hard_frame(k, sd, iw, ih) for k, (sd, iw, ih) in zip(g["kinds"].tolist(), g["params"].tolist()) if iw == 640]))
