@@ -195,23 +195,32 @@ __device__ __forceinline__ unsigned div_small_m(unsigned s, unsigned m) { return
 // rounds 1-3 and most of round 4 staged the tile in LDS and read a pixel's ten samples - five per side, the ones beyond the run from a region of zeros -
 // with a compare and a select per sample: 59 vector instructions per pixel and pass, 70.0 us per launch of 8 frames against 53.4).
 // A window's sum is a difference of two prefix values plus the
-// centre:  sum = P[c + nr] - P[c + 1 - nl] + v[c]  (P[i] = sum of the cells before i; covers nl = 0, nr = 0 and both), and the prefix words are plain 32-bit
+// centre:  sum = P[c + nr] - P[c + 1 - nl] + v[c]  (P[i] = sum of the cells before i; covers nl = 0, nr = 0 and both), and the prefix words are plain 64-bit
 // sums of the expanded cells (L | a << 16, b): whatever a prefix wrapped to or carried between its fields, the DIFFERENCE is the window's own sum, whose
-// fields stay below 2^16 - exact.  That takes the ten selected LDS reads, ten compares, ten selects and ten additions of a pixel down to four reads and six
-// subtractions; what it costs is building the prefixes, which is arranged so that the thread that produces a cell also holds its neighbours along the axis:
-//   horizontal: lanes = the tile's 62 rows, wave s walks columns 9s .. 9s+8 of its row with the sum in registers (row pitch 73: conflict-free), the
-//               segment totals meet in LDS, every thread adds the totals of the segments before its own and writes its nine prefix values in place;
-//   vertical:   lanes = columns, wave w computes the horizontal results of rows 8w .. 8w+7 (from the row prefixes) and sums them on the way; totals and
-//               offsets as before; the column prefixes take the memory the row prefixes had.
-// Tile: 64 x BQ_ROWS outputs (BQ_ROWS + 8 <= 64 rows of the horizontal strip are the lanes of a wave), 512 threads, 40 KB of LDS and 60 registers: four blocks per CU.
+// fields stay below 2^16 - exact, in whatever order the modular additions are made.
+// OWNERSHIP: thread (wave wv, lane tx) owns rows 8 wv + j (j = 0..7; rows >= 62 do not exist) of the staged 62 x 72 strip at frame column x0 + tx (strip column
+// tx + 4), in all three phases.  It loads the cell and the pixel's `ext` word from one pixel index (one `ext` load per pixel: bits 0-5 serve the horizontal,
+// bits 6-11 the vertical pass), computes the pixel's horizontal result and, for strip rows 4..57, its output, which lies at that same pixel index.  So the
+// centre term is never fetched: in the horizontal pass it is the expanded cell the thread staged, in the vertical pass the horizontal result it computed - a
+// result costs two 64-bit LDS reads (the window's two prefix values) and one 32-bit read of the reciprocal table, which is indexed by the six extent bits as
+// they are.  Wave 0 has 4 output rows, wave 7 has 2, the others 8; a store is one 256-byte row segment per wave.  The eight halo columns (strip columns 0..3
+// and 68..71) are one cell per thread for tid < 8 x 62.
+// What the prefixes cost is arranged so that the thread that sums a cell also holds its neighbours along the axis:
+//   horizontal: lanes = the tile's 62 rows, wave s walks columns 9s .. 9s+8 of its row (row pitch 73: conflict-free), the segment totals meet in LDS, every
+//               thread adds the totals of the segments before its own and writes its nine prefix values in place (off; off += v[j]);
+//   vertical:   the owner sums its eight horizontal results on the way; totals and offsets as before; the column prefixes take the memory the row prefixes had.
+// LDS addresses are unsigned byte offsets: one per thread and layout (strip pitch 73, prefix pitch 64) plus immediates.
+// Tile: 64 x BQ_ROWS outputs (BQ_ROWS + 8 <= 64 rows of the horizontal strip are the lanes of a wave), 512 threads, 40 KB of LDS and at most 64 registers: four blocks per CU.
 #ifndef BQ_ROWS
-#define BQ_ROWS 54            // (1080 = 20 x 54)
+#define BQ_ROWS 54            // (1080 = 20 x 54.  A tuning build may choose 49..55: every wave must own strip row 8 wv, so 48-row tiles no longer compile - the assertions below)
 #endif
 #define BQ_HR (BQ_ROWS + 8)   // rows of the staged tile / horizontal strip
 #define BQ_SW 73
 static_assert(BQ_ROWS + 9 <= 64, "the column prefixes have 64 rows: the last output row reads prefix row BQ_ROWS + 8");
+static_assert(BQ_HR > 56, "every wave owns strip row 8 wv: the rows that do not exist (j >= BQ_HR - 56 of wave 7) borrow its addresses");
 #ifndef BQ_WB
-#define BQ_WB 2              // pixels of a thread evaluated together (1 / 2 / 4 / 8: 53.4 / 53.1 / 54.0 / 62.5 us per launch of 8 frames - 8 costs a wave per SIMD)
+#define BQ_WB 1              // pixels of a thread evaluated together, all their LDS reads requested before the first is used (1 / 2 / 4: 3042-3051 / 3017-3038 / 3017-3029 frames/s, profiles/NOTES_blur_pair.md:
+                             // with two reads per pixel instead of four the other waves of the SIMD cover the latency, and batching only costs instructions)
 #endif
 __global__ __launch_bounds__(512) void k_blblur_pair(uint32_t *__restrict__ out, const uint16_t *__restrict__ ext, const uint32_t *__restrict__ in, int iw, int ih, size_t zs, int gdim) {
   const rd_tile rd_b = rd_block_tile(gdim);
@@ -223,75 +232,67 @@ __global__ __launch_bounds__(512) void k_blblur_pair(uint32_t *__restrict__ out,
 #define BQ_PAD 0
 #endif
   __shared__ u64 tot[8 * 64 + BQ_PAD];        // segment totals of the scan in progress
-  __shared__ unsigned rwt[16];
+  __shared__ unsigned rwt[64];                // ceil(2^19 / (nl + nr)) by the six extent bits of an axis (nr << 3 | nl)
   // (the wave's index as a SCALAR: everything that depends on it alone - row numbers, row addresses, "this row does not exist" - stays out of the vector unit)
   const int tx = threadIdx.x, wv = rd_ty(), tid = wv * 64 + tx;
   const int x0 = rd_b.x * 64, y0 = rd_b.y * BQ_ROWS;
-  const int x = x0 + tx;
-  constexpr int NV = (BQ_ROWS + 7) / 8;
-  unsigned eh[8], ev[NV];
-  uint32_t q[9];
-  // staging: wave wv takes rows wv + 8 i of the tile, its lanes columns 0..63; the eight columns left over are a cell per thread (row tid / 8) - no division,
-  // row addresses advance by a scalar.  Run extents of the thread's pixels: rows 8 wv .. 8 wv + 7 of the horizontal strip, rows wv + 8 k of the output tile.
+  const int x = x0 + tx, r0 = 8 * wv;
+  const unsigned pb = (unsigned)((y0 - 4 + r0) * iw + x);       // pixel index of the thread's first strip row: cell, `ext` word and output share it (rows above the frame: never used)
+  unsigned eh[8];
+  uint32_t q[8], qh;
+  // staging: the thread's eight cells and `ext` words, and one halo cell (row tid / 8) - no division, row addresses advance by a scalar.
   // Every load is unconditional (clamped address, value replaced afterwards) and requested before the first is used.
-  const int sr = tid >> 3, sc = 64 + (tid & 7);
+  const int sr = tid >> 3, sc = (tid & 7) + ((tid & 4) << 4);      // halo columns 0..3, 68..71
   const bool interior = x0 >= 4 && y0 >= 4 && x0 + 68 <= iw && y0 + BQ_ROWS + 4 <= ih;
   if (interior) {
-    const unsigned ib = (unsigned)((y0 - 4 + wv) * iw + x0 - 4 + tx);
-#pragma unroll
-    for (int i = 0; i < 8; i++) q[i] = wv + 8 * i < BQ_HR ? atu(in, ib + (unsigned)(8 * i * iw)) : 0u;
-    q[8] = sr < BQ_HR ? atu(in, (unsigned)((y0 - 4) * iw + x0 - 4) + (unsigned)__umul24(sr, iw) + (unsigned)sc) : 0u;
-    const unsigned eb = (unsigned)((y0 - 4 + 8 * wv) * iw + x);
-#pragma unroll
-    for (int j = 0; j < 8; j++) eh[j] = 8 * wv + j < BQ_HR ? (unsigned)atu(ext, eb + (unsigned)(j * iw)) : 0u;
-    const unsigned vb = (unsigned)((y0 + wv) * iw + x);
-#pragma unroll
-    for (int k = 0; k < NV; k++) ev[k] = wv + 8 * k < BQ_ROWS ? (unsigned)atu(ext, vb + (unsigned)(8 * k * iw)) : 0u;
-  } else {
-    bool okq[9], okh[8], okv[NV];
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-      const int r = i < 8 ? wv + 8 * i : sr, c = i < 8 ? tx : sc;
-      const int xx = x0 - 4 + c, yy = y0 - 4 + r;
-      okq[i] = r < BQ_HR && xx >= 0 && xx < iw && yy >= 0 && yy < ih;
-      q[i] = atu(in, okq[i] ? (unsigned)(yy * iw + xx) : 0u);
-    }
 #pragma unroll
     for (int j = 0; j < 8; j++) {
-      const int r = 8 * wv + j, y = y0 - 4 + r;
-      okh[j] = r < BQ_HR && x < iw && y >= 0 && y < ih;
-      eh[j] = atu(ext, okh[j] ? (unsigned)(y * iw + x) : 0u);
+      const unsigned a = pb + (unsigned)((j < BQ_HR - 56 || r0 + j < BQ_HR ? j : 0) * iw);      // (rows 62, 63 of wave 7 do not exist: row 56's address, the values are replaced)
+      q[j] = atu(in, a);
+      eh[j] = atu(ext, a);
     }
+    qh = atu(in, (unsigned)((y0 - 4) * iw + x0 - 4) + (unsigned)__umul24(sr < BQ_HR ? sr : 0, iw) + (unsigned)sc);
 #pragma unroll
-    for (int k = 0; k < NV; k++) {
-      const int r = wv + 8 * k, y = y0 + r;
-      okv[k] = r < BQ_ROWS && x < iw && y < ih;
-      ev[k] = atu(ext, okv[k] ? (unsigned)(y * iw + x) : 0u);
+    for (int j = BQ_HR - 56; j < 8; j++) if (r0 + j >= BQ_HR) { q[j] = 0u; eh[j] = 0u; }
+  } else {
+    bool ok[8];
+    const bool cx = x < iw;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const int r = r0 + j, y = y0 - 4 + r;
+      ok[j] = r < BQ_HR && y >= 0 && y < ih && cx;
+      const unsigned a = ok[j] ? pb + (unsigned)(j * iw) : 0u;
+      q[j] = atu(in, a);
+      eh[j] = atu(ext, a);
     }
+    const int xx = x0 - 4 + sc, yy = y0 - 4 + sr;
+    const bool okq = sr < BQ_HR && xx >= 0 && xx < iw && yy >= 0 && yy < ih;
+    qh = atu(in, okq ? (unsigned)(yy * iw + xx) : 0u);
 #pragma unroll
-    for (int i = 0; i < 9; i++) if (!okq[i]) q[i] = 0u;
-#pragma unroll
-    for (int j = 0; j < 8; j++) if (!okh[j]) eh[j] = 0u;
-#pragma unroll
-    for (int k = 0; k < NV; k++) if (!okv[k]) ev[k] = 0u;
+    for (int j = 0; j < 8; j++) if (!ok[j]) { q[j] = 0u; eh[j] = 0u; }
+    if (!okq) qh = 0u;
   }
-  if (tid < 16) rwt[tid] = tid >= 1 && tid <= 10 ? ((1u << 19) + (unsigned)tid - 1u) / (unsigned)tid : 0u;
+  if (tid < 64) { const unsigned w = (unsigned)((tid & 7) + (tid >> 3)); rwt[tid] = w >= 1 && w <= 10 ? ((1u << 19) + w - 1u) / w : 0u; }
+  char *const plb = (char *)pl;
+  const unsigned hb = (unsigned)((r0 * BQ_SW + tx + 4) * 8);       // byte offset of the thread's cell of strip row r0; row j: + j * BQ_SW * 8
+  u64 cell[8];
 #pragma unroll
-  for (int i = 0; i < 9; i++) {
-    const int r = i < 8 ? wv + 8 * i : sr, c = i < 8 ? tx : sc;
-    const uint32_t v = q[i];
-    if (r < BQ_HR) pl[r * BQ_SW + c] = (u64)((v & 4095u) | ((v << 4) & 0x3ff0000u)) | ((u64)(v >> 22) << 32);
+  for (int j = 0; j < 8; j++) {
+    const uint32_t v = q[j];
+    cell[j] = (u64)((v & 4095u) | ((v << 4) & 0x3ff0000u)) | ((u64)(v >> 22) << 32);
+    if (j < BQ_HR - 56 || r0 + j < BQ_HR) *(u64 *)(plb + hb + (unsigned)(j * BQ_SW * 8)) = cell[j];
   }
+  if (sr < BQ_HR) pl[sr * BQ_SW + sc] = (u64)((qh & 4095u) | ((qh << 4) & 0x3ff0000u)) | ((u64)(qh >> 22) << 32);
   __syncthreads();
   // ---- row prefixes: lane = row, wave = segment of nine columns
   {
-    u64 p[10], v[9], sum = 0;
-    const int b = (tx < BQ_HR ? tx : BQ_HR - 1) * BQ_SW + 9 * wv;
+    u64 v[9];
+    const unsigned b = (unsigned)(((tx < BQ_HR ? tx : BQ_HR - 1) * BQ_SW + 9 * wv) * 8);
 #pragma unroll
-    for (int j = 0; j < 9; j++) v[j] = pl[b + j];
+    for (int j = 0; j < 9; j++) v[j] = *(const u64 *)(plb + b + (unsigned)(8 * j));
+    u64 sum = v[0];
 #pragma unroll
-    for (int j = 0; j < 9; j++) { p[j] = sum; sum += v[j]; }
-    p[9] = sum;
+    for (int j = 1; j < 9; j++) sum += v[j];
     tot[wv * 64 + tx] = sum;
     __syncthreads();
     u64 off = 0, ts[7];
@@ -301,43 +302,40 @@ __global__ __launch_bounds__(512) void k_blblur_pair(uint32_t *__restrict__ out,
     for (int s2 = 0; s2 < 7; s2++) off += ts[s2];
     if (tx < BQ_HR) {      // (lanes 62, 63 have no row)
 #pragma unroll
-      for (int j = 0; j < 9; j++) pl[b + j] = p[j] + off;
-      if (wv == 7) pl[b + 9] = p[9] + off;      // P[72]
+      for (int j = 0; j < 9; j++) { *(u64 *)(plb + b + (unsigned)(8 * j)) = off; off += v[j]; }
+      if (wv == 7) *(u64 *)(plb + b + 72u) = off;      // P[72]
     }
   }
   __syncthreads();
-  // ---- horizontal results of rows 8 wv .. 8 wv + 7 (lane = column), summed down the column on the way
-  // (BQ_WB pixels at a time: all their reads are requested before the first is used.  No pixel of the frame has an empty window - k_blblur_extents turns
-  //  "no run at all" into "the centre alone", which divides to itself; cells outside the frame carry extents 0 and weight 0 and come out as the zeros they are)
-  u64 pv[9];
-  {
-    u64 sum = 0;
+  // ---- horizontal results of the thread's own cells, summed down the column on the way: window = P[c + nr] - P[c + 1 - nl] + the cell in the register
+  // (BQ_WB pixels at a time.  No pixel of the frame has an empty window - k_blblur_extents turns "no run at all" into "the centre alone", which divides to
+  //  itself; cells outside the frame carry extents 0 and weight 0 and come out as the zeros they are; so do rows 62, 63 of wave 7, which read row 56's prefixes)
+  u64 o[8], osum = 0;
 #pragma unroll
-    for (int j0 = 0; j0 < 8; j0 += BQ_WB) {
-      u64 hi[BQ_WB], lo[BQ_WB], c0[BQ_WB], c1[BQ_WB];
-      unsigned rw[BQ_WB];
+  for (int j0 = 0; j0 < 8; j0 += BQ_WB) {
+    u64 hi[BQ_WB], lo[BQ_WB];
+    unsigned rw[BQ_WB];
 #pragma unroll
-      for (int u = 0; u < BQ_WB; u++) {
-        const unsigned e = eh[j0 + u];
-        const int nl = e & 7, nr = (e >> 3) & 7;
-        const int c = (8 * wv + j0 + u < BQ_HR ? 8 * wv + j0 + u : BQ_HR - 1) * BQ_SW + tx + 4;      // (rows 62, 63 of wave 7 do not exist: any address, the result is dropped)
-        hi[u] = pl[c + nr]; lo[u] = pl[c + 1 - nl]; c0[u] = pl[c]; c1[u] = pl[c + 1];
-        rw[u] = rwt[nl + nr];
-      }
-#pragma unroll
-      for (int u = 0; u < BQ_WB; u++) {
-        const u64 a = (hi[u] + c1[u]) - (lo[u] + c0[u]);
-        const unsigned ax = (unsigned)a, ay = (unsigned)(a >> 32);
-        u64 o = (u64)(div_small_m(ax & 0xffffu, rw[u]) | (div_small_m(ax >> 16, rw[u]) << 16)) | ((u64)div_small_m(ay, rw[u]) << 32);
-        if (8 * wv + j0 + u >= BQ_HR) o = 0;
-        pv[j0 + u] = sum;
-        sum += o;
-      }
+    for (int u = 0; u < BQ_WB; u++) {
+      const int j = j0 + u;
+      const unsigned e = eh[j];
+      const unsigned c = hb + (unsigned)((j < BQ_HR - 56 || r0 + j < BQ_HR ? j : 0) * BQ_SW * 8);
+      hi[u] = *(const u64 *)(plb + c + (e & 0x38u));                       // nr cells on
+      lo[u] = *(const u64 *)(plb + c + 8u - ((e & 7u) << 3));              // 1 - nl cells on
+      rw[u] = *(const unsigned *)((const char *)rwt + ((e & 63u) << 2));
     }
-    pv[8] = sum;
+#pragma unroll
+    for (int u = 0; u < BQ_WB; u++) {
+      const int j = j0 + u;
+      const u64 a = hi[u] - lo[u] + cell[j];
+      const unsigned ax = (unsigned)a, ay = (unsigned)(a >> 32);
+      o[j] = (u64)(div_small_m(ax & 0xffffu, rw[u]) | (div_small_m(ax >> 16, rw[u]) << 16)) | ((u64)div_small_m(ay, rw[u]) << 32);
+      osum += o[j];
+    }
   }
-  tot[wv * 64 + tx] = pv[8];       // (the totals of the row scan were last read before the barrier above)
+  tot[wv * 64 + tx] = osum;        // (the totals of the row scan were last read before the barrier above)
   __syncthreads();                 // (every read of the row prefixes is done as well: their memory takes the column prefixes)
+  const unsigned vb = (unsigned)((r0 * 64 + tx) * 8);      // byte offset of the thread's column prefix of strip row r0; row j: + j * 512
   {
     u64 off = 0, ts[7];
 #pragma unroll
@@ -345,32 +343,32 @@ __global__ __launch_bounds__(512) void k_blblur_pair(uint32_t *__restrict__ out,
 #pragma unroll
     for (int s2 = 0; s2 < 7; s2++) off += ts[s2];
 #pragma unroll
-    for (int j = 0; j < 8; j++) pl[(8 * wv + j) * 64 + tx] = pv[j] + off;
+    for (int j = 0; j < 8; j++) { *(u64 *)(plb + vb + (unsigned)(j * 512)) = off; off += o[j]; }
   }
   __syncthreads();
   if (x >= iw) return;
+  // ---- outputs: strip rows 4 .. BQ_ROWS + 3 inside the frame (a scalar test); window = P[r + nr] - P[r + 1 - nl] + the horizontal result in the register
 #pragma unroll
-  for (int k0 = 0; k0 < NV; k0 += BQ_WB) {
-    u64 hi[BQ_WB], lo[BQ_WB], c0[BQ_WB], c1[BQ_WB];
+  for (int j0 = 0; j0 < 8; j0 += BQ_WB) {
+    u64 hi[BQ_WB], lo[BQ_WB];
     unsigned rw[BQ_WB];
 #pragma unroll
     for (int u = 0; u < BQ_WB; u++) {
-      if (k0 + u >= NV) continue;
-      const unsigned e = ev[k0 + u] >> 6;
-      const int nl = e & 7, nr = (e >> 3) & 7;
-      const int r = wv + 8 * (k0 + u);
-      const int c = ((r < BQ_ROWS ? r : 0) + 4) * 64 + tx;
-      hi[u] = pl[c + nr * 64]; lo[u] = pl[c + (1 - nl) * 64]; c0[u] = pl[c]; c1[u] = pl[c + 64];
-      rw[u] = rwt[nl + nr];
+      const int j = j0 + u, r = r0 + j;
+      if (r < 4 || r >= BQ_ROWS + 4 || y0 - 4 + r >= ih) continue;
+      const unsigned e = eh[j];
+      const unsigned c = vb + (unsigned)(j * 512);
+      hi[u] = *(const u64 *)(plb + c + (e & 0xe00u));                      // nr rows on (bits 9-11 are nr * 512 as they stand)
+      lo[u] = *(const u64 *)(plb + c + 512u - ((e & 0x1c0u) << 3));        // 1 - nl rows on
+      rw[u] = *(const unsigned *)((const char *)rwt + ((e >> 4) & 0xfcu));
     }
 #pragma unroll
     for (int u = 0; u < BQ_WB; u++) {
-      if (k0 + u >= NV) continue;
-      const int r = wv + 8 * (k0 + u);
-      const int y = y0 + r;
-      const u64 a = (hi[u] + c1[u]) - (lo[u] + c0[u]);
+      const int j = j0 + u, r = r0 + j;
+      if (r < 4 || r >= BQ_ROWS + 4 || y0 - 4 + r >= ih) continue;
+      const u64 a = hi[u] - lo[u] + o[j];
       const unsigned ax = (unsigned)a, ay = (unsigned)(a >> 32);
-      if (r < BQ_ROWS && y < ih) atu(out, (unsigned)(y * iw + x)) = div_small_m(ax & 0xffffu, rw[u]) | (div_small_m(ax >> 16, rw[u]) << 12) | (div_small_m(ay, rw[u]) << 22);
+      atu(out, pb + (unsigned)(j * iw)) = div_small_m(ax & 0xffffu, rw[u]) | (div_small_m(ax >> 16, rw[u]) << 12) | (div_small_m(ay, rw[u]) << 22);
     }
   }
 }
