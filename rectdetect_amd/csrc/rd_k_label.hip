@@ -17,16 +17,26 @@ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 const dim3 block2(64, 4);
 inline dim3 grid2(int iw, int ih) { return dim3(cdiv(iw, 64), cdiv(ih, 4)); }
 
-// Phase 1 (one block per 64x32 tile, everything in LDS): runs inside each 64-pixel row segment (ballot of run starts +
-// count-leading-zeros), unions between the rows of the tile, path compression; the tile's pixels leave pointing at the
+// Phase 1 (one block per 64x32 tile): wave w owns the tile's rows RW w .. RW w + RW - 1 (RW = LT_H / TY = 8), lane tx holds its column's RW values in
+// registers.  Runs inside each 64-pixel row segment (ballot of run starts + count-leading-zeros); the neighbour tests of the unions between rows take N from
+// the thread's own registers and W, E, NW, NE - values and run starts - from the neighbouring lanes by DPP wave shifts; a wave's first row meets the row
+// above through one published row (values and run starts) per wave.  Only the labels live in LDS: a run's pixels point at its first pixel, the unions hook
+// roots with atomicMin, and the thread's final walks to the roots take their steps together.  The tile's pixels leave pointing at the
 // GLOBAL index of their tile-local root, which is the smallest index of the component's part inside the tile.
 #define LT_W 64
 #ifndef LT_H
 #define LT_H 32
 #endif
+#define LT_NIL (LT_W * LT_H)      // one word behind the tile's labels that points at itself: where a walk without work rests (its loads are unconditional)
 // (the walks re-read words other lanes lower meanwhile: relaxed atomic loads, workgroup scope - LDS reads as ds_read.  A `volatile` pointer instead loses its
 //  address space: every step of every walk was a FLAT load with system-scope bits, several times the latency of the LDS instruction)
 __device__ __forceinline__ int lt_ld(const int *lab, int a) { return __hip_atomic_load(lab + a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+// lane i takes lane i - 1's / lane i + 1's word (DPP wave shifts, no LDS); lane 0 / lane 63 keep their own: callers test the lane first
+__device__ __forceinline__ int lt_west(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x138, 0xf, 0xf, false); }
+__device__ __forceinline__ int lt_east(int v) { return __builtin_amdgcn_update_dpp(v, v, 0x130, 0xf, 0xf, false); }
+// (a union starts at the first pixels of the two runs - the thread knows them without a read - and takes one find after the other, inside a branch only the lanes with work
+//  enter.  Measured against it on the 1920x1080 stream and not kept: both finds of a union in step, the unions of 1, 2, 4 or 8 rows of the thread in step, hooking
+//  without walking - profiles/NOTES_label_tile.md: with six waves per SIMD the kernel is bound by the instructions it issues, not by the latency of a chain.)
 __device__ __forceinline__ int lt_find(const int *lab, int a) {
   int l = lt_ld(lab, a);
   while (l != a) { a = l; l = lt_ld(lab, a); }
@@ -43,66 +53,85 @@ __device__ __forceinline__ void lt_union(int *lab, int a, int b) {
     a = old;
   }
 }
+// The unions a pixel issues against the row above: only where no pixel of its run is guaranteed to issue an equivalent one (same case analysis as
+// k_label_border below).  v, vW, vE: the pixel and its neighbours in the row; vP, vPW, vPE: N, NW, NE; sP, sPW, sPE: their runs' first pixels; wok / eok: a W / an E
+// column exists in the tile and the frame.  act = inside the frame and not background: a neighbour of equal value is then inside and not background either.
+// pA: the run to unite with through N or NW, pB: through NE; LT_NIL = none.
+__device__ __forceinline__ void lt_pairs(bool act, bool wok, bool eok, int v, int vW, int vE, int vP, int vPW, int vPE, int sP, int sPW, int sPE, int &pA, int &pB) {
+  const bool wSame = wok && vW == v, eSame = eok && vE == v, nSame = vP == v, nwSame = wok && vPW == v, neSame = eok && vPE == v;
+  const bool goA = act && (nSame ? !(wSame && nwSame) : (nwSame && !wSame));
+  pA = goA ? (nSame ? sP : sPW) : LT_NIL;
+  pB = (act && !nSame && neSame && !eSame) ? sPE : LT_NIL;
+}
 
 #ifndef LT_TY
 #define LT_TY 4
 #endif
 #ifndef LT_TY1
-#define LT_TY1 LT_TY      // thread rows of the boundary variant (the tidy variant's tile code is written for four waves)
+#define LT_TY1 LT_TY      // waves of the boundary variant (the tidy variant's tile code is written for four waves)
 #endif
-// LT_TY: thread rows per block (16 is ~20% faster run alone, but costs 50% more wave-cycles: worse with frames in flight)
+// LT_TY: waves per block, each with a strip of LT_H / LT_TY rows (with rows dealt out one by one, 16 waves were ~20% faster run alone but cost 50% more
+// wave-cycles: worse with frames in flight)
 #define LT_MP 68      // row pitch of the staged region tile of the boundary variant (64 + 2 x 2 cells of halo)
-// BOUNDARY = false: the pixel values are read from `pix`.  BOUNDARY = true: they are the region-boundary marks of oclrect.cl:373-390,
+// SRC == 0: the pixel values are read from `pix`.  SRC == 1 (BOUNDARY): they are the region-boundary marks of oclrect.cl:373-390,
 // computed here from the region plane `src` (a pixel of the interior whose 5x5 window holds another label carries its own label,
 // every other pixel -1; evaluated separably like this: hu = "the five cells x-2..x+2 of a row equal the one at x", window uniform
-// iff the five cells of the centre column equal the centre and their rows are uniform) and also written to `pix_out` for the
+// iff the five cells of the centre column equal the centre and their rows are uniform; the five-row window slides down the thread's
+// column, every staged cell read once per thread) and also written to `pix_out` for the
 // border kernel - one launch and one pass over the plane less than marking first and labelling then.
 // SRC == 2: the pixel values are the rect-variant edge tidy of the NMS response `nms` (rd_tidy_tile.h), computed here and written to
-// mask0 / pix_out (and zero_plane cleared) as k_rect_tidy would.
+// mask0 / pix_out (and zero_plane cleared) as k_rect_tidy would.  SRC == 3: the poly kind's mask, see below.
 template <int SRC, int TY>
 __global__ __launch_bounds__(64 * TY) void k_label_tile(int *__restrict__ label, const int *__restrict__ pix, int bgc, int iw, int ih, int *__restrict__ pix_out,
                                                     const float *__restrict__ nms, int *__restrict__ mask0, int *__restrict__ zero_plane, size_t zs, int gdim) {
   constexpr bool BOUNDARY = SRC == 1;
+  constexpr int RW = LT_H / TY;                                      // rows of a wave's strip
+  static_assert(RW * TY == LT_H, "whole strips");
   const rd_tile rd_b = rd_block_tile(gdim);
   if (rd_b.x < 0) return;
   RD_ZSHIFTZ(rd_b.z, zs, label, pix, pix_out, nms, mask0, zero_plane);
-  __shared__ int lab[LT_W * LT_H];
-  __shared__ int pv[LT_W * LT_H];
-  const int tx = threadIdx.x, x = rd_b.x * LT_W + tx, y0 = rd_b.y * LT_H;
+  __shared__ int lab[LT_W * LT_H + 1];
+  __shared__ int s_pv[TY * LT_W], s_st[TY * LT_W];      // the last row of every wave's strip for the wave below: values, first pixels of the runs
+  const int tx = threadIdx.x, wv = rd_ty(), x = rd_b.x * LT_W + tx, y0 = rd_b.y * LT_H, r0 = wv * RW;
   const bool xin = x < iw;
   int v00;
   bool uniform = true;
-  int pv8[LT_H / TY];            // this thread's pixels, requested together (one wait for memory instead of one per row)
+  int pv8[RW];            // this thread's pixels, requested together (one wait for memory instead of one per row)
   if constexpr (SRC == 2) {
     __shared__ __align__(16) uint8_t A[(LT_H + 2 * TD_M) * TD_P], B[(LT_H + 2 * TD_M) * TD_P];
-    rect_tidy_tile<LT_H>(A, B, rd_b.x * LT_W, y0, threadIdx.y * 64 + tx, nms, mask0, pix_out, zero_plane, iw, ih, pv8);
+    static_assert(TY == 4, "rect_tidy_tile: four waves");
+    rect_tidy_tile<LT_H>(A, B, rd_b.x * LT_W, y0, wv * 64 + tx, nms, mask0, pix_out, zero_plane, iw, ih, pv8);
     __shared__ int s_t00;            // the value of the tile's first pixel, for the uniform-tile test below
-    if (threadIdx.y == 0 && tx == 0) s_t00 = pv8[0];
+    if (wv == 0 && tx == 0) s_t00 = pv8[0];
     __syncthreads();
     v00 = s_t00;
   } else if constexpr (SRC == 3) {
     // the poly kind's mask (poly.cpp:115-116: threshold_f_f(0, 0, 1) + cast_i_f) straight from the suppressed response, no tidy; written to pix_out for the
     // border kernel, and the strength sums (zero_plane) cleared on the way (poly.cpp:118)
+    float e[RW];
 #pragma unroll
-    for (int k = 0; k < LT_H / TY; k++) {
-      const int y = y0 + threadIdx.y + k * TY;
-      const bool in = xin && y < ih;
-      const float e = nms[in ? y * iw + x : 0];
-      pv8[k] = e > 0.0f ? 1 : 0;
-      if (in) { pix_out[y * iw + x] = pv8[k]; zero_plane[y * iw + x] = 0; }
+    for (int k = 0; k < RW; k++) {
+      const int y = y0 + r0 + k;
+      e[k] = nms[(xin && y < ih) ? y * iw + x : 0];
+    }
+#pragma unroll
+    for (int k = 0; k < RW; k++) {
+      const int y = y0 + r0 + k;
+      pv8[k] = e[k] > 0.0f ? 1 : 0;
+      if (xin && y < ih) { pix_out[y * iw + x] = pv8[k]; zero_plane[y * iw + x] = 0; }
     }
     v00 = nms[(size_t)y0 * iw + rd_b.x * LT_W] > 0.0f ? 1 : 0;   // the tile's first pixel is always inside the frame
   } else if constexpr (!BOUNDARY) {
     v00 = pix[(size_t)y0 * iw + rd_b.x * LT_W];   // the tile's first pixel is always inside the frame
 #pragma unroll
-    for (int k = 0; k < LT_H / TY; k++) {
-      const int y = y0 + threadIdx.y + k * TY;
+    for (int k = 0; k < RW; k++) {
+      const int y = y0 + r0 + k;
       pv8[k] = pix[(xin && y < ih) ? y * iw + x : 0];
     }
   } else {
     __shared__ int t[(LT_H + 4) * LT_MP];
     __shared__ uint8_t hu[(LT_H + 4) * 64];
-    const int x0 = rd_b.x * LT_W, tid = threadIdx.y * 64 + tx;
+    const int x0 = rd_b.x * LT_W, tid = wv * 64 + tx;
     const int r00 = pix[(size_t)y0 * iw + x0];
     bool flat = true;
     {
@@ -116,7 +145,7 @@ __global__ __launch_bounds__(64 * TY) void k_label_tile(int *__restrict__ label,
       const bool cok = xl >= 0 && xl < iw;
 #pragma unroll
       for (int i = 0; i < NR; i++) {
-        const int r = threadIdx.y + TY * i, yy = y0 - 2 + r;
+        const int r = wv + TY * i, yy = y0 - 2 + r;
         ok[i] = r < LT_H + 4 && cok && yy >= 0 && yy < ih;
         v[i] = pix[ok[i] ? yy * iw + xl : 0];
       }
@@ -128,7 +157,7 @@ __global__ __launch_bounds__(64 * TY) void k_label_tile(int *__restrict__ label,
       }
 #pragma unroll
       for (int i = 0; i < NR; i++) {
-        const int r = threadIdx.y + TY * i;
+        const int r = wv + TY * i;
         if (r < LT_H + 4) { flat = flat && (!ok[i] || v[i] == r00); t[r * LT_MP + tx] = ok[i] ? v[i] : 0; }
       }
       if (sr < LT_H + 4) { flat = flat && (!ok[NR] || v[NR] == r00); t[sr * LT_MP + sc] = ok[NR] ? v[NR] : 0; }
@@ -136,95 +165,110 @@ __global__ __launch_bounds__(64 * TY) void k_label_tile(int *__restrict__ label,
     if (__syncthreads_and(flat)) {
       // no differing cell anywhere in reach: nothing is a boundary pixel, nothing to label
 #pragma unroll
-      for (int k = 0; k < LT_H / TY; k++) {
-        const int y = y0 + threadIdx.y + k * TY;
+      for (int k = 0; k < RW; k++) {
+        const int y = y0 + r0 + k;
         if (xin && y < ih) { pix_out[y * iw + x] = -1; label[y * iw + x] = -1; }
       }
       return;
     }
-    for (int r = threadIdx.y; r < LT_H + 4; r += TY) {
+    for (int r = wv; r < LT_H + 4; r += TY) {
       const int *row = t + r * LT_MP + tx + 2;
       const int c = row[0];
       hu[r * 64 + tx] = (row[-2] == c && row[-1] == c && row[1] == c && row[2] == c) ? 1 : 0;
     }
     __syncthreads();
+    // the thread's column of the staged tile, rows r0 .. r0 + RW + 3 (staged row i = tile row i - 2): each cell and each row flag once
+    int cc[RW + 4];
+    bool hh[RW + 4];
 #pragma unroll
-    for (int k = 0; k < LT_H / TY; k++) {
-      const int r = threadIdx.y + k * TY;
-      const int y = y0 + r;
+    for (int i = 0; i < RW + 4; i++) { cc[i] = t[(r0 + i) * LT_MP + tx + 2]; hh[i] = hu[(r0 + i) * 64 + tx] != 0; }
+#pragma unroll
+    for (int k = 0; k < RW; k++) {
+      const int y = y0 + r0 + k;
       int res = -1;
-      if (xin && y < ih && x > 1 && y > 1 && x < iw - 2 && y < ih - 2) {
-        const int c0 = t[(r + 2) * LT_MP + tx + 2];
-        bool same = true;
+      const int c0 = cc[k + 2];
+      bool same = true;
 #pragma unroll
-        for (int dy = 0; dy < 5; dy++) same = same && t[(r + dy) * LT_MP + tx + 2] == c0 && hu[(r + dy) * 64 + tx] != 0;
-        if (!same) res = c0;
-      }
+      for (int dy = 0; dy < 5; dy++) same = same && cc[k + dy] == c0 && hh[k + dy];
+      if (xin && y < ih && x > 1 && y > 1 && x < iw - 2 && y < ih - 2 && !same) res = c0;
       pv8[k] = res;
       if (xin && y < ih) pix_out[y * iw + x] = res;
     }
     __shared__ int s_v00;            // the mark of the tile's first pixel, for the uniform-tile test below
-    if (threadIdx.y == 0 && tx == 0) s_v00 = pv8[0];
+    if (wv == 0 && tx == 0) s_v00 = pv8[0];
     __syncthreads();
     v00 = s_v00;
   }
+  // runs, labels and - for the rows whose row above is the thread's own - the candidate unions, all from registers and the neighbouring lanes
+  const bool wok = tx > 0, eok = tx < LT_W - 1 && x + 1 < iw;
+  int st[RW], pA[RW], pB[RW];      // first pixel of the pixel's run (tile-local index; LT_NIL: outside the frame or background), the runs to unite with
+  int v0 = 0, v0W = 0, v0E = 0;    // the strip's first row, for its unions with the strip above
+  int vP = 0, vPW = 0, vPE = 0, sP = LT_NIL, sPW = LT_NIL, sPE = LT_NIL;
 #pragma unroll
-  for (int k = 0; k < LT_H / TY; k++) {
-    const int r = threadIdx.y + k * TY;
+  for (int k = 0; k < RW; k++) {
+    const int r = r0 + k;
     const int y = y0 + r;
     const bool valid = xin && y < ih;
     const int v = valid ? pv8[k] : 0;
     uniform = uniform && (!valid || v == v00);
-    const int vl = __shfl_up(v, 1);
-    const bool lvalid = __shfl_up((int)valid, 1) != 0;
-    const bool same = valid && tx > 0 && lvalid && vl == v;
+    const int vW = lt_west(v), vE = lt_east(v);
+    const bool same = valid && wok && vW == v;      // (the pixel left of one inside the frame is inside)
     const unsigned long long starts = __ballot(!same);
     const unsigned long long upto = starts & ((2ull << tx) - 1ull);
     const int start = 63 - __clzll((long long)upto);
-    pv[r * LT_W + tx] = v;
-    lab[r * LT_W + tx] = (!valid || v == bgc) ? -1 : r * LT_W + start;
+    const bool act = valid && v != bgc;
+    const int s = act ? r * LT_W + start : LT_NIL;
+    lab[r * LT_W + tx] = act ? s : -1;
+    st[k] = s;
+    const int sW = lt_west(s), sE = lt_east(s);
+    if (k == 0) { v0 = v; v0W = vW; v0E = vE; }
+    else lt_pairs(act, wok, eok, v, vW, vE, vP, vPW, vPE, sP, sPW, sPE, pA[k], pB[k]);
+    vP = v; vPW = vW; vPE = vE; sP = s; sPW = sW; sPE = sE;
   }
+  s_pv[wv * LT_W + tx] = vP;
+  s_st[wv * LT_W + tx] = sP;
+  if (wv == 0 && tx == 0) lab[LT_NIL] = LT_NIL;
   // fast path: the whole tile holds one value (background, the inside of a large component): one component, no unions
   {
     if (__syncthreads_and(uniform)) {
       const int l = v00 == bgc ? -1 : y0 * iw + rd_b.x * LT_W;
 #pragma unroll
-      for (int r = threadIdx.y; r < LT_H; r += TY) {
-        const int y = y0 + r;
+      for (int k = 0; k < RW; k++) {
+        const int y = y0 + r0 + k;
         if (xin && y < ih) label[y * iw + x] = l;
       }
       return;
     }
   }
-  // unions with the row above, inside the tile; a pixel only issues one when no pixel of its run is guaranteed to issue
-  // an equivalent one (same case analysis as k_label_border below)
+  // the strip's first row against the last row of the strip above
+  if (wv > 0) {
+    vP = s_pv[(wv - 1) * LT_W + tx];
+    sP = s_st[(wv - 1) * LT_W + tx];
+    lt_pairs(st[0] != LT_NIL, wok, eok, v0, v0W, v0E, vP, lt_west(vP), lt_east(vP), sP, lt_west(sP), lt_east(sP), pA[0], pB[0]);
+  } else { pA[0] = LT_NIL; pB[0] = LT_NIL; }
+  // unions with the row above, inside the tile, the strip's rows from top to bottom
 #pragma unroll
-  for (int r = threadIdx.y; r < LT_H; r += TY) {
-    if (r == 0) continue;
-    const int q = r * LT_W + tx;
-    if (lab[q] < 0) continue;
-    const int v = pv[q];
-    const bool wSame = tx > 0 && lab[q - 1] >= 0 && pv[q - 1] == v;
-    const bool nSame = lab[q - LT_W] >= 0 && pv[q - LT_W] == v;
-    const bool nwSame = tx > 0 && lab[q - LT_W - 1] >= 0 && pv[q - LT_W - 1] == v;
-    if (nSame) {
-      if (!(wSame && nwSame)) lt_union(lab, q, q - LT_W);
-    } else {
-      const bool neSame = tx < LT_W - 1 && lab[q - LT_W + 1] >= 0 && pv[q - LT_W + 1] == v;
-      const bool eSame = tx < LT_W - 1 && lab[q + 1] >= 0 && pv[q + 1] == v;
-      if (nwSame && !wSame) lt_union(lab, q, q - LT_W - 1);
-      if (neSame && !eSame) lt_union(lab, q, q - LT_W + 1);
-    }
+  for (int k = 0; k < RW; k++) {
+    if (pA[k] != LT_NIL) lt_union(lab, st[k], pA[k]);
+    if (pB[k] != LT_NIL) lt_union(lab, st[k], pB[k]);
   }
   __syncthreads();
+  // the thread's RW walks to the roots level by level (unconditional loads: a walk that has arrived re-reads its root, one without a pixel rests at LT_NIL)
+  int rt[RW], nx[RW];
 #pragma unroll
-  for (int r = threadIdx.y; r < LT_H; r += TY) {
-    const int y = y0 + r;
-    if (!xin || y >= ih) continue;
-    const int q = r * LT_W + tx;
-    int l = lab[q];
-    if (l >= 0) { l = lt_find(lab, l); l = (y0 + l / LT_W) * iw + rd_b.x * LT_W + l % LT_W; }
-    label[y * iw + x] = l;
+  for (int k = 0; k < RW; k++) { rt[k] = st[k]; nx[k] = lt_ld(lab, rt[k]); }
+  for (;;) {
+    bool moving = false;
+#pragma unroll
+    for (int k = 0; k < RW; k++) moving = moving || nx[k] != rt[k];
+    if (!moving) break;
+#pragma unroll
+    for (int k = 0; k < RW; k++) { rt[k] = nx[k]; nx[k] = lt_ld(lab, rt[k]); }
+  }
+#pragma unroll
+  for (int k = 0; k < RW; k++) {
+    const int y = y0 + r0 + k;
+    if (xin && y < ih) label[y * iw + x] = st[k] == LT_NIL ? -1 : (y0 + rt[k] / LT_W) * iw + rd_b.x * LT_W + rt[k] % LT_W;
   }
 }
 

@@ -37,7 +37,7 @@ __device__ __forceinline__ void br_count8(bitrow u, bitrow m, bitrow d, bitrow &
 // 64 x ROWS tile: the four stencils need 4 cells of margin in total.
 // Block of 256 threads (64 x 4), tid = ty * 64 + tx.  A, B: (ROWS + 8) * 72 bytes of LDS each, 16-byte aligned (they hold three bit
 // planes each).  The results of the tile's own pixels are stored to mask0 (if given) / tidy (and zero_plane cleared, if given) and returned in
-// outv[j] for row ty + 4 j, column tx (0 for pixels outside the frame).
+// outv[j] for row (ROWS / 4) ty + j, column tx (0 for pixels outside the frame): a wave hands out a strip of consecutive rows, a lane its column of the strip.
 #define TD_M 4
 #define TD_P (64 + 2 * TD_M)
 template <int ROWS>
@@ -118,7 +118,7 @@ __device__ __forceinline__ void rect_tidy_tile(uint8_t *A, uint8_t *B, int x0, i
   const int tx = lane, x = x0 + tx;
 #pragma unroll
   for (int j = 0; j < ROWS / 4; j++) {
-    const int tr = w + 4 * j, yy = y0 + tr;
+    const int tr = (ROWS / 4) * w + j, yy = y0 + tr;
     int v = 0;
     if (x < iw && yy < ih) {
       v = br_bit(T1[tr + TD_M], tx + TD_M);
