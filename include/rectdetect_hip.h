@@ -165,9 +165,13 @@ long rd_detector_counter(rd_detector *d, int which);
  * Switches of experiments that were measured and not kept exist only in tuning builds (-DRD_TUNING, tools/variants.sh). */
 
 /* Test hook: copy an internal plane of the most recently completed frame to host memory.  Returns bytes written,
- * 0 for an unknown name.  Names: plab0 plab1 lblur vxy strength nms mask0 tidy label1 strsum edge500 smooth quant
- * strong junction mergemask region0 (merged regions) rsize region (after absorbing small ones) boundarysrc boundary lsid table;
- * polyline kind: plab0 lblur nms mask0 (nms > 0) label1 (its components) strsum polymask (the traced mask, poly.cpp:121) lslist lsid polyctr */
+ * 0 for an unknown name or a name of the other kind.  Both kinds are served from one table (rd_api.hip).
+ * Rectangle kind: plab0 plab1 lblur vxy strength nms mask0 tidy label1 strsum edge500 smooth quant strong junction mergemask
+ * region0 (merged regions) rsize region (after absorbing small ones) boundarysrc boundary lsid table lslist (the segment list, 16 bytes per pixel)
+ * polyctr (64 counters of the polyline stage) iirflags (16 ints) d2work (16 ints) absorb (8 status words of the absorption);
+ * polyline kind: plab0 lblur nms mask0 (nms > 0) label1 (its components) strsum polymask (the traced mask, poly.cpp:121) lslist lsid polyctr.
+ * A shorter buffer gets the first max_bytes bytes; of the planes kept in another shape on the device and handed out as ints (mask0 of the rectangle kind,
+ * edge500, strong, junction, mergemask, polymask) the first max_bytes / 4 elements. */
 size_t rd_detector_debug_plane(rd_detector *d, const char *name, void *dst, size_t max_bytes);
 
 /* ---- host post-process alone (oclrect.c:1049-1226 restated): segments + samples -> rectangles.  Used by tests to

@@ -310,7 +310,7 @@ struct Slot {
   unsigned long long *mmbits;             // the merge mask (oclrect.c:315-321) as a bit plane
   unsigned long long *strongbits;         // this frame's strong mask as a bit plane (ceil(iw / 64) words per row): what the polyline stage traces
   uint16_t *ext;
-  float *tails; int *flags; int iir_chunked;
+  float *tails; int *flags;
   void *lslist;
   rdk::PolyScratch *ps;
   rdk::PolyFrame *frame;                  // this slot's descriptor for the sparse stages (element `slot index` of the detector's array)
@@ -362,7 +362,7 @@ struct rd_detector {
   Slot *slots;
   int nstreams;
   int zb;                 // frames per launch of the DENSE stages as well (groups of zb consecutive slots, frame = blockIdx.z): small frames, whose launches do not fill the device
-  char *arena; size_t slot_pitch;      // zb > 1: all slots' planes in one allocation, slot k at arena + k * slot_pitch
+  char *arena; size_t slot_pitch;      // all slots' planes in one allocation, slot k at arena + k * slot_pitch (kSlotPlanes; rd_detector_counter 31: the pitch)
   // strong-edge masks of the last frames (reference quirk H1: a frame's strength sums start from the mask of the frame before), one byte per
   // pixel: a ring of nslots + 1 planes - frame t reads plane t mod (nslots + 1) and writes the next one, so what a frame read stays intact as
   // long as its slot's planes do (debug plane "strsum")
@@ -400,68 +400,67 @@ struct rd_detector {
   int p_thre, p_size; float p_minerror;     // filterStrength threshold, sizeThre, minerror
   int handoff_rec;           // records (header included) each slot's pinned block receives at the end of a frame (RD_POLY_HANDOFF)
   long n_long_lists;         // frames whose list did not fit that block and was fetched by the poll (rd_detector_counter 30)
-  size_t slot_bytes;         // device bytes of one slot's planes (rd_detector_counter 31; evaluated on first request)
 };
 #define RD_KIND_RECT 0
 #define RD_KIND_POLY 1
 #define RD_POLY_HANDOFF_DEFAULT 2048      // records handed off per frame: 112 KB of pinned memory per slot
 
-// The device planes of a slot.  With frames batched per launch (rd_detector::zb > 1) every slot's planes are carved out of one allocation at
-// the same offsets, so that the planes of slot k + z lie a constant number of bytes (the slot pitch) behind those of slot k: a kernel of a
-// group launch reaches frame z's planes as `pointer + blockIdx.z * pitch`.  Otherwise every plane is an allocation of its own.
-struct PlaneAlloc {
-  char *base; size_t at; int mode;       // mode 0: hipMalloc per plane; 1: carve from base; 2: count bytes only
-  template <typename T> T *get(size_t n) {
-    if (mode == 0) return dnew<T>(n);
-    const size_t bytes = (((n ? n : 1) * sizeof(T)) + 255) & ~(size_t)255;
-    T *p = mode == 1 ? (T *)(base + at) : (T *)nullptr;
-    at += bytes;
-    return p;
-  }
-  bool real() const { return mode != 2; }
+// The device planes of a slot: the one list of them, both kinds, in layout order.  Every detector carves its slots out of one allocation (rd_detector::arena): slot k
+// at arena + k * slot_pitch, its planes in the order of the rows its kind owns, each rounded up to 256 bytes.  The planes of slot k + z then lie a constant number
+// of bytes behind those of slot k - a kernel of a group launch reaches frame z's planes as `pointer + blockIdx.z * pitch` - and a frame that is launched on its own
+// runs on the layout the groups use: a kernel that runs past its plane lands in the neighbouring plane in every configuration.
+// Offsets, the slot's size and the Slot's pointers all come from one walk of this list (slot_planes); nothing else names the planes.
+#define PK_RECT 1
+#define PK_POLY 2
+#define PK_POLY_UNFUSED 4      // the polyline kind at frame sizes the fused front kernel's tiles do not cover (!front_is_fused): the three operators need their planes
+#define PK_BOTH (PK_RECT | PK_POLY)
+typedef size_t PlaneCount(const rd_detector *d);      // elements of a plane
+static size_t pn_n(const rd_detector *d) { return (size_t)d->N; }
+static size_t pn_2n(const rd_detector *d) { return (size_t)d->N * 2; }
+static size_t pn_4n(const rd_detector *d) { return (size_t)d->N * 4; }
+static size_t pn_16n(const rd_detector *d) { return (size_t)d->N * 16; }
+static size_t pn_scratch2(const rd_detector *d) { return (size_t)d->N * 3 + 256; }      // region_merge: the initial forest, flags + allow bytes, the second label plane of the rounds
+static size_t pn_d2(const rd_detector *d) { return RD_D2_SCRATCH_INTS(d->N); }
+static size_t pn_bits(const rd_detector *d) { return (size_t)((d->iw + 63) / 64) * d->ih + 8; }      // a bit plane: ceil(iw / 64) words per row
+static size_t pn_tails(const rd_detector *d) { const size_t a = rdk::iir_pass_scratch_floats(3, d->ih, d->iw), b = rdk::iir_pass_scratch_floats(3, d->iw, d->ih); return a > b ? a : b; }
+static size_t pn_flags(const rd_detector *) { return 16; }
+static size_t pn_probes(const rd_detector *d) { return (size_t)d->maxrec_dev * 15 * 6; }
+#define PLANE(field, count, kinds) { offsetof(Slot, field), sizeof(*((Slot *)0)->field), count, kinds }
+#define BLUR_PLANES(k) PLANE(tr[k], pn_n, PK_BOTH), PLANE(fw[k], pn_n, PK_BOTH), PLANE(bw[k], pn_n, PK_BOTH), PLANE(hz[k], pn_n, PK_BOTH), PLANE(bl[k], pn_n, PK_BOTH)
+static const struct { size_t field, elem; PlaneCount *count; int kinds; } kSlotPlanes[] = {
+  PLANE(bgr, pn_4n, PK_BOTH),
+  PLANE(plab0, pn_n, PK_BOTH),            // (polyline kind: the colour conversion's packed output is read by nothing but the debug plane)
+  PLANE(plab1, pn_n, PK_RECT), PLANE(smooth, pn_n, PK_RECT), PLANE(quant, pn_n, PK_RECT),
+  BLUR_PLANES(0), BLUR_PLANES(1), BLUR_PLANES(2),
+  PLANE(plab1, pn_n, PK_POLY_UNFUSED),    // (the polyline kind has it behind the blur's planes: a second row, so that no plane of either kind moves)
+  PLANE(vxy, pn_2n, PK_RECT | PK_POLY_UNFUSED), PLANE(strength, pn_n, PK_RECT | PK_POLY_UNFUSED),
+  PLANE(nms, pn_n, PK_BOTH),
+  PLANE(i0, pn_n, PK_RECT), PLANE(i1, pn_n, PK_RECT), PLANE(mask0, pn_n, PK_BOTH), PLANE(tidy, pn_n, PK_RECT), PLANE(label1, pn_n, PK_BOTH), PLANE(strsum, pn_n, PK_BOTH),
+  PLANE(region, pn_n, PK_RECT), PLANE(rsize, pn_n, PK_RECT), PLANE(boundarysrc, pn_n, PK_RECT), PLANE(boundary, pn_n, PK_RECT), PLANE(lsid, pn_n, PK_BOTH), PLANE(region0, pn_n, PK_RECT),
+  PLANE(scratch2, pn_scratch2, PK_RECT), PLANE(d2s, pn_d2, PK_RECT),
+  PLANE(table, pn_4n, PK_RECT), PLANE(claim, pn_n, PK_RECT), PLANE(tlist, pn_n, PK_RECT),
+  PLANE(e8, pn_n, PK_RECT),
+  PLANE(strongbits, pn_bits, PK_BOTH),    // (polyline kind: the poly mask, what the polyline stage traces)
+  PLANE(mmbits, pn_bits, PK_RECT),
+  PLANE(ext, pn_n, PK_RECT),
+  PLANE(tails, pn_tails, PK_BOTH), PLANE(flags, pn_flags, PK_BOTH),
+  { offsetof(Slot, lslist), 1, pn_16n, PK_BOTH },      // (bytes: the list has the reference's capacity)
+  PLANE(probes, pn_probes, PK_RECT),
 };
+#undef BLUR_PLANES
+#undef PLANE
 
 static bool front_is_fused(const rd_detector *d);
-// The planes of a polyline-kind slot: the front end up to the suppressed response, the labelling, the strength sums, the mask bits, the list and the id
-// plane.  None of the rect kind's later planes (edge-stopped blur, quantisation, merge mask, regions, boundaries, vote tables, probes, post-process).
-static void slot_planes_poly(rd_detector *d, Slot *s, PlaneAlloc &A) {
-  const size_t N = (size_t)d->N;
-  s->bgr = A.get<uint8_t>(N * 4);
-  s->plab0 = A.get<uint32_t>(N);         // (the colour conversion's packed output: read by nothing on this path but the debug plane)
-  for (int k = 0; k < 3; k++) { s->tr[k] = A.get<float>(N); s->fw[k] = A.get<float>(N); s->bw[k] = A.get<float>(N); s->hz[k] = A.get<float>(N); s->bl[k] = A.get<float>(N); }
-  if (!front_is_fused(d)) { s->plab1 = A.get<uint32_t>(N); s->vxy = A.get<float>(N * 2); s->strength = A.get<float>(N); }      // (frame sizes the fused kernel's tiles do not cover: the three operators)
-  s->nms = A.get<float>(N);
-  s->mask0 = A.get<int>(N); s->label1 = A.get<int>(N); s->strsum = A.get<int>(N); s->lsid = A.get<int>(N);
-  s->strongbits = A.get<unsigned long long>((size_t)((d->iw + 63) / 64) * d->ih + 8);      // the poly mask as a bit plane: what the polyline stage traces
-  { size_t a = rdk::iir_pass_scratch_floats(3, d->ih, d->iw), b = rdk::iir_pass_scratch_floats(3, d->iw, d->ih); s->tails = A.get<float>(a > b ? a : b); }
-  s->flags = A.get<int>(16); if (A.real()) { RD_HIP(hipMemset(s->flags, 0, 16 * sizeof(int))); RD_HIP(hipStreamSynchronize(0)); }
-  s->iir_chunked = 1;
-  s->lslist = A.get<uint8_t>(N * 16);
-}
-
-static void slot_planes(rd_detector *d, Slot *s, PlaneAlloc &A) {
-  if (d->kind == RD_KIND_POLY) { slot_planes_poly(d, s, A); return; }
-  const size_t N = (size_t)d->N;
-  s->bgr = A.get<uint8_t>(N * 4);
-  s->plab0 = A.get<uint32_t>(N); s->plab1 = A.get<uint32_t>(N); s->smooth = A.get<uint32_t>(N); s->quant = A.get<uint32_t>(N);
-  for (int k = 0; k < 3; k++) { s->tr[k] = A.get<float>(N); s->fw[k] = A.get<float>(N); s->bw[k] = A.get<float>(N); s->hz[k] = A.get<float>(N); s->bl[k] = A.get<float>(N); }
-  s->vxy = A.get<float>(N * 2); s->strength = A.get<float>(N); s->nms = A.get<float>(N);
-  int **ip[] = { &s->i0, &s->i1, &s->mask0, &s->tidy, &s->label1, &s->strsum, &s->region, &s->rsize,
-                 &s->boundarysrc, &s->boundary, &s->lsid, &s->region0 };
-  for (size_t i = 0; i < sizeof(ip) / sizeof(ip[0]); i++) *ip[i] = A.get<int>(N);
-  s->scratch2 = A.get<int>(N * 3 + 256);      // region_merge: the initial forest, flags + allow bytes, the second label plane of the rounds
-  s->d2s = A.get<int>(RD_D2_SCRATCH_INTS(N));
-  s->table = A.get<int>(N * 4); s->claim = A.get<int>(N); s->tlist = A.get<int>(N);
-  if (A.real()) rdk::reduce_ls_init(s->st, s->table, s->claim, s->tlist, (int)(N * 4 / 5));
-  s->e8 = A.get<int8_t>(N);
-  s->strongbits = A.get<unsigned long long>((size_t)((d->iw + 63) / 64) * d->ih + 8);
-  s->mmbits = A.get<unsigned long long>((size_t)((d->iw + 63) / 64) * d->ih + 8);
-  s->ext = A.get<uint16_t>(N);
-  { size_t a = rdk::iir_pass_scratch_floats(3, d->ih, d->iw), b = rdk::iir_pass_scratch_floats(3, d->iw, d->ih); s->tails = A.get<float>(a > b ? a : b); }
-  s->flags = A.get<int>(16); if (A.real()) { RD_HIP(hipMemset(s->flags, 0, 16 * sizeof(int))); RD_HIP(hipStreamSynchronize(0)); }
-  s->iir_chunked = 1;
-  s->lslist = A.get<uint8_t>(N * 16);
-  s->probes = A.get<int>((size_t)d->maxrec_dev * 15 * 6);
+// The walk: the size of a slot of d's kind; with s != NULL also s's pointers, into the slot's range at `base`.
+static size_t slot_planes(const rd_detector *d, Slot *s, char *base) {
+  const int kind = d->kind == RD_KIND_POLY ? PK_POLY | (front_is_fused(d) ? 0 : PK_POLY_UNFUSED) : PK_RECT;
+  size_t at = 0;
+  for (const auto &r : kSlotPlanes) {
+    if (!(r.kinds & kind)) continue;
+    if (s) { char *p = base + at; memcpy((char *)s + r.field, &p, sizeof(p)); }
+    at += (r.count(d) * r.elem + 255) & ~(size_t)255;
+  }
+  return at;
 }
 
 // Streams of the high-priority pool (see slot_alloc) are kept for the life of the process and handed to the next detector of the same device: a detector
@@ -519,6 +518,12 @@ static hipStream_t make_redo_stream() {
   return st;
 }
 
+// the events of a slot; ev_begin / ev_done carry timestamps (device time of the frame: rd_detector_counter 1)
+static const struct { hipEvent_t Slot::*ev; bool timing; } kSlotEvents[] = {
+  { &Slot::ev_fork, false }, { &Slot::ev_join, false }, { &Slot::ev_mm, false }, { &Slot::ev_begin, true }, { &Slot::ev_done, true },
+  { &Slot::ev_strong, false }, { &Slot::ev_redo, false }, { &Slot::ev_upload, false }, { &Slot::ev_dense, false },
+};
+
 // share: the slot whose streams this one uses as well (NULL: own streams)
 static void slot_alloc(rd_detector *d, Slot *s, Slot *share) {
   const size_t N = (size_t)d->N;
@@ -542,16 +547,11 @@ static void slot_alloc(rd_detector *d, Slot *s, Slot *share) {
     RD_HIP(hipStreamCreateWithFlags(&s->st2, hipStreamNonBlocking));
     }
   }
-  RD_HIP(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
-  RD_HIP(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
-  RD_HIP(hipEventCreateWithFlags(&s->ev_mm, hipEventDisableTiming));
-  RD_HIP(hipEventCreate(&s->ev_begin));
-  RD_HIP(hipEventCreate(&s->ev_done));
-  RD_HIP(hipEventCreateWithFlags(&s->ev_strong, hipEventDisableTiming));
-  RD_HIP(hipEventCreateWithFlags(&s->ev_redo, hipEventDisableTiming));
-  RD_HIP(hipEventCreateWithFlags(&s->ev_upload, hipEventDisableTiming));
-  RD_HIP(hipEventCreateWithFlags(&s->ev_dense, hipEventDisableTiming));
-  { PlaneAlloc A = { d->arena ? d->arena + (size_t)(s - d->slots) * d->slot_pitch : NULL, 0, d->arena ? 1 : 0 }; slot_planes(d, s, A); }
+  for (const auto &e : kSlotEvents) { if (e.timing) RD_HIP(hipEventCreate(&(s->*e.ev))); else RD_HIP(hipEventCreateWithFlags(&(s->*e.ev), hipEventDisableTiming)); }
+  slot_planes(d, s, d->arena + (size_t)(s - d->slots) * d->slot_pitch);
+  // what the planes must hold before the first frame: empty vote tables, the blur's flags at zero
+  if (d->kind == RD_KIND_RECT) rdk::reduce_ls_init(s->st, s->table, s->claim, s->tlist, (int)(N * 4 / 5));
+  RD_HIP(hipMemset(s->flags, 0, 16 * sizeof(int))); RD_HIP(hipStreamSynchronize(0));
   s->ps = rdk::poly_scratch_create(d->iw, d->ih);
   RD_HIP(hipHostMalloc(&s->h_bgr, N * 4, hipHostMallocDefault));
   const size_t pack_ints = d->kind == RD_KIND_POLY ? 64 + (size_t)d->handoff_rec * 14 : 64 + (size_t)RD_MAXREC * (14 + 15 * 6);      // (poly kind: counters + records, no probes)
@@ -576,19 +576,13 @@ static void slot_alloc(rd_detector *d, Slot *s, Slot *share) {
 
 static void slot_free(Slot *s, int device) {
   RD_HIP(hipStreamSynchronize(s->st));
-  void *all[] = { s->bgr, s->plab0, s->plab1, s->smooth, s->quant, s->vxy, s->strength, s->nms, s->i0, s->i1, s->mask0, s->tidy, s->label1, s->strsum,
-                  s->region, s->rsize, s->scratch2, s->d2s, s->boundarysrc, s->boundary, s->lsid, s->table, s->claim, s->tlist, s->region0, s->probes, s->e8, s->strongbits, s->mmbits, s->ext, s->tails, s->flags, s->lslist };
-  if (!s->owner->arena) {
-  for (void *p : all) dfree(p);
-  for (int k = 0; k < 3; k++) { dfree(s->tr[k]); dfree(s->fw[k]); dfree(s->bw[k]); dfree(s->hz[k]); dfree(s->bl[k]); }
-  }
+  // (the planes: part of the detector's arena, freed with it)
   rdk::poly_scratch_destroy(s->ps);
   RD_HIP(hipHostFree(s->h_bgr)); RD_HIP(hipHostFree(s->h_pack));
   if (s->sc_bgr) RD_HIP(hipFree(s->sc_bgr));
   if (s->sc_h) RD_HIP(hipHostFree(s->sc_h));
   dfree(s->post_scratch); if (s->h_post) RD_HIP(hipHostFree(s->h_post));
-  RD_HIP(hipEventDestroy(s->ev_begin)); RD_HIP(hipEventDestroy(s->ev_done)); RD_HIP(hipEventDestroy(s->ev_strong));
-  RD_HIP(hipEventDestroy(s->ev_fork)); RD_HIP(hipEventDestroy(s->ev_mm)); RD_HIP(hipEventDestroy(s->ev_join)); RD_HIP(hipEventDestroy(s->ev_redo)); RD_HIP(hipEventDestroy(s->ev_dense)); RD_HIP(hipEventDestroy(s->ev_upload));
+  for (const auto &e : kSlotEvents) RD_HIP(hipEventDestroy(s->*e.ev));
   if (s->st_redo) RD_HIP(hipStreamDestroy(s->st_redo));
   dfree(s->big_probes);
   if (!s->shares_streams) {
@@ -1205,13 +1199,8 @@ static void detector_slots(rd_detector *d, int nstreams) {
   if (rd_env("RD_ZBATCH")) { const int z = rd_env_int("RD_ZBATCH", 1); d->zb = z < 1 ? 1 : (z > RD_ZB_MAX ? RD_ZB_MAX : z); }
   if (d->fork_poly || d->zb > nslots) d->zb = 1;
   if (d->zb > 1) { d->batch = 1; d->defer = 0; }      // (a group's sparse stages follow its dense stages on the same stream)
-  if (d->zb > 1) {
-    Slot tmp; memset(&tmp, 0, sizeof(tmp));
-    PlaneAlloc A = { NULL, 0, 2 };
-    slot_planes(d, &tmp, A);
-    d->slot_pitch = A.at;
-    d->arena = dnew<char>((size_t)nslots * d->slot_pitch);
-  }
+  d->slot_pitch = slot_planes(d, NULL, NULL);
+  d->arena = dnew<char>((size_t)nslots * d->slot_pitch);
   for (int i = 0; i < nslots; i++) {
     Slot *s = &d->slots[i];
     slot_alloc(d, s, (!d->fork_poly && i >= nstreams) ? &d->slots[i % nstreams] : NULL);
@@ -1644,10 +1633,7 @@ long rd_detector_counter(rd_detector *d, int which) {
   if (which == 1) return d->dev_us;
   if (which == 2) return d->dev_frames;
   if (which == 30) return __atomic_load_n(&d->n_long_lists, __ATOMIC_RELAXED);
-  if (which == 31) {      // (counted the way the slots were carved: every plane rounded up to 256 bytes)
-    if (!d->slot_bytes) { Slot tmp; memset(&tmp, 0, sizeof(tmp)); PlaneAlloc A = { NULL, 0, 2 }; slot_planes(d, &tmp, A); d->slot_bytes = A.at; }
-    return (long)d->slot_bytes;
-  }
+  if (which == 31) return (long)d->slot_pitch;      // (device bytes of one slot's planes, the way the slots are carved: every plane rounded up to 256 bytes)
   if (which == 32) return d->kind == RD_KIND_POLY ? d->handoff_rec : RD_MAXREC;
   if (which == 33) { size_t b = 0; for (int i = 0; i < d->nslots; i++) if (d->slots[i].sc_bgr && d->slots[i].sc_bytes > b) b = d->slots[i].sc_bytes; return (long)b; }
   return which == 0 ? __atomic_load_n(&d->n_redo, __ATOMIC_RELAXED) : -1;
@@ -1661,7 +1647,6 @@ int rd_detector_last_segments(rd_detector *d, void *dst, int max_records) {
   return d->last_nsegs;
 }
 
-static size_t poly_debug_plane(rd_detector *d, Slot *s, const char *name, void *dst, size_t max_bytes);
 // A plane kept as bits on the device (ceil(iw / 64) words per row), handed out as an int plane.  junction: not the bits but the junction counts
 // (oclrect.cl:74-95: on-pixels of the 3x3 block, 1 -> 0, frame border 0) evaluated from them.
 static size_t bit_plane_as_ints(rd_detector *d, const void *bits, int junction, void *dst, size_t max_bytes) {
@@ -1683,63 +1668,73 @@ static size_t bit_plane_as_ints(rd_detector *d, const void *bits, int junction, 
   free(tmp);
   return n * 4;
 }
+// The debug planes of both kinds: the one table of them (include/rectdetect_hip.h lists the names).  A row: name, kinds, plane + byte offset, `bytes`, how the plane is
+// viewed, what has to be launched before it can be looked at.  `bytes` is what the CALLER gets when max_bytes is ample, not what lies at the pointer: the rows of the int
+// views say N * 4 where the device holds N bytes (edge500) or a bit plane (strong, junction, mergemask, polymask); a raw row's two sizes are the same.
+enum { VIEW_RAW,          // as stored; a shorter buffer gets min(bytes, max_bytes)
+       // int views - kept in another shape on the device, handed out as the reference's int planes; a shorter buffer gets max_bytes / 4 elements:
+       VIEW_BITS,         // a bit plane (what the polyline stage traces / what the region stage reads; oclrect.c:307-321, poly.cpp:121)
+       VIEW_JUNCTION,     // the junction counts evaluated from a bit plane
+       VIEW_POSITIVE,     // `> 0` of a float plane (rect kind's mask0, oclrect.c:262-264: not stored on the frame path, derived from the suppressed strength)
+       VIEW_INT8,         // bytes (the blur's mask; oclrect.c:277-284)
+       VIEW_STRSUM };     // raw + the strong mask the frame read: the reference's plane holds the sums ON TOP of the previous frame's strong mask (H1)
+enum { PREP_NONE,
+       PREP_IDS,          // polyline_ids: the id plane is not part of the frame path, it is built from the compact state
+       PREP_FLATTEN,      // a -DRD_BOUNDARY_FLATTEN=0 build leaves the boundary components as a forest (its few readers walk): flattened here, where the plane is looked at
+       PREP_TAPS };       // plab1, vxy, strength never leave the chip where the front is fused: the same kernel again, writing them out (the blurred planes are intact)
 size_t rd_detector_debug_plane(rd_detector *d, const char *name, void *dst, size_t max_bytes) {
   if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_debug_plane: bad handle\n");
   if (d->last_polled_slot < 0) return 0;
   RD_HIP(hipSetDevice(d->device));
   Slot *s = &d->slots[d->last_polled_slot];
-  const size_t N = (size_t)d->N;
-  if (d->kind == RD_KIND_POLY) return poly_debug_plane(d, s, name, dst, max_bytes);
-  struct { const char *n; const void *p; size_t bytes; } tab[] = {
-    { "plab0", s->plab0, N * 4 }, { "plab1", s->plab1, N * 4 }, { "lblur", s->bl[0], N * 4 }, { "vxy", s->vxy, N * 8 }, { "strength", s->strength, N * 4 },
-    { "nms", s->nms, N * 4 }, { "mask0", s->nms, N * 4 }, { "tidy", s->tidy, N * 4 }, { "label1", s->label1, N * 4 }, { "strsum", s->strsum, N * 4 },
-    { "edge500", s->e8, N }, { "smooth", s->smooth, N * 4 }, { "quant", s->quant, N * 4 }, { "strong", s->strongbits, (size_t)((d->iw + 63) / 64) * d->ih * 8 }, { "junction", s->strongbits, (size_t)((d->iw + 63) / 64) * d->ih * 8 },
-    { "mergemask", s->mmbits, (size_t)((d->iw + 63) / 64) * d->ih * 8 }, /* (bit planes: handed out as int planes by the branch below) */ { "region", s->region, N * 4 }, { "region0", s->region0, N * 4 }, { "rsize", s->rsize, N * 4 }, { "boundarysrc", s->boundarysrc, N * 4 },
-    { "boundary", s->boundary, N * 4 }, { "lsid", s->lsid, N * 4 }, { "table", s->table, (N * 4 / 5) * 5 * 4 }, { "lslist", s->lslist, N * 16 }, { "polyctr", rdk::poly_scratch_counters(s->ps), 64 * 4 }, { "iirflags", s->flags, 16 * 4 }, { "d2work", s->d2s + N, 16 * 4 }, { "absorb", s->scratch2 + N + RD_REGION_STATUS_AT, 8 * 4 },
+  const size_t N = (size_t)d->N, NI = N * 4;
+  const int kind = d->kind == RD_KIND_POLY ? PK_POLY : PK_RECT;
+  const struct { const char *n; int kinds; const void *p; size_t off, bytes; int view, prep; } tab[] = {
+    { "plab0", PK_BOTH, s->plab0, 0, NI, VIEW_RAW, PREP_NONE }, { "plab1", PK_RECT, s->plab1, 0, NI, VIEW_RAW, PREP_TAPS }, { "lblur", PK_BOTH, s->bl[0], 0, NI, VIEW_RAW, PREP_NONE },
+    { "vxy", PK_RECT, s->vxy, 0, N * 8, VIEW_RAW, PREP_TAPS }, { "strength", PK_RECT, s->strength, 0, NI, VIEW_RAW, PREP_TAPS }, { "nms", PK_BOTH, s->nms, 0, NI, VIEW_RAW, PREP_NONE },
+    { "mask0", PK_RECT, s->nms, 0, NI, VIEW_POSITIVE, PREP_NONE }, { "mask0", PK_POLY, s->mask0, 0, NI, VIEW_RAW, PREP_NONE }, { "tidy", PK_RECT, s->tidy, 0, NI, VIEW_RAW, PREP_NONE },
+    { "label1", PK_BOTH, s->label1, 0, NI, VIEW_RAW, PREP_NONE }, { "strsum", PK_RECT, s->strsum, 0, NI, VIEW_STRSUM, PREP_NONE }, { "strsum", PK_POLY, s->strsum, 0, NI, VIEW_RAW, PREP_NONE },
+    { "edge500", PK_RECT, s->e8, 0, NI, VIEW_INT8, PREP_NONE }, { "smooth", PK_RECT, s->smooth, 0, NI, VIEW_RAW, PREP_NONE }, { "quant", PK_RECT, s->quant, 0, NI, VIEW_RAW, PREP_NONE },
+    { "strong", PK_RECT, s->strongbits, 0, NI, VIEW_BITS, PREP_NONE }, { "junction", PK_RECT, s->strongbits, 0, NI, VIEW_JUNCTION, PREP_NONE }, { "mergemask", PK_RECT, s->mmbits, 0, NI, VIEW_BITS, PREP_NONE },
+    { "polymask", PK_POLY, s->strongbits, 0, NI, VIEW_BITS, PREP_NONE },
+    { "region", PK_RECT, s->region, 0, NI, VIEW_RAW, PREP_NONE }, { "region0", PK_RECT, s->region0, 0, NI, VIEW_RAW, PREP_NONE }, { "rsize", PK_RECT, s->rsize, 0, NI, VIEW_RAW, PREP_NONE },
+    { "boundarysrc", PK_RECT, s->boundarysrc, 0, NI, VIEW_RAW, PREP_NONE }, { "boundary", PK_RECT, s->boundary, 0, NI, VIEW_RAW, PREP_FLATTEN }, { "lsid", PK_BOTH, s->lsid, 0, NI, VIEW_RAW, PREP_IDS },
+    { "table", PK_RECT, s->table, 0, (N * 4 / 5) * 5 * 4, VIEW_RAW, PREP_NONE }, { "lslist", PK_BOTH, s->lslist, 0, N * 16, VIEW_RAW, PREP_NONE },
+    { "polyctr", PK_BOTH, rdk::poly_scratch_counters(s->ps), 0, 64 * 4, VIEW_RAW, PREP_NONE }, { "iirflags", PK_RECT, s->flags, 0, 16 * 4, VIEW_RAW, PREP_NONE },
+    { "d2work", PK_RECT, s->d2s, NI, 16 * 4, VIEW_RAW, PREP_NONE }, { "absorb", PK_RECT, s->scratch2, (N + RD_REGION_STATUS_AT) * 4, 8 * 4, VIEW_RAW, PREP_NONE },
   };
-  for (size_t i = 0; i < sizeof(tab) / sizeof(tab[0]); i++)
-    if (!strcmp(tab[i].n, name)) {
-      const size_t b = tab[i].bytes < max_bytes ? tab[i].bytes : max_bytes;
-      // (launches of a test tap: under the lock that keeps launches out of another thread's graph capture)
-      pthread_mutex_lock(&d->launch_mu);
-      if (!strcmp(name, "lsid")) rdk::polyline_ids(s->st, s->frame, 1, (int)N);   // not part of the frame path: built from the compact state
-      if (!strcmp(name, "boundary") && !RD_BOUNDARY_FLATTEN) rdk::label8_flatten(s->st, s->boundary, (int)N);   // the frame path leaves the components as a forest (its few readers walk): flattened here, where the plane is looked at
-      if ((!strcmp(name, "plab1") || !strcmp(name, "vxy") || !strcmp(name, "strength")) && front_is_fused(d))
-        frames_grad_nms(d, s, s->st, 1, 0, 1);      // these never leave the chip on the frame path: the same kernel again, writing them out (the blurred planes are intact)
-      pthread_mutex_unlock(&d->launch_mu);
-      RD_HIP(hipStreamSynchronize(s->st));
-      if (!strcmp(name, "strong") || !strcmp(name, "mergemask") || !strcmp(name, "junction")) {
-        // kept as bit planes on the device (what the polyline stage traces / what the region stage reads); handed out as the int planes of
-        // oclrect.c:307-321 - the junction counts from the strong mask
-        return bit_plane_as_ints(d, tab[i].p, !strcmp(name, "junction"), dst, max_bytes);
-      }
-      if (!strcmp(name, "mask0")) {         // not stored on the frame path: the mask of positive responses (oclrect.c:262-264), from the suppressed strength
-        const size_t n = N * 4 <= max_bytes ? N : max_bytes / 4;
-        float *tmp = (float *)malloc(n ? n * 4 : 4);
-        if (!tmp) exitf(-1, "rd_detector_debug_plane: out of memory\n");
-        RD_HIP(hipMemcpy(tmp, s->nms, n * 4, hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < n; k++) ((int *)dst)[k] = tmp[k] > 0.0f ? 1 : 0;
-        free(tmp);
-        return n * 4;
-      }
-      if (!strcmp(name, "edge500")) {       // kept as bytes on the device (the blur's mask); handed out as the int plane of oclrect.c:277-284
-        const size_t n = N * 4 <= max_bytes ? N : max_bytes / 4;
-        int8_t *tmp = (int8_t *)malloc(n ? n : 1);
-        RD_HIP(hipMemcpy(tmp, tab[i].p, n, hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < n; k++) ((int *)dst)[k] = tmp[k];
-        free(tmp);
-        return n * 4;
-      }
-      RD_HIP(hipMemcpy(dst, tab[i].p, b, hipMemcpyDeviceToHost));
-      if (!strcmp(name, "strsum") && s->prev_in) {      // the reference's plane holds the sums ON TOP of the previous frame's strong mask (H1): added here, where it is looked at
-        const size_t n = b / 4;
-        int8_t *tmp = (int8_t *)malloc(n ? n : 1);
-        RD_HIP(hipMemcpy(tmp, s->prev_in, n, hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < n; k++) ((int *)dst)[k] += tmp[k];
-        free(tmp);
-      }
-      return b;
+  for (const auto &r : tab) {
+    if (!(r.kinds & kind) || strcmp(r.n, name)) continue;
+    const char *p = (const char *)r.p + r.off;
+    // (launches of a test tap: under the lock that keeps launches out of another thread's graph capture)
+    pthread_mutex_lock(&d->launch_mu);
+    if (r.prep == PREP_IDS) rdk::polyline_ids(s->st, s->frame, 1, (int)N);
+    if (r.prep == PREP_FLATTEN && !RD_BOUNDARY_FLATTEN) rdk::label8_flatten(s->st, s->boundary, (int)N);
+    if (r.prep == PREP_TAPS && front_is_fused(d)) frames_grad_nms(d, s, s->st, 1, 0, 1);
+    if (r.prep != PREP_NONE) rdrt::check_launch("debug plane");
+    pthread_mutex_unlock(&d->launch_mu);
+    RD_HIP(hipStreamSynchronize(s->st));
+    if (r.view == VIEW_BITS || r.view == VIEW_JUNCTION) return bit_plane_as_ints(d, p, r.view == VIEW_JUNCTION, dst, max_bytes);
+    if (r.view == VIEW_POSITIVE || r.view == VIEW_INT8) {
+      const size_t n = NI <= max_bytes ? N : max_bytes / 4, eb = r.view == VIEW_INT8 ? 1 : 4;
+      void *tmp = malloc(n ? n * eb : 4);
+      if (!tmp) exitf(-1, "rd_detector_debug_plane: out of memory\n");
+      RD_HIP(hipMemcpy(tmp, p, n * eb, hipMemcpyDeviceToHost));
+      for (size_t k = 0; k < n; k++) ((int *)dst)[k] = r.view == VIEW_INT8 ? ((const int8_t *)tmp)[k] : (((const float *)tmp)[k] > 0.0f ? 1 : 0);
+      free(tmp);
+      return n * 4;
     }
+    const size_t b = r.bytes < max_bytes ? r.bytes : max_bytes;
+    RD_HIP(hipMemcpy(dst, p, b, hipMemcpyDeviceToHost));
+    if (r.view == VIEW_STRSUM && s->prev_in) {
+      const size_t n = b / 4;
+      int8_t *tmp = (int8_t *)malloc(n ? n : 1);
+      RD_HIP(hipMemcpy(tmp, s->prev_in, n, hipMemcpyDeviceToHost));
+      for (size_t k = 0; k < n; k++) ((int *)dst)[k] += tmp[k];
+      free(tmp);
+    }
+    return b;
+  }
   return 0;
 }
 
@@ -1792,27 +1787,6 @@ void *rd_detector_poll_segments(rd_detector *d, int32_t *ids_out) {
   d->last_polled_slot = si;
   d->next_poll++;
   return out;
-}
-
-// debug planes of the polyline kind (the planes it has): plab0 lblur nms mask0 label1 strsum polymask lslist lsid polyctr
-static size_t poly_debug_plane(rd_detector *d, Slot *s, const char *name, void *dst, size_t max_bytes) {
-  const size_t N = (size_t)d->N;
-  const int wpr = (d->iw + 63) / 64;
-  struct { const char *n; const void *p; size_t bytes; } tab[] = {
-    { "plab0", s->plab0, N * 4 }, { "lblur", s->bl[0], N * 4 }, { "nms", s->nms, N * 4 }, { "mask0", s->mask0, N * 4 }, { "label1", s->label1, N * 4 },
-    { "strsum", s->strsum, N * 4 }, { "polymask", s->strongbits, (size_t)wpr * d->ih * 8 }, { "lslist", s->lslist, N * 16 }, { "lsid", s->lsid, N * 4 },
-    { "polyctr", rdk::poly_scratch_counters(s->ps), 64 * 4 },
-  };
-  for (size_t i = 0; i < sizeof(tab) / sizeof(tab[0]); i++) {
-    if (strcmp(tab[i].n, name)) continue;
-    if (!strcmp(name, "lsid")) { rdk::polyline_ids(s->st, s->frame, 1, (int)N); rdrt::check_launch("polyline ids"); }
-    RD_HIP(hipStreamSynchronize(s->st));
-    if (!strcmp(name, "polymask")) return bit_plane_as_ints(d, tab[i].p, 0, dst, max_bytes);      // (poly.cpp:121)
-    const size_t b = tab[i].bytes < max_bytes ? tab[i].bytes : max_bytes;
-    RD_HIP(hipMemcpy(dst, tab[i].p, b, hipMemcpyDeviceToHost));
-    return b;
-  }
-  return 0;
 }
 
 // ================================================================================================ oclrect (reference API)

@@ -1782,3 +1782,90 @@ def test_builtin_sensitivity_report():
         order_dependent = any(k.endswith(f"_s{seed}_100_f{t}_union") and f"{iw}x{ih}" in k for k in golden("stream_orders").files)
         helpers.parity_report("builtin sensitivity of the reference (rectangle lists)", f"frame {fi}: {iw}x{ih} seed {seed} t {t} (order-dependent)", order_dependent)
         assert "baseline" in same or order_dependent, f"frame {fi}: the HIP path shares the baseline's builtin definitions and must return its list"
+
+
+# ---- the slots' planes: one list (rd_api.hip: kSlotPlanes), one allocation per detector, one table of debug planes
+# device bytes of one slot (counter 31) as commit 1a1e500 returns them (its library, run once on the GPU) - the commit before the plane list became one table, which must not
+# add, drop, resize or re-round a plane
+SLOT_BYTES = {("rect", 16, 16): 89856, ("rect", 65, 55): 1178112, ("rect", 64, 54): 1136384, ("rect", 333, 217): 23737856, ("rect", 1920, 1080): 489198592,
+              ("poly", 16, 16): 32512, ("poly", 65, 55): 453376, ("poly", 64, 54): 381696, ("poly", 333, 217): 7979008, ("poly", 1920, 1080): 226881024}
+
+
+def _new_detector(kind, iw, ih, nslots):
+    return ra.Detector(iw, ih, nslots=nslots) if kind == "rect" else ra.PolylineDetector(iw, ih, nslots=nslots)
+
+
+def _poll(kind, det):
+    return det.poll(TAN36) if kind == "rect" else det.poll()
+
+
+@pytest.mark.parametrize("kind,iw,ih", sorted(SLOT_BYTES))
+def test_slot_layout_is_pinned(kind, iw, ih):
+    """16x16: the minimum; 65x55: the unfused front, where the polyline kind owns plab1 / vxy / strength; 64x54: fused; an odd size; the benchmark's"""
+    det = _new_detector(kind, iw, ih, 1)
+    got = ra.lib().rd_detector_counter(det.h, 31)
+    det.close()
+    print(f"slot bytes {kind} {iw}x{ih}: {got}, pinned {SLOT_BYTES[kind, iw, ih]}")
+    assert got == SLOT_BYTES[kind, iw, ih]
+
+
+# what rd_detector_debug_plane hands out per kind (include/rectdetect_hip.h): name -> bytes as a function of N; INT_VIEWS: kept in another shape on the device, truncated by elements
+RECT_PLANES = dict({n: (lambda N: N * 4) for n in "plab0 plab1 lblur strength nms mask0 tidy label1 strsum edge500 smooth quant strong junction mergemask region0 rsize region boundarysrc boundary lsid".split()},
+                   vxy=lambda N: N * 8, table=lambda N: N * 4 // 5 * 20, lslist=lambda N: N * 16, polyctr=lambda N: 256, iirflags=lambda N: 64, d2work=lambda N: 64, absorb=lambda N: 32)
+POLY_PLANES = dict({n: (lambda N: N * 4) for n in "plab0 lblur nms mask0 label1 strsum polymask lsid".split()}, lslist=lambda N: N * 16, polyctr=lambda N: 256)
+INT_VIEWS = {"rect": ("mask0", "edge500", "strong", "junction", "mergemask"), "poly": ("polymask",)}
+POLY_COMPARED = "plab0 lblur nms mask0 label1 strsum polymask lsid".split()
+
+
+@pytest.fixture(scope="module", params=[("rect", 65, 55, 9), ("rect", 130, 109, 10), ("poly", 65, 55, 9), ("poly", 130, 109, 10)], ids=lambda p: "%s_%dx%d" % p[:3])
+def one_and_six_slots(request):
+    """the same two frames through a one-slot detector (ungrouped) and a six-slot detector, where they form one group launch and frame 1 ends in slot 1 - not the first
+    slot of the arena; both detectors stand at the poll of frame 1 (whose strsum view adds the strong mask of frame 0).  65x55: unfused front; 130x109: fused, two tiles wide"""
+    kind, iw, ih, seed = request.param
+    frames = [synth.frame(synth.SEED0 + seed, iw, ih, t) for t in range(2)]
+    one, six = _new_detector(kind, iw, ih, 1), _new_detector(kind, iw, ih, 6)
+    for f in frames:
+        one.enqueue(f)
+        _poll(kind, one)
+    for f in frames:
+        six.enqueue(f)
+    for f in frames:
+        _poll(kind, six)
+    yield kind, one, six
+    one.close()
+    six.close()
+
+
+def test_debug_planes_of_a_later_slot_of_the_arena(one_and_six_slots):
+    kind, one, six = one_and_six_slots
+    ctr = ra.lib().rd_detector_counter
+    assert ctr(one.h, 15) == 1 and ctr(six.h, 15) == 2, "the six-slot detector must launch in groups of two"
+    if kind == "rect":      # (the strong masks of a group are counted per group launch: in one launch, 16, or frame by frame, 17; a frame launched on its own counts in neither)
+        assert ctr(six.h, 16) + ctr(six.h, 17) == 1 and ctr(one.h, 16) + ctr(one.h, 17) == 0, "the two frames must have run as one group launch"
+    N = one.N
+    names = [(g, N * k) for g, _, k in EXACT] + [(g, N * 4 // 5 * 5 if g == "table" else N) for g, _ in REGION_EXACT] if kind == "rect" else [(g, N) for g in POLY_COMPARED]
+    for g, count in names:
+        a, b = one.plane(g, np.uint32, count), six.plane(g, np.uint32, count)
+        assert a.tobytes() == b.tobytes(), f"plane {g}: {int((a != b).sum())} elements differ between slot 0 of a one-slot detector and slot 1 of a group"
+
+
+def test_debug_plane_table_contract(one_and_six_slots):
+    """every name of the kind: its full byte count into an ample buffer, the truncated count into 40 and 42 bytes (raw planes: bytes; int views: whole elements), nothing written
+    behind what is reported; names of the other kind and unknown names: 0"""
+    kind, one, _ = one_and_six_slots
+    N, call = one.N, ra.lib().rd_detector_debug_plane
+    mine, other = (RECT_PLANES, POLY_PLANES) if kind == "rect" else (POLY_PLANES, RECT_PLANES)
+    for name, nbytes in mine.items():
+        full = nbytes(N)
+        buf = np.full(full + 64, 0xAB, np.uint8)
+        assert call(one.h, name.encode(), buf.ctypes.data, buf.nbytes) == full, name
+        assert (buf[full:] == 0xAB).all(), name
+        for max_bytes in (40, 42):      # (42: where min(bytes, max_bytes) and max_bytes / 4 whole elements part)
+            small = np.full(104, 0xAB, np.uint8)
+            want = max_bytes // 4 * 4 if name in INT_VIEWS[kind] else min(full, max_bytes)
+            assert call(one.h, name.encode(), small.ctypes.data, max_bytes) == want, (name, max_bytes)
+            whole = want // 4 * 4      # (the strsum view adds the previous strong mask to whole elements only)
+            assert (small[want:] == 0xAB).all() and small[:whole].tobytes() == buf[:whole].tobytes(), (name, max_bytes)
+    buf = np.zeros(64, np.uint8)
+    for name in sorted(set(other) - set(mine)) + ["nope"]:
+        assert call(one.h, name.encode(), buf.ctypes.data, buf.nbytes) == 0, name
