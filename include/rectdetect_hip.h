@@ -266,6 +266,91 @@ int rd_rectifier_wait(rd_rectifier *r, uint8_t *status_out);
  * the full-size source, see there.  Returns as rd_rectifier_enqueue; -1 also when nothing has been polled yet or d and r are on different devices. */
 long rd_detector_rectify_polled(rd_detector *d, rd_rectifier *r, const double *quads, int n, void *out, int out_kind);
 
+/* ---- annotated frames: rectangles' outlines and line segments drawn INTO a frame on the device (rd_k_annotate.hip, rd_annotate.hip) - the picture vidrect.cpp /
+ * rect.cpp (showRect) and vidpoly.cpp / poly.cpp make with OpenCV's line() on the host, for frames that never leave HBM.  OpenCV's round brush is not restated; the
+ * arithmetic is defined here, in integers, exactly, so that an independent restatement (tests/annotate.py) reproduces every byte.
+ *
+ * A primitive is one line segment (x0, y0) - (x1, y1) in frame pixels, pixel centres at integers as in rect_t::c2, with a colour and a thickness.  Every coordinate lies
+ * in [-1048576, 1048575] and thickness is >= 1: a job with any other primitive is refused (-1).
+ *
+ * Coverage - independent of the order of the endpoints:
+ *   dx = x1 - x0, dy = y1 - y0.  The primitive is x-major when |dx| >= |dy|, else y-major; u is the major coordinate of a pixel, v the minor one.
+ *   Swap the endpoints so that the major coordinate does not decrease: (ua, va) -> (ub, vb), D = ub - ua >= 0.
+ *   The brush extends along the minor axis only: lo = (t - 1) / 2, hi = t / 2 (integer division) for thickness t.
+ *   For every u in [ua, ub]:  V(u) = va + floor((2 (u - ua) (vb - va) + D) / (2 D))   (floor division; V = va when D = 0)
+ *   and the primitive covers the pixels (u, V(u) + o), o in [-lo, hi].  No end caps.  Pixels outside the frame are not written; nothing clips or alters the line.
+ * The same test per pixel without a division (what the kernel and rd_annot_covers evaluate, rd_annot_cover.h; int64, |e| < 2^45 at every legal coordinate):
+ *   covered  <=>  ua <= u <= ub  and  -2 D hi <= e < 2 D (lo + 1)   with  e = 2 (u - ua) (vb - va) + D - 2 D (v - va);     D = 0:  -lo <= v - va <= hi.
+ *
+ * Painter's order: where several primitives of a job cover a pixel, the one with the HIGHEST index wins, as successive line() calls would have it.  The result is a
+ * function of the job alone, never of scheduling.
+ *
+ * Formats: all six RD_PIX_*.  Packed formats: the pixel's B, G, R bytes, in the format's order, are written; A never is, not even by RD_ANNOT_CLEAR.  NV12 and I420 (even
+ * iw and ih, as elsewhere): each primitive's colour is converted once, on the host (rd_annot_yuv; int32, arithmetic shifts)
+ *   Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16;   U = ((-38 R - 74 G + 112 B + 128) >> 8) + 128;   V = ((112 R - 94 G - 18 B + 128) >> 8) + 128
+ * luma is written per covered pixel, and a chroma sample takes the U, V of the highest-indexed primitive that covers ANY of its four luma pixels; it stays as it is
+ * when none does.
+ * RD_ANNOT_CLEAR (flags bit 0; vidpoly.cpp's and poly.cpp's picture): before drawing, every pixel's colour becomes black - B = G = R = 0, or Y = 16 and U = V = 128.
+ * A job IN PLACE writes covered pixels only (with RD_ANNOT_CLEAR: every pixel's colour bytes).  A job into ANOTHER frame leaves the source as it is and writes every
+ * pixel of the destination once: it is the in-place job on a copy of the source's pixels (all bytes of a pixel, A included, travel with it).  Pitch padding and
+ * bytes behind the planes are never written, in either frame. */
+typedef struct { int32_t x0, y0, x1, y1; uint8_t b, g, r, thickness; } rd_annot_prim;   /* 20 bytes */
+#define RD_ANNOT_CLEAR 1
+
+/* host helpers; none needs a GPU */
+/* 1 when primitive p covers pixel (x, y), else 0 (p must be legal): the shared coverage test (test tap) */
+int rd_annot_covers(const rd_annot_prim *p, int x, int y);
+/* 1 when the kernel's binning puts p into a tile that is the pixel rectangle [x0, x1] x [y0, y1] (inclusive): it may say 1 for a tile p only passes close to, never
+ * 0 for a tile with a covered pixel (test tap) */
+int rd_annot_touches(const rd_annot_prim *p, int x0, int y0, int x1, int y1);
+void rd_annot_yuv(uint8_t b, uint8_t g, uint8_t r, uint8_t yuv[3]);
+/* out[0], out[1]: width and height of the tile of pixels one block draws (both even), out[2]: primitives the blocks test per pass = records of a tile's list held in
+ * LDS at a time (lists of any length are drawn in as many passes: no capacity other than max_prims exists), out[3] = 0 */
+void rd_annot_limits(int32_t out[4]);
+/* Six primitives per rectangle (rects: n records of 176 bytes WITHOUT the header element: pass ret + 1) in showRect's order (vidrect.cpp:33-45): the edges
+ * c2[i] -> c2[(i+1)%4], i = 0..3, then c2[0] - c2[2], then c2[1] - c2[3].  Coordinates: (int) of the double - truncation toward zero, as cvPoint does; scale 2 (the
+ * rectangles of a frame that came in through rd_detector_enqueue_scaled, drawn into its full-size source): (int)(v * 2.0 + 0.5) and every thickness doubled
+ * (capped at 255).  style: b, g, r, thickness for status 0, 1, 2, 3; edges take the style's thickness, diagonals 1.  NULL: vidrect.cpp's table as the bytes that land
+ * in its BGR Mat - status 0 (0,255,0,1), 1 (0,200,255,2), 2 (255,0,0,1), 3 (0,0,255,2).  A rectangle with a corner that is not finite or that lands outside the
+ * legal range, or with a status above 3, is skipped as a whole.  Returns the primitives written (out holds 6 n); 0 for a scale other than 1 or 2. */
+int rd_annot_rects(const void *rects, int n, int scale, const uint8_t style[16], rd_annot_prim *out);
+/* The segments of a linesegment_t list WITH its header (what rd_detector_poll_segments returns), thickness 1 (2 at scale 2), coordinates as rd_annot_rects.
+ * RD_ANNOT_SEG_ALL: records 1..n in white (vidpoly.cpp:200-207).  RD_ANNOT_SEG_CHAINS (poly.cpp:142-153): from every head - polyid != 0 and leftPtr <= 0 - along
+ * rightPtr while it stays in 1..n, at most n steps (a cycle ends there), colours (b,g,r) (255,255,100) / (100,100,255) alternating by position in the chain.  Records
+ * out of range are skipped (their position still counts).  Writes at most max primitives; returns how many there are, which may exceed max. */
+#define RD_ANNOT_SEG_ALL 0
+#define RD_ANNOT_SEG_CHAINS 1
+int rd_annot_segments(const void *lslist, int mode, int scale, rd_annot_prim *out, int max);
+
+/* An annotator draws up to max_prims primitives per job, up to njobs jobs in flight, on one stream of its own.  NULL on bad arguments (max_prims < 1 or > 1048576,
+ * njobs < 1 or > 1024, no such device). */
+typedef struct rd_annotator rd_annotator;
+rd_annotator *rd_annotator_create(int device, int max_prims, int njobs);
+void rd_annotator_destroy(rd_annotator *a);      /* waits for the jobs in flight */
+/* One job: n primitives into one iw x ih frame in pixel format `format` (planes / pitches as for rd_detector_enqueue_planes).  The primitives are copied before the
+ * call returns.
+ * out_planes == NULL: in place - on_device must be RD_FRAME_DEVICE; the frame is the caller's until the job's wait.
+ * otherwise: the source is not modified and the annotated frame goes to out_planes / out_pitches, memory of kind out_kind: RD_FRAME_DEVICE (the kernel writes there) or
+ *   RD_FRAME_HOST_PINNED (through a device buffer of the annotator, which grows on demand; the copy engine writes the rows).  The source is RD_FRAME_HOST (copied into
+ *   the annotator's own device buffer before the call returns), RD_FRAME_DEVICE (read in place) or RD_FRAME_HOST_PINNED (the copy engine reads it in place; memory that
+ *   is not pinned is fatal); device and pinned sources, and the output, stay valid until the job's wait returned.  Source and destination must not overlap.
+ * Returns the job's sequence number, or -1 with nothing enqueued for an argument error: an unknown format, on_device or out_kind, flag bits other than RD_ANNOT_CLEAR,
+ * iw or ih < 1 or > 65536, a NULL plane the format uses (source or output), a pitch smaller than its plane's row (source or output), NV12 / I420 with an odd iw or ih,
+ * n < 0, n > max_prims, n > 0 with prims NULL, a primitive out of range (a coordinate, or thickness 0), in place with a frame that is not on the device, an output
+ * plane that is not memory of the kind out_kind names.  A call with njobs jobs already in flight is fatal, as it is for the rectifier.
+ * An in-place job on a frame that a rectifier job reads must follow that job's rd_rectifier_wait: the two objects have streams of their own. */
+long rd_annotator_enqueue(rd_annotator *a, int format, const void *const planes[3], const int pitches[3], int iw, int ih, int on_device,
+                          const rd_annot_prim *prims, int n, int flags, void *const out_planes[3], const int out_pitches[3], int out_kind);
+/* the oldest job: blocks until the frame is where it was told to go, returns its n.  -1: no job in flight. */
+int rd_annotator_wait(rd_annotator *a);
+/* One job on the frame of the most recently polled slot of d (either kind of detector): its planes, pitches and format as they were handed over, at the SOURCE's
+ * size - a frame that came in at scale 2 (rd_detector_enqueue_scaled) is annotated at 2 iw x 2 ih, with primitives in source coordinates (rd_annot_rects and
+ * rd_annot_segments with scale 2 make them from the detector's lists).  A device frame: in place (out_planes NULL) or into out_planes.  A host or pinned frame: the
+ * source is the copy the detector uploaded, which must stay what the rectifier reads, so out_planes is required (-1 without); that copy lasts until the next enqueue
+ * on d: wait for the job first.  Returns as rd_annotator_enqueue; -1 also when nothing has been polled yet or d and a are on different devices. */
+long rd_detector_annotate_polled(rd_detector *d, rd_annotator *a, const rd_annot_prim *prims, int n, int flags,
+                                 void *const out_planes[3], const int out_pitches[3], int out_kind);
+
 /* ---- synthetic frames (csrc/rd_synth.c) */
 int rd_synth_num_quads(int iw, int ih);
 void rd_synth_frame(uint8_t *bgr, int iw, int ih, int ws, uint64_t seed, int t, int noise);

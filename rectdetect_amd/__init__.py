@@ -11,6 +11,7 @@ Mirrors of the reference programs' call sequences:
   * :class:`Detector` - the ``rd_detector`` extension (device-resident frames, several frames in flight)
   * :class:`PolylineDetector` - its polyline kind: poly.cpp / vidpoly.cpp per frame, several frames in flight
   * :class:`Rectifier` - the ``rd_rectifier`` extension: what is inside detected quads as upright patches of fixed size
+  * :class:`Annotator` - the ``rd_annotator`` extension: rectangles' outlines and line segments drawn into frames on the device
 """
 import ctypes
 import os
@@ -24,7 +25,11 @@ RECT_DTYPE = np.dtype([("c2", "<f8", (4, 2)), ("c3", "<f8", (4, 3)), ("value", "
 LS_DTYPE = np.dtype([("x0", "<f4"), ("y0", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("startIndex", "<i4"), ("endIndex", "<i4"),
                      ("leftPtr", "<i4"), ("rightPtr", "<i4"), ("startCount", "<i4"), ("endCount", "<i4"), ("maxDist", "<i4"),
                      ("polyid", "<i4"), ("npix", "<i4"), ("level", "<i4")])
-assert RECT_DTYPE.itemsize == 176 and LS_DTYPE.itemsize == 56
+# a primitive of an annotator's job (rd_annot_prim; the coverage contract is in include/rectdetect_hip.h, "annotated frames")
+PRIM_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("thickness", "u1")])
+assert RECT_DTYPE.itemsize == 176 and LS_DTYPE.itemsize == 56 and PRIM_DTYPE.itemsize == 20
+ANNOT_CLEAR = 1
+ANNOT_SEG_ALL, ANNOT_SEG_CHAINS = 0, 1
 
 # pixel formats of enqueue_planes (rd_detector_enqueue_planes; the conversion contract is in include/rectdetect_hip.h)
 PIX_BGR, PIX_RGB, PIX_BGRA, PIX_RGBA, PIX_NV12, PIX_I420 = range(6)
@@ -93,6 +98,18 @@ def _declare(L):
         "rd_rectifier_enqueue": (ctypes.c_long, [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ci, ci, vp, ci, vp, ci]),
         "rd_rectifier_wait": (ci, [vp, vp]),
         "rd_detector_rectify_polled": (ctypes.c_long, [vp, vp, vp, ci, vp, ci]),
+        # annotated frames (rd_annotate.hip)
+        "rd_annot_covers": (ci, [vp, ci, ci]),
+        "rd_annot_touches": (ci, [vp, ci, ci, ci, ci]),
+        "rd_annot_yuv": (None, [ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint8, vp]),
+        "rd_annot_limits": (None, [vp]),
+        "rd_annot_rects": (ci, [vp, ci, ci, vp, vp]),
+        "rd_annot_segments": (ci, [vp, ci, ci, vp, ci]),
+        "rd_annotator_create": (vp, [ci, ci, ci]),
+        "rd_annotator_destroy": (None, [vp]),
+        "rd_annotator_enqueue": (ctypes.c_long, [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ci, ci, vp, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci]),
+        "rd_annotator_wait": (ci, [vp]),
+        "rd_detector_annotate_polled": (ctypes.c_long, [vp, vp, vp, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci]),
         "rd_synth_frame": (None, [vp, ci, ci, ci, ctypes.c_uint64, ci, ci]),
         "rd_synth_num_quads": (ci, [ci, ci]),
         # reference API (oclhelper.h / raw cl*)
@@ -360,6 +377,33 @@ def _rectify_polled(h, rectifier, quads, out, out_pinned):
     return r
 
 
+def _prims_arg(prims):
+    p = np.ascontiguousarray(prims, dtype=PRIM_DTYPE).reshape(-1)
+    return p, len(p)
+
+
+def _out_args(out_planes, out_pitches):
+    """(plane pointers, pitches) of an annotator's destination - ADDRESSES of device or pinned planes - or (None, None): in place"""
+    if out_planes is None:
+        return None, None
+    if out_pitches is None:
+        raise ValueError("annotate: out_pitches are required with out_planes")
+    if not isinstance(out_planes, (list, tuple)):
+        out_planes, out_pitches = (out_planes,), (out_pitches,)
+    ptrs = [int(p) if p else None for p in list(out_planes)[:3]]
+    pitch = [int(p) for p in list(out_pitches)[:3]]
+    return (ctypes.c_void_p * 3)(*(ptrs + [None] * (3 - len(ptrs)))), (ctypes.c_int * 3)(*(pitch + [0] * (3 - len(pitch))))
+
+
+def _annotate_polled(h, annotator, prims, flags, out_planes, out_pitches, out_pinned):
+    p, n = _prims_arg(prims)
+    optrs, opitch = _out_args(out_planes, out_pitches)
+    r = lib().rd_detector_annotate_polled(h, annotator.h, p.ctypes.data, n, int(flags), optrs, opitch, 2 if out_pinned else 1)
+    if r == -1:
+        raise ValueError("rd_detector_annotate_polled: invalid arguments (nothing polled yet, a host frame without out_planes, %d primitives, flags %r)" % (n, flags))
+    return r
+
+
 class Detector:
     """The rd_detector extension: frames may already live in HBM, several frames in flight."""
 
@@ -399,6 +443,12 @@ class Detector:
         with out_pinned, of pinned host memory - as one job of `rectifier` (take it with rectifier.wait()); a host frame is read from the detector's own copy,
         which lasts until the next enqueue here.  ValueError on an argument error (nothing enqueued)."""
         return _rectify_polled(self.h, rectifier, quads, out, out_pinned)
+
+    def annotate_polled(self, annotator, prims, flags=0, out_planes=None, out_pitches=None, out_pinned=False):
+        """`prims` (PRIM_DTYPE; annot_rects / annot_segments make them) drawn into the frame of the most recently polled slot as one job of `annotator` (take it with
+        annotator.wait()): a device frame in place, or with out_planes / out_pitches - ADDRESSES of device planes or, with out_pinned, of pinned host planes - into
+        another frame; a host frame needs out_planes.  A frame that came in at scale 2 is annotated at its source size.  ValueError on an argument error."""
+        return _annotate_polled(self.h, annotator, prims, flags, out_planes, out_pitches, out_pinned)
 
     def drain(self):
         lib().rd_detector_drain(self.h)
@@ -488,6 +538,10 @@ class PolylineDetector:
         """as Detector.rectify_polled"""
         return _rectify_polled(self.h, rectifier, quads, out, out_pinned)
 
+    def annotate_polled(self, annotator, prims, flags=0, out_planes=None, out_pitches=None, out_pinned=False):
+        """as Detector.annotate_polled"""
+        return _annotate_polled(self.h, annotator, prims, flags, out_planes, out_pitches, out_pinned)
+
     def drain(self):
         lib().rd_detector_drain(self.h)
 
@@ -576,6 +630,85 @@ class Rectifier:
     def close(self):
         if self.h:
             lib().rd_rectifier_destroy(self.h)
+            self.h = None
+
+
+def annot_limits():
+    """{"tile_w", "tile_h", "chunk"} of the annotator's kernel (rd_annot_limits); runs without a GPU"""
+    out = np.zeros(4, np.int32)
+    lib().rd_annot_limits(out.ctypes.data)
+    return {"tile_w": int(out[0]), "tile_h": int(out[1]), "chunk": int(out[2])}
+
+
+def annot_rects(rects, scale=1, style=None):
+    """the six primitives per rectangle of a RECT_DTYPE array in showRect's order (rd_annot_rects); style: 4 x (b, g, r, thickness) by status, None: vidrect.cpp's"""
+    a = np.ascontiguousarray(rects, dtype=RECT_DTYPE).reshape(-1)
+    out = np.zeros(6 * len(a), PRIM_DTYPE)
+    st = None if style is None else np.ascontiguousarray(style, dtype=np.uint8).reshape(16)
+    n = lib().rd_annot_rects(a.ctypes.data, len(a), int(scale), None if st is None else st.ctypes.data, out.ctypes.data)
+    return out[:n].copy()
+
+
+def annot_segments(segs, mode=ANNOT_SEG_ALL, scale=1, max_prims=None):
+    """the primitives of an LS_DTYPE list WITH its header record (PolylineDetector.poll, Detector.last_segments): ANNOT_SEG_ALL as vidpoly.cpp draws them,
+    ANNOT_SEG_CHAINS as poly.cpp does (rd_annot_segments); at most max_prims of them"""
+    a = np.ascontiguousarray(segs, dtype=LS_DTYPE).reshape(-1)
+    n = lib().rd_annot_segments(a.ctypes.data, int(mode), int(scale), None, 0)
+    if max_prims is not None:
+        n = min(n, int(max_prims))
+    out = np.zeros(n, PRIM_DTYPE)
+    lib().rd_annot_segments(a.ctypes.data, int(mode), int(scale), out.ctypes.data, n)
+    return out
+
+
+class Annotator:
+    """The rd_annotator extension: up to max_prims primitives per job drawn into a frame on the device, njobs jobs in flight (the contract: include/rectdetect_hip.h)."""
+
+    def __init__(self, max_prims=4096, njobs=2, device=0):
+        L = lib()
+        if L.rd_device_count() <= 0:
+            raise RuntimeError("rectdetect_amd: no HIP device visible - there is no CPU fallback")
+        self.max_prims, self.njobs = max_prims, njobs
+        self.h = L.rd_annotator_create(device, max_prims, njobs)
+        if not self.h:
+            raise ValueError("rd_annotator_create: invalid arguments (%r)" % ((device, max_prims, njobs),))
+
+    def enqueue(self, fmt, planes, pitches, iw, ih, prims, flags=0, out_planes=None, out_pitches=None, on_device=False, pinned=False, out_pinned=False):
+        """one job: `prims` (PRIM_DTYPE) into an iw x ih frame in format fmt (PIX_*).  planes / pitches as Detector.enqueue_planes: numpy planes (copied before the call
+        returns; pitches may be None), or with on_device / pinned their addresses.  out_planes None: in place (device frames only); otherwise the ADDRESSES of the
+        destination's planes in device memory or, with out_pinned, in pinned host memory, and their out_pitches.  Returns the job's sequence number; ValueError on an
+        argument error (nothing enqueued)."""
+        ptrs, pitch_c, kind, pitch, _ = _plane_args(planes, pitches, on_device, pinned)
+        p, n = _prims_arg(prims)
+        optrs, opitch = _out_args(out_planes, out_pitches)
+        r = lib().rd_annotator_enqueue(self.h, int(fmt), ptrs, pitch_c, int(iw), int(ih), kind, p.ctypes.data, n, int(flags), optrs, opitch, 2 if out_pinned else 1)
+        if r == -1:
+            raise ValueError("rd_annotator_enqueue: invalid arguments (format %r, pitches %r, %dx%d, %d primitives, flags %r)" % (fmt, pitch, iw, ih, n, flags))
+        return r
+
+    def wait(self):
+        """blocks until the oldest job is done: its number of primitives"""
+        n = lib().rd_annotator_wait(self.h)
+        if n < 0:
+            raise RuntimeError("rd_annotator_wait: no job in flight")
+        return n
+
+    def annotate(self, frame_bgr, prims, flags=0):
+        """convenience: a numpy BGR image with `prims` drawn into it, as a new array, through pinned memory (one job, waited for)"""
+        a = np.asarray(frame_bgr, dtype=np.uint8)
+        ih, iw = a.shape[:2]
+        nbytes = ih * iw * 3
+        p = lib().rd_host_alloc(nbytes)
+        try:
+            self.enqueue(PIX_BGR, a, None, iw, ih, prims, flags, out_planes=(p,), out_pitches=(iw * 3,), out_pinned=True)
+            self.wait()
+            return np.frombuffer((ctypes.c_uint8 * nbytes).from_address(p), np.uint8).reshape(ih, iw, 3).copy()
+        finally:
+            lib().rd_host_free(p)
+
+    def close(self):
+        if self.h:
+            lib().rd_annotator_destroy(self.h)
             self.h = None
 
 

@@ -1590,6 +1590,18 @@ long rd_detector_rectify_polled(rd_detector *d, rd_rectifier *r, const double *q
   return rd_rectifier_enqueue(r, s->fmt, planes, s->pitch, s->scale == 2 ? 2 * d->iw : d->iw, s->scale == 2 ? 2 * d->ih : d->ih, RD_FRAME_DEVICE, quads, n, out, out_kind);
 }
 
+// Annotated frames (rd_annotate.hip) on the frame of the most recently polled slot, at the size it came in.  A caller's device frame may be drawn into in place; a host or
+// pinned frame lies in the slot's own buffer (bgr, or sc_bgr at scale 2), which the rectifier reads and nothing may change: such a job needs a destination.
+long rd_detector_annotate_polled(rd_detector *d, rd_annotator *a, const rd_annot_prim *prims, int n, int flags, void *const out_planes[3], const int out_pitches[3], int out_kind) {
+  if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_annotate_polled: bad handle\n");
+  if (d->last_polled_slot < 0 || rdrt::annotator_device(a) != d->device) return -1;
+  const Slot *s = &d->slots[d->last_polled_slot];
+  const bool own = s->pl[0] == s->bgr || (s->sc_bgr && s->pl[0] == s->sc_bgr);
+  if (own && !out_planes) return -1;
+  const void *const planes[3] = { s->pl[0], s->pl[1], s->pl[2] };
+  return rd_annotator_enqueue(a, s->fmt, planes, s->pitch, s->scale == 2 ? 2 * d->iw : d->iw, s->scale == 2 ? 2 * d->ih : d->ih, RD_FRAME_DEVICE, prims, n, flags, out_planes, out_pitches, out_kind);
+}
+
 // The reference hands the aperture over with the poll, i.e. after the frame (oclrect_pollTask); whatever runs ahead of the poll - the
 // worker threads' post-process, the rectangles on the device - uses the last one seen.  A caller that knows it beforehand says so here,
 // and the first frames of a stream are treated like all later ones.

@@ -34,6 +34,7 @@ struct _cl_kernel { int dummy; };
   } while (0)
 
 struct rd_rectifier;
+struct rd_annotator;
 
 namespace rdrt {
 inline void *dptr(cl_mem m) {
@@ -52,4 +53,5 @@ void check_launch(const char *what);
 int current_device();
 int rectifier_device(const rd_rectifier *r);      // rd_rectify.hip: the device a rectifier lives on (-1: not a rectifier)
 int rectifier_max_quads(const rd_rectifier *r);   // rd_rectify.hip: the most quads one of its jobs takes (-1: not a rectifier)
+int annotator_device(const rd_annotator *a);      // rd_annotate.hip: the device an annotator lives on (-1: not an annotator)
 }  // namespace rdrt

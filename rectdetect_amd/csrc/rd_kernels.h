@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include "rd_annot_cover.h"
 
 // Group launches (small frames, rd_api.hip): launchers of the frame path take `nz` frames per launch and `zs`, the byte pitch between the planes
 // of consecutive frame slots (rd_device.h: RD_ZSHIFT); the defaults launch one frame.
@@ -150,5 +151,14 @@ void polyline_ids(hipStream_t s, const PolyFrame *frames, int nb, int n);
 struct RectifyQuad { double c[8]; int status; int pad; };
 // n patches of pw x ph BGR pixels, patch k at out + k * pw * ph * 3, from one iw x ih frame in format fmt (RD_PIX_*; planes / pitch as the caller's), one launch (quad = blockIdx.z)
 void rectify(hipStream_t s, uint8_t *out, int fmt, const uint8_t *const planes[3], const int pitch[3], int iw, int ih, const RectifyQuad *quads, int n, int pw, int ph);
+
+// ---- rd_k_annotate.hip: annotated frames (the contract: rectdetect_hip.h, "annotated frames")
+// what a job uploads per primitive: its line record (rd_annot_cover.h) and its colour - the three bytes a covered pixel gets, in the order the frame's format
+// stores them (BGR / BGRA: b, g, r; RGB / RGBA: r, g, b; NV12 / I420: y, u, v of rd_annot_yuv) - as col = c0 | c1 << 8 | c2 << 16
+struct AnnotRec { rd_annot_line L; uint32_t col; uint32_t pad; };
+enum { ANNOT_TILE_W = 64, ANNOT_TILE_H = 32, ANNOT_CHUNK = 256 };      // a block's tile of pixels; primitives tested per pass = records of the tile's list in LDS at a time
+// n primitives drawn into one iw x ih frame in format fmt, one launch, one block per tile.  dst == src plane by plane: in place (only covered pixels are written,
+// with clear every pixel); otherwise every pixel of dst is written once: the source's, black, or a primitive's colour.  clear: RD_ANNOT_CLEAR.
+void annotate(hipStream_t s, int fmt, uint8_t *const dst[3], const int dpitch[3], const uint8_t *const src[3], const int spitch[3], int iw, int ih, const AnnotRec *recs, int n, int clear);
 
 }  // namespace rdk
