@@ -351,6 +351,105 @@ int rd_annotator_wait(rd_annotator *a);
 long rd_detector_annotate_polled(rd_detector *d, rd_annotator *a, const rd_annot_prim *prims, int n, int flags,
                                  void *const out_planes[3], const int out_pitches[3], int out_kind);
 
+/* ---- composited quads: a colour or an image written INTO every quad of a frame on the device (rd_k_composite.hip, rd_composite.hip, rd_comp_host.c) - redaction
+ * (fill every detected screen) and replacement (put an image into every detected rectangle) for frames that never leave HBM.  The exact inverse of the rectifier:
+ * the same quad convention, the same patch layout, the same eight coefficients.  The arithmetic is defined here, exactly, so that an independent restatement
+ * (tests/composite.py, numpy float64) reproduces every byte.
+ *
+ * An item is a quad with either a colour or the number of a patch.  `quad`: four corners in PATCH ORDER in the coordinates of rect_t::c2, exactly as for the
+ * rectifier - where the corners (0,0) (1,0) (1,1) (0,1) of the unit square land; rd_rect_quads makes them.  patch >= 0: paste patch number `patch` of the job's patch
+ * array - npatches images of pw x ph pixels of 3 bytes B, G, R, rows back to back, patch k at k * pw * ph * 3: the layout rd_rectifier writes.  patch == -1: fill with
+ * (b, g, r).  Any other negative value, or patch >= npatches, is an argument error.
+ *
+ * Per item - once, on the host, IEEE double, exactly these operations, no contraction (rd_composite_coefficients):
+ *   a .. h and validity from rd_rectify_coefficients, unchanged (finite corners, strictly convex in either orientation, finite coefficients).
+ *   The adjugate of the map's matrix:
+ *     A = e - f*h;   B = c*h - b;   C = b*f - c*e
+ *     D = f*g - d;   E = a - c*g;   F = c*d - a*f
+ *     G = d*h - e*g; H = b*g - a*h; I = a*e - b*d                          inv[9] = { A, B, C, D, E, F, G, H, I }
+ *   An item is also INVALID when one of the nine is not finite.  An invalid item has status 0 and writes nothing.
+ *   The pixel box, in double:  fl = floor(min x_i) - 1.0;  ce = ceil(max x_i) + 1.0.  The box is EMPTY when ce < 0.0 or fl > iw-1 (compared in double); otherwise
+ *     bx0 = (int)max(fl, 0.0);  bx1 = (int)min(ce, (double)(iw-1))         (by0, by1 the same from y and ih)
+ *   An item with an empty box is valid and covers nothing.  box[4] = { bx0, by0, bx1, by1 }; an empty box, and the box of an invalid item, is { 0, 0, -1, -1 }.
+ *
+ * Per frame pixel (X, Y) - on the device, in double, uncontracted, in this order:
+ *   wn = (G*X + H*Y) + I
+ *   s  = ((A*X + B*Y) + C) / wn;   t = ((D*X + E*Y) + F) / wn
+ *   covered  <=>  bx0 <= X <= bx1  and  by0 <= Y <= by1  and  s >= 0.0  and  s < 1.0  and  t >= 0.0  and  t < 1.0
+ * A NaN or an infinity fails the comparisons: such a pixel is not covered.  s and t are rounded values: two quads that share an edge may BOTH claim a pixel centre that
+ * lies on it, or NEITHER may - away from edges (further than the rounding of the map, far below 1e-6 pixel for quads of a frame's size) coverage is the inside test.
+ *   Fill:  the pixel's colour is (b, g, r).
+ *   Paste: u = s*pw - 0.5;  v = t*ph - 0.5;  ui = floor(u * 256.0) clamped in double to [0, (pw-1)*256] - anything not above 0, a NaN too, gives 0 - then an integer
+ *          (vi the same with ph);  x0 = ui >> 8;  fx = ui & 255;  x1 = min(x0+1, pw-1)  (y0, fy, y1 the same) and per channel, in int32, with p(x, y) the channel's
+ *          byte of patch pixel (x, y):  top = p(x0,y0)*(256-fx) + p(x1,y0)*fx;  bot = p(x0,y1)*(256-fx) + p(x1,y1)*fx;  out = (top*(256-fy) + bot*fy + 32768) >> 16
+ *          - the rectifier's blend over the patch's bytes.
+ * With the axis-aligned quad (x0-0.5, y0-0.5) (x0+N-0.5, y0-0.5) (x0+N-0.5, y0+N-0.5) (x0-0.5, y0+N-0.5) and pw = ph = N a power of two, coverage is exactly the N x N
+ * pixels, u and v are the integer column and row, and rectify followed by composite reproduces the frame's bytes.
+ *
+ * Painter's order: where several items of a job cover a pixel, the one with the HIGHEST index wins.  The result is a function of the job alone, never of scheduling.
+ *
+ * Formats: all six RD_PIX_*.  Packed formats: the pixel's B, G, R bytes, in the format's order, are written; A never is.  NV12 and I420 (even iw and ih, as
+ * elsewhere): the luma of a covered pixel is Y of its final colour (rd_annot_yuv).  A chroma sample is written when n >= 1 of its four luma pixels are covered: with
+ * S_c the sum of channel c over those n pixels' final colours, M_c = (S_c + n/2) / n in integer division, and U, V are those of rd_annot_yuv(M_b, M_g, M_r).  A
+ * sample none of whose four pixels is covered stays as it is.
+ *
+ * IN PLACE only covered pixels are written, and no pixel is ever read: there is no alpha and no read-modify-write.  A job into ANOTHER frame is the in-place job on
+ * a copy of the source's pixels, with the annotator's rules: the source is unchanged, every pixel of the destination is written (all bytes of a pixel, A included,
+ * travel with it), pitch padding and bytes behind the planes are never written.
+ *
+ * Out of scope: alpha blending; anti-aliased edges; patches in formats other than BGR; a mosaic of the frame's own pixels.  For the last the supported route is to
+ * rectify the quad into a small patch, 8 x 8 for example, and paste it back: a redaction that never leaves the device (examples/rdredact.c, "mosaic"). */
+typedef struct { double quad[8]; int32_t patch; uint8_t b, g, r, pad; } rd_comp_item;   /* 72 bytes */
+
+/* host taps; none needs a GPU */
+/* the adjugate, the pixel box and the status of one quad in an iw x ih frame as above - what a job uploads per item.  Invalid: zeros, the empty box, status 0. */
+void rd_composite_coefficients(const double quad[8], int iw, int ih, double inv[9], int32_t box[4], int *status);
+/* 1 when the quad covers pixel (x, y) of an iw x ih frame, else 0: the per-pixel test on the host, in the same operations.  st != NULL: st[0] = s, st[1] = t when
+ * the quad is valid and its box holds the pixel, else zeros. */
+int rd_composite_covers(const double quad[8], int iw, int ih, int x, int y, double st[2]);
+/* The tiles an in-place job of these items launches: the union of the valid items' boxes in tiles of rd_comp_limits' width and height (tile (tx, ty) starts at pixel
+ * (tx * width, ty * height)), each once, in raster order.  Writes up to max pairs tx, ty to tiles_xy (may be NULL with max 0) and returns how many there are, which may
+ * exceed max; -1 for iw or ih < 1 or > 65536, n < 0 or n > 0 with items NULL.  Only the quads are looked at. */
+int rd_composite_tiles(const rd_comp_item *items, int n, int iw, int ih, int32_t *tiles_xy, int max);
+/* out[0], out[1]: width and height of the tile of pixels one wave composites (both even), out[2]: items whose boxes a wave tests per pass (any number of items up to
+ * max_items may overlap one tile: no other capacity exists), out[3] = 0 */
+void rd_comp_limits(int32_t out[4]);
+
+/* A compositor writes up to max_items items per job, pasting patches of pw x ph pixels, up to njobs jobs in flight, on one stream of its own.  NULL on bad arguments
+ * (pw, ph, max_items or njobs < 1, pw or ph > 16384, max_items > 1048576, njobs > 1024, no such device). */
+typedef struct rd_compositor rd_compositor;
+rd_compositor *rd_compositor_create(int device, int pw, int ph, int max_items, int njobs);
+void rd_compositor_destroy(rd_compositor *c);      /* waits for the jobs in flight */
+/* One job: n items into one iw x ih frame in pixel format `format` (planes / pitches as for rd_detector_enqueue_planes).  The items are validated and turned into
+ * device records before the call returns; the caller may reuse the array.
+ * out_planes == NULL: in place - on_device must be RD_FRAME_DEVICE; the frame is the caller's until the job's wait.
+ * otherwise: the source - RD_FRAME_HOST (copied before the call returns), RD_FRAME_DEVICE or RD_FRAME_HOST_PINNED (memory that is not pinned is fatal) - is not
+ *   modified and the frame goes to out_planes / out_pitches, memory of kind out_kind: RD_FRAME_DEVICE or RD_FRAME_HOST_PINNED (through a device buffer of the
+ *   compositor, which grows on demand).  Device and pinned sources, and the output, stay valid until the job's wait returned.  Source and destination must not overlap.
+ * patches / npatches / patches_kind: the patch array the items' `patch` numbers refer to - RD_FRAME_DEVICE (read in place until the job's wait), RD_FRAME_HOST_PINNED
+ *   (the copy engine brings it into a device buffer of the compositor, which grows on demand; valid until the job's wait; memory that is not pinned is fatal) or
+ *   RD_FRAME_HOST (copied before the call returns).  A job of fills alone may pass NULL and 0.
+ * Returns the job's sequence number, or -1 with nothing enqueued for an argument error: the annotator's - an unknown format, on_device or out_kind, iw or ih < 1 or
+ * > 65536, a NULL plane the format uses (source or output), a pitch smaller than its plane's row (source or output), NV12 / I420 with an odd iw or ih, n < 0,
+ * n > max_items, n > 0 with items NULL, in place with a frame that is not on the device, an output plane that is not memory of the kind out_kind names - and an item
+ * whose `patch` is below -1 or not below npatches, npatches < 0, and, while some item pastes, patches NULL, an unknown patches_kind or patches of kind RD_FRAME_DEVICE
+ * that are not device memory.  A call with njobs jobs already in flight is fatal, as it is for the annotator.
+ * An in-place job on a frame that a rectifier job reads must follow that job's rd_rectifier_wait: the two objects have streams of their own. */
+long rd_compositor_enqueue(rd_compositor *c, int format, const void *const planes[3], const int pitches[3], int iw, int ih, int on_device,
+                           const rd_comp_item *items, int n, const void *patches, int npatches, int patches_kind,
+                           void *const out_planes[3], const int out_pitches[3], int out_kind);
+/* the oldest job: blocks until the frame is where it was told to go, returns its n and writes the n status bytes (1 valid, 0 invalid: nothing written) to status_out
+ * when that is not NULL.  -1: no job in flight. */
+int rd_compositor_wait(rd_compositor *c, uint8_t *status_out);
+/* One job on the frame of the most recently polled slot of d (either kind of detector): its planes, pitches and format as they were handed over, at the SOURCE's size.
+ * A frame that came in at scale 2 (rd_detector_enqueue_scaled): the items' quads in DETECTOR coordinates - what rd_rect_quads gives for that frame's rectangles - each
+ * corner mapped on the host, in double, X = x * 2.0 + 0.5, Y = y * 2.0 + 0.5, as rd_detector_rectify_polled maps them; the job runs on the full-size source.  A device
+ * frame: in place (out_planes NULL) or into out_planes.  A host or pinned frame: the source is the copy the detector uploaded, which must stay what the rectifier
+ * reads, so out_planes is required (-1 without); that copy lasts until the next enqueue on d: wait for the job first.  Returns as rd_compositor_enqueue; -1 also when
+ * nothing has been polled yet or d and c are on different devices. */
+long rd_detector_composite_polled(rd_detector *d, rd_compositor *c, const rd_comp_item *items, int n, const void *patches, int npatches, int patches_kind,
+                                  void *const out_planes[3], const int out_pitches[3], int out_kind);
+
 /* ---- synthetic frames (csrc/rd_synth.c) */
 int rd_synth_num_quads(int iw, int ih);
 void rd_synth_frame(uint8_t *bgr, int iw, int ih, int ws, uint64_t seed, int t, int noise);

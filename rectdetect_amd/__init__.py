@@ -29,6 +29,8 @@ LS_DTYPE = np.dtype([("x0", "<f4"), ("y0", "<f4"), ("x1", "<f4"), ("y1", "<f4"),
 PRIM_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("thickness", "u1")])
 assert RECT_DTYPE.itemsize == 176 and LS_DTYPE.itemsize == 56 and PRIM_DTYPE.itemsize == 20
 ANNOT_CLEAR = 1
+COMP_ITEM_DTYPE = np.dtype([("quad", "<f8", (4, 2)), ("patch", "<i4"), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("pad", "u1")])      # rd_comp_item, 72 bytes
+COMP_FILL = -1
 ANNOT_SEG_ALL, ANNOT_SEG_CHAINS = 0, 1
 
 # pixel formats of enqueue_planes (rd_detector_enqueue_planes; the conversion contract is in include/rectdetect_hip.h)
@@ -110,6 +112,16 @@ def _declare(L):
         "rd_annotator_enqueue": (ctypes.c_long, [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ci, ci, vp, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci]),
         "rd_annotator_wait": (ci, [vp]),
         "rd_detector_annotate_polled": (ctypes.c_long, [vp, vp, vp, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci]),
+        # composited quads (rd_composite.hip, rd_comp_host.c)
+        "rd_composite_coefficients": (None, [vp, ci, ci, vp, vp, ctypes.POINTER(ci)]),
+        "rd_composite_covers": (ci, [vp, ci, ci, ci, ci, vp]),
+        "rd_composite_tiles": (ci, [vp, ci, ci, ci, vp, ci]),
+        "rd_comp_limits": (None, [vp]),
+        "rd_compositor_create": (vp, [ci, ci, ci, ci, ci]),
+        "rd_compositor_destroy": (None, [vp]),
+        "rd_compositor_enqueue": (ctypes.c_long, [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ci, ci, vp, ci, vp, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci]),
+        "rd_compositor_wait": (ci, [vp, vp]),
+        "rd_detector_composite_polled": (ctypes.c_long, [vp, vp, vp, ci, vp, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci]),
         "rd_synth_frame": (None, [vp, ci, ci, ci, ctypes.c_uint64, ci, ci]),
         "rd_synth_num_quads": (ci, [ci, ci]),
         # reference API (oclhelper.h / raw cl*)
@@ -404,6 +416,38 @@ def _annotate_polled(h, annotator, prims, flags, out_planes, out_pitches, out_pi
     return r
 
 
+def _items_arg(items):
+    p = np.ascontiguousarray(items, dtype=COMP_ITEM_DTYPE).reshape(-1)
+    return p, len(p)
+
+
+def _patches_arg(patches, patches_on_device, patches_pinned):
+    """(pointer, number of patches or None, kind, array to keep alive) of a compositor's patch array: None, a numpy (n, ph, pw, 3) uint8 array (copied before the call
+    returns), or with patches_on_device / patches_pinned an (ADDRESS, n) pair"""
+    if patches is None:
+        return None, 0, 0, None
+    if patches_on_device or patches_pinned:
+        addr, n = patches
+        return (int(addr) if addr else None), int(n), 1 if patches_on_device else 2, None
+    a = np.ascontiguousarray(patches, dtype=np.uint8)
+    if a.ndim != 4 or a.shape[3] != 3:
+        raise ValueError("composite: host patches are an (n, ph, pw, 3) uint8 array, not %r" % (a.shape,))
+    return a.ctypes.data, None, 0, a
+
+
+def _composite_polled(h, compositor, items, patches, out_planes, out_pitches, out_pinned, patches_on_device, patches_pinned):
+    it, n = _items_arg(items)
+    pp, npatches, pkind, keep = _patches_arg(patches, patches_on_device, patches_pinned)
+    if keep is not None:
+        compositor._check_patches(keep)
+        npatches = len(keep)
+    optrs, opitch = _out_args(out_planes, out_pitches)
+    r = lib().rd_detector_composite_polled(h, compositor.h, it.ctypes.data, n, pp, npatches, pkind, optrs, opitch, 2 if out_pinned else 1)
+    if r == -1:
+        raise ValueError("rd_detector_composite_polled: invalid arguments (nothing polled yet, a host frame without out_planes, %d items, %d patches)" % (n, npatches))
+    return r
+
+
 class Detector:
     """The rd_detector extension: frames may already live in HBM, several frames in flight."""
 
@@ -449,6 +493,12 @@ class Detector:
         annotator.wait()): a device frame in place, or with out_planes / out_pitches - ADDRESSES of device planes or, with out_pinned, of pinned host planes - into
         another frame; a host frame needs out_planes.  A frame that came in at scale 2 is annotated at its source size.  ValueError on an argument error."""
         return _annotate_polled(self.h, annotator, prims, flags, out_planes, out_pitches, out_pinned)
+
+    def composite_polled(self, compositor, items, patches=None, out_planes=None, out_pitches=None, out_pinned=False, patches_on_device=False, patches_pinned=False):
+        """`items` (COMP_ITEM_DTYPE; comp_items makes them) composited into the frame of the most recently polled slot as one job of `compositor` (take it with
+        compositor.wait()): a device frame in place, or with out_planes / out_pitches into another frame; a host frame needs out_planes.  patches as
+        Compositor.enqueue.  A frame that came in at scale 2 takes quads in detector coordinates and is composited at its source size.  ValueError on an argument error."""
+        return _composite_polled(self.h, compositor, items, patches, out_planes, out_pitches, out_pinned, patches_on_device, patches_pinned)
 
     def drain(self):
         lib().rd_detector_drain(self.h)
@@ -541,6 +591,10 @@ class PolylineDetector:
     def annotate_polled(self, annotator, prims, flags=0, out_planes=None, out_pitches=None, out_pinned=False):
         """as Detector.annotate_polled"""
         return _annotate_polled(self.h, annotator, prims, flags, out_planes, out_pitches, out_pinned)
+
+    def composite_polled(self, compositor, items, patches=None, out_planes=None, out_pitches=None, out_pinned=False, patches_on_device=False, patches_pinned=False):
+        """as Detector.composite_polled"""
+        return _composite_polled(self.h, compositor, items, patches, out_planes, out_pitches, out_pinned, patches_on_device, patches_pinned)
 
     def drain(self):
         lib().rd_detector_drain(self.h)
@@ -709,6 +763,119 @@ class Annotator:
     def close(self):
         if self.h:
             lib().rd_annotator_destroy(self.h)
+            self.h = None
+
+
+def comp_limits():
+    """{"tile_w", "tile_h", "chunk"} of the compositor's kernel (rd_comp_limits); runs without a GPU"""
+    out = np.zeros(4, np.int32)
+    lib().rd_comp_limits(out.ctypes.data)
+    return {"tile_w": int(out[0]), "tile_h": int(out[1]), "chunk": int(out[2])}
+
+
+def comp_items(quads, patch=COMP_FILL, colour=(0, 0, 0)):
+    """COMP_ITEM_DTYPE items of `quads` (n x 8 or n x 4 x 2 doubles, patch order: rect_quads makes them).  patch: one number for all or one per quad (COMP_FILL: fill
+    with `colour`); colour: one (b, g, r) for all or one per quad"""
+    q = np.ascontiguousarray(quads, dtype=np.float64).reshape(-1, 4, 2)
+    out = np.zeros(len(q), COMP_ITEM_DTYPE)
+    out["quad"] = q
+    out["patch"] = patch
+    if len(colour) == 3 and np.ndim(colour[0]) == 0:
+        out["b"], out["g"], out["r"] = colour
+    else:
+        c = np.asarray(colour, np.uint8).reshape(len(q), 3)
+        out["b"], out["g"], out["r"] = c[:, 0], c[:, 1], c[:, 2]
+    return out
+
+
+def composite_coefficients(quad, iw, ih):
+    """(the adjugate A..I as 9 doubles, the pixel box bx0, by0, bx1, by1 as 4 ints, status) of one quad in an iw x ih frame - what a job uploads
+    (rd_composite_coefficients; host only)"""
+    q = np.ascontiguousarray(quad, dtype=np.float64).reshape(8)
+    inv, box, status = np.zeros(9, np.float64), np.zeros(4, np.int32), ctypes.c_int(0)
+    lib().rd_composite_coefficients(q.ctypes.data, int(iw), int(ih), inv.ctypes.data, box.ctypes.data, ctypes.byref(status))
+    return inv, box, status.value
+
+
+def composite_covers(quad, iw, ih, x, y):
+    """(covered?, s, t) of pixel (x, y) of an iw x ih frame under one quad (rd_composite_covers; host only)"""
+    q = np.ascontiguousarray(quad, dtype=np.float64).reshape(8)
+    st = np.zeros(2, np.float64)
+    c = lib().rd_composite_covers(q.ctypes.data, int(iw), int(ih), int(x), int(y), st.ctypes.data)
+    return bool(c), float(st[0]), float(st[1])
+
+
+def composite_tiles(items, iw, ih):
+    """the (m, 2) int32 tiles tx, ty an in-place job of `items` launches, in raster order (rd_composite_tiles; host only)"""
+    it, n = _items_arg(items)
+    m = lib().rd_composite_tiles(it.ctypes.data, n, int(iw), int(ih), None, 0)
+    if m < 0:
+        raise ValueError("rd_composite_tiles: invalid arguments (%d items, %dx%d)" % (n, iw, ih))
+    out = np.zeros((m, 2), np.int32)
+    lib().rd_composite_tiles(it.ctypes.data, n, int(iw), int(ih), out.ctypes.data, m)
+    return out
+
+
+class Compositor:
+    """The rd_compositor extension: up to max_items quads per job filled with a colour or pasted with a pw x ph BGR patch, in a frame on the device, njobs jobs in
+    flight (the contract: include/rectdetect_hip.h)."""
+
+    def __init__(self, pw=64, ph=64, max_items=256, njobs=2, device=0):
+        L = lib()
+        if L.rd_device_count() <= 0:
+            raise RuntimeError("rectdetect_amd: no HIP device visible - there is no CPU fallback")
+        self.pw, self.ph, self.max_items, self.njobs = pw, ph, max_items, njobs
+        self.h = L.rd_compositor_create(device, pw, ph, max_items, njobs)
+        if not self.h:
+            raise ValueError("rd_compositor_create: invalid arguments (%r)" % ((device, pw, ph, max_items, njobs),))
+
+    def _check_patches(self, a):
+        if a.shape[1:] != (self.ph, self.pw, 3):
+            raise ValueError("composite: patches of shape %r for a compositor of %dx%d patches" % (a.shape, self.pw, self.ph))
+
+    def enqueue(self, fmt, planes, pitches, iw, ih, items, patches=None, out_planes=None, out_pitches=None, on_device=False, pinned=False, out_pinned=False,
+                patches_on_device=False, patches_pinned=False):
+        """one job: `items` (COMP_ITEM_DTYPE) into an iw x ih frame in format fmt (PIX_*).  planes / pitches as Detector.enqueue_planes: numpy planes (copied before the
+        call returns; pitches may be None), or with on_device / pinned their addresses.  patches: None (fills only), a numpy (n, ph, pw, 3) uint8 array (copied before
+        the call returns), or with patches_on_device / patches_pinned an (ADDRESS, n) pair.  out_planes None: in place (device frames only); otherwise the ADDRESSES of
+        the destination's planes in device memory or, with out_pinned, in pinned host memory, and their out_pitches.  Returns the job's sequence number; ValueError on
+        an argument error (nothing enqueued)."""
+        ptrs, pitch_c, kind, pitch, _ = _plane_args(planes, pitches, on_device, pinned)
+        it, n = _items_arg(items)
+        pp, npatches, pkind, keep = _patches_arg(patches, patches_on_device, patches_pinned)
+        if keep is not None:
+            self._check_patches(keep)
+            npatches = len(keep)
+        optrs, opitch = _out_args(out_planes, out_pitches)
+        r = lib().rd_compositor_enqueue(self.h, int(fmt), ptrs, pitch_c, int(iw), int(ih), kind, it.ctypes.data, n, pp, npatches, pkind, optrs, opitch, 2 if out_pinned else 1)
+        if r == -1:
+            raise ValueError("rd_compositor_enqueue: invalid arguments (format %r, pitches %r, %dx%d, %d items, %d patches)" % (fmt, pitch, iw, ih, n, npatches))
+        return r
+
+    def wait(self):
+        """blocks until the oldest job is done: its status array (uint8 per item: 1 valid, 0 invalid - nothing written)"""
+        status = np.zeros(self.max_items, np.uint8)
+        n = lib().rd_compositor_wait(self.h, status.ctypes.data)
+        if n < 0:
+            raise RuntimeError("rd_compositor_wait: no job in flight")
+        return status[:n].copy()
+
+    def composite(self, frame_bgr, items, patches=None):
+        """convenience: a numpy BGR image with `items` composited into it, as a new array, through pinned memory (one job, waited for)"""
+        a = np.asarray(frame_bgr, dtype=np.uint8)
+        ih, iw = a.shape[:2]
+        nbytes = ih * iw * 3
+        p = lib().rd_host_alloc(nbytes)
+        try:
+            self.enqueue(PIX_BGR, a, None, iw, ih, items, patches, out_planes=(p,), out_pitches=(iw * 3,), out_pinned=True)
+            self.wait()
+            return np.frombuffer((ctypes.c_uint8 * nbytes).from_address(p), np.uint8).reshape(ih, iw, 3).copy()
+        finally:
+            lib().rd_host_free(p)
+
+    def close(self):
+        if self.h:
+            lib().rd_compositor_destroy(self.h)
             self.h = None
 
 

@@ -2,6 +2,7 @@
 // extension on top of the gfx950 kernels.  C ABI, opaque handles, fatal-on-error like the reference.
 #include "rd_internal.h"
 #include "rd_kernels.h"
+#include "rd_comp.h"
 #include "rd_poly_scratch.h"
 #include "rectdetect_hip.h"
 #include <stdio.h>
@@ -1600,6 +1601,30 @@ long rd_detector_annotate_polled(rd_detector *d, rd_annotator *a, const rd_annot
   if (own && !out_planes) return -1;
   const void *const planes[3] = { s->pl[0], s->pl[1], s->pl[2] };
   return rd_annotator_enqueue(a, s->fmt, planes, s->pitch, s->scale == 2 ? 2 * d->iw : d->iw, s->scale == 2 ? 2 * d->ih : d->ih, RD_FRAME_DEVICE, prims, n, flags, out_planes, out_pitches, out_kind);
+}
+
+// Composited quads (rd_composite.hip) on the frame of the most recently polled slot, at the size it came in; in place or into a destination by the annotator's rule
+// above.  A frame that came in at scale 2: the quads arrive in detector coordinates and are mapped to the source's as rd_detector_rectify_polled maps them.
+long rd_detector_composite_polled(rd_detector *d, rd_compositor *c, const rd_comp_item *items, int n, const void *patches, int npatches, int patches_kind,
+                                  void *const out_planes[3], const int out_pitches[3], int out_kind) {
+  if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_composite_polled: bad handle\n");
+  if (d->last_polled_slot < 0 || rdrt::compositor_device(c) != d->device) return -1;
+  const Slot *s = &d->slots[d->last_polled_slot];
+  const bool own = s->pl[0] == s->bgr || (s->sc_bgr && s->pl[0] == s->sc_bgr);
+  if (own && !out_planes) return -1;
+  const void *const planes[3] = { s->pl[0], s->pl[1], s->pl[2] };
+  if (s->scale == 2 && items && n > 0 && n <= rdrt::compositor_max_items(c)) {
+    rd_comp_item *m = (rd_comp_item *)malloc((size_t)n * sizeof(rd_comp_item));
+    if (!m) exitf(-1, "rd_detector_composite_polled: out of memory\n");
+    memcpy(m, items, (size_t)n * sizeof(rd_comp_item));
+    for (int k = 0; k < n; k++)
+      for (int i = 0; i < 8; i++) m[k].quad[i] = items[k].quad[i] * 2.0 + 0.5;
+    const long q = rd_compositor_enqueue(c, s->fmt, planes, s->pitch, 2 * d->iw, 2 * d->ih, RD_FRAME_DEVICE, m, n, patches, npatches, patches_kind, out_planes, out_pitches, out_kind);
+    free(m);      // (the job holds its records: rd_compositor_enqueue makes them before it returns)
+    return q;
+  }
+  return rd_compositor_enqueue(c, s->fmt, planes, s->pitch, s->scale == 2 ? 2 * d->iw : d->iw, s->scale == 2 ? 2 * d->ih : d->ih, RD_FRAME_DEVICE, items, n, patches, npatches, patches_kind,
+                               out_planes, out_pitches, out_kind);
 }
 
 // The reference hands the aperture over with the poll, i.e. after the frame (oclrect_pollTask); whatever runs ahead of the poll - the
