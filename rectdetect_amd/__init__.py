@@ -381,14 +381,6 @@ def _quads_arg(quads):
     return q, len(q)
 
 
-def _rectify_polled(h, rectifier, quads, out, out_pinned):
-    q, n = _quads_arg(quads)
-    r = lib().rd_detector_rectify_polled(h, rectifier.h, q.ctypes.data, n, int(out) if out else None, 2 if out_pinned else 1)
-    if r == -1:
-        raise ValueError("rd_detector_rectify_polled: invalid arguments (nothing polled yet, %d quads, out %r)" % (n, out))
-    return r
-
-
 def _prims_arg(prims):
     p = np.ascontiguousarray(prims, dtype=PRIM_DTYPE).reshape(-1)
     return p, len(p)
@@ -407,48 +399,49 @@ def _out_args(out_planes, out_pitches):
     return (ctypes.c_void_p * 3)(*(ptrs + [None] * (3 - len(ptrs)))), (ctypes.c_int * 3)(*(pitch + [0] * (3 - len(pitch))))
 
 
-def _annotate_polled(h, annotator, prims, flags, out_planes, out_pitches, out_pinned):
-    p, n = _prims_arg(prims)
-    optrs, opitch = _out_args(out_planes, out_pitches)
-    r = lib().rd_detector_annotate_polled(h, annotator.h, p.ctypes.data, n, int(flags), optrs, opitch, 2 if out_pinned else 1)
-    if r == -1:
-        raise ValueError("rd_detector_annotate_polled: invalid arguments (nothing polled yet, a host frame without out_planes, %d primitives, flags %r)" % (n, flags))
-    return r
-
-
 def _items_arg(items):
     p = np.ascontiguousarray(items, dtype=COMP_ITEM_DTYPE).reshape(-1)
     return p, len(p)
 
 
-def _patches_arg(patches, patches_on_device, patches_pinned):
-    """(pointer, number of patches or None, kind, array to keep alive) of a compositor's patch array: None, a numpy (n, ph, pw, 3) uint8 array (copied before the call
-    returns), or with patches_on_device / patches_pinned an (ADDRESS, n) pair"""
-    if patches is None:
-        return None, 0, 0, None
-    if patches_on_device or patches_pinned:
-        addr, n = patches
-        return (int(addr) if addr else None), int(n), 1 if patches_on_device else 2, None
-    a = np.ascontiguousarray(patches, dtype=np.uint8)
-    if a.ndim != 4 or a.shape[3] != 3:
-        raise ValueError("composite: host patches are an (n, ph, pw, 3) uint8 array, not %r" % (a.shape,))
-    return a.ctypes.data, None, 0, a
+class _PolledJobs:
+    """what both detector kinds forward to the services behind their poll: one job on the frame of the most recently polled slot"""
+
+    def rectify_polled(self, rectifier, quads, out, out_pinned=False):
+        """patches of `quads` (n x 8 or n x 4 x 2 doubles, patch order) from the frame of the most recently polled slot into `out` - the ADDRESS of device memory or,
+        with out_pinned, of pinned host memory - as one job of `rectifier` (take it with rectifier.wait()); a host frame is read from the detector's own copy,
+        which lasts until the next enqueue here.  ValueError on an argument error (nothing enqueued)."""
+        q, n = _quads_arg(quads)
+        r = lib().rd_detector_rectify_polled(self.h, rectifier.h, q.ctypes.data, n, int(out) if out else None, 2 if out_pinned else 1)
+        if r == -1:
+            raise ValueError("rd_detector_rectify_polled: invalid arguments (nothing polled yet, %d quads, out %r)" % (n, out))
+        return r
+
+    def annotate_polled(self, annotator, prims, flags=0, out_planes=None, out_pitches=None, out_pinned=False):
+        """`prims` (PRIM_DTYPE; annot_rects / annot_segments make them) drawn into the frame of the most recently polled slot as one job of `annotator` (take it with
+        annotator.wait()): a device frame in place, or with out_planes / out_pitches - ADDRESSES of device planes or, with out_pinned, of pinned host planes - into
+        another frame; a host frame needs out_planes.  A frame that came in at scale 2 is annotated at its source size.  ValueError on an argument error."""
+        p, n = _prims_arg(prims)
+        optrs, opitch = _out_args(out_planes, out_pitches)
+        r = lib().rd_detector_annotate_polled(self.h, annotator.h, p.ctypes.data, n, int(flags), optrs, opitch, 2 if out_pinned else 1)
+        if r == -1:
+            raise ValueError("rd_detector_annotate_polled: invalid arguments (nothing polled yet, a host frame without out_planes, %d primitives, flags %r)" % (n, flags))
+        return r
+
+    def composite_polled(self, compositor, items, patches=None, out_planes=None, out_pitches=None, out_pinned=False, patches_on_device=False, patches_pinned=False):
+        """`items` (COMP_ITEM_DTYPE; comp_items makes them) composited into the frame of the most recently polled slot as one job of `compositor` (take it with
+        compositor.wait()): a device frame in place, or with out_planes / out_pitches into another frame; a host frame needs out_planes.  patches as
+        Compositor.enqueue.  A frame that came in at scale 2 takes quads in detector coordinates and is composited at its source size.  ValueError on an argument error."""
+        it, n = _items_arg(items)
+        pp, npatches, pkind, _ = compositor._patches(patches, patches_on_device, patches_pinned)
+        optrs, opitch = _out_args(out_planes, out_pitches)
+        r = lib().rd_detector_composite_polled(self.h, compositor.h, it.ctypes.data, n, pp, npatches, pkind, optrs, opitch, 2 if out_pinned else 1)
+        if r == -1:
+            raise ValueError("rd_detector_composite_polled: invalid arguments (nothing polled yet, a host frame without out_planes, %d items, %d patches)" % (n, npatches))
+        return r
 
 
-def _composite_polled(h, compositor, items, patches, out_planes, out_pitches, out_pinned, patches_on_device, patches_pinned):
-    it, n = _items_arg(items)
-    pp, npatches, pkind, keep = _patches_arg(patches, patches_on_device, patches_pinned)
-    if keep is not None:
-        compositor._check_patches(keep)
-        npatches = len(keep)
-    optrs, opitch = _out_args(out_planes, out_pitches)
-    r = lib().rd_detector_composite_polled(h, compositor.h, it.ctypes.data, n, pp, npatches, pkind, optrs, opitch, 2 if out_pinned else 1)
-    if r == -1:
-        raise ValueError("rd_detector_composite_polled: invalid arguments (nothing polled yet, a host frame without out_planes, %d items, %d patches)" % (n, npatches))
-    return r
-
-
-class Detector:
+class Detector(_PolledJobs):
     """The rd_detector extension: frames may already live in HBM, several frames in flight."""
 
     def __init__(self, iw, ih, device=0, nslots=2, nworkers=0, aperture=None):
@@ -481,24 +474,6 @@ class Detector:
 
     def poll(self, tan_aov):
         return _take_rects(lib().rd_detector_poll(self.h, float(tan_aov)))
-
-    def rectify_polled(self, rectifier, quads, out, out_pinned=False):
-        """patches of `quads` (n x 8 or n x 4 x 2 doubles, patch order) from the frame of the most recently polled slot into `out` - the ADDRESS of device memory or,
-        with out_pinned, of pinned host memory - as one job of `rectifier` (take it with rectifier.wait()); a host frame is read from the detector's own copy,
-        which lasts until the next enqueue here.  ValueError on an argument error (nothing enqueued)."""
-        return _rectify_polled(self.h, rectifier, quads, out, out_pinned)
-
-    def annotate_polled(self, annotator, prims, flags=0, out_planes=None, out_pitches=None, out_pinned=False):
-        """`prims` (PRIM_DTYPE; annot_rects / annot_segments make them) drawn into the frame of the most recently polled slot as one job of `annotator` (take it with
-        annotator.wait()): a device frame in place, or with out_planes / out_pitches - ADDRESSES of device planes or, with out_pinned, of pinned host planes - into
-        another frame; a host frame needs out_planes.  A frame that came in at scale 2 is annotated at its source size.  ValueError on an argument error."""
-        return _annotate_polled(self.h, annotator, prims, flags, out_planes, out_pitches, out_pinned)
-
-    def composite_polled(self, compositor, items, patches=None, out_planes=None, out_pitches=None, out_pinned=False, patches_on_device=False, patches_pinned=False):
-        """`items` (COMP_ITEM_DTYPE; comp_items makes them) composited into the frame of the most recently polled slot as one job of `compositor` (take it with
-        compositor.wait()): a device frame in place, or with out_planes / out_pitches into another frame; a host frame needs out_planes.  patches as
-        Compositor.enqueue.  A frame that came in at scale 2 takes quads in detector coordinates and is composited at its source size.  ValueError on an argument error."""
-        return _composite_polled(self.h, compositor, items, patches, out_planes, out_pitches, out_pinned, patches_on_device, patches_pinned)
 
     def drain(self):
         lib().rd_detector_drain(self.h)
@@ -546,7 +521,7 @@ class Detector:
         lib().rd_detector_destroy(self.h)
 
 
-class PolylineDetector:
+class PolylineDetector(_PolledJobs):
     """The polyline kind of rd_detector (rd_polyline_detector_create): the line segments of poly.cpp (strength_thre 500, minerror 1, size_thre 20) or
     vidpoly.cpp (2000, 1, 10) for a stream of frames, several in flight."""
 
@@ -583,18 +558,6 @@ class PolylineDetector:
         segs = np.frombuffer((ctypes.c_char * (56 * (n + 1))).from_address(ptr), dtype=LS_DTYPE).copy()
         _libc.free(ptr)
         return segs, out
-
-    def rectify_polled(self, rectifier, quads, out, out_pinned=False):
-        """as Detector.rectify_polled"""
-        return _rectify_polled(self.h, rectifier, quads, out, out_pinned)
-
-    def annotate_polled(self, annotator, prims, flags=0, out_planes=None, out_pitches=None, out_pinned=False):
-        """as Detector.annotate_polled"""
-        return _annotate_polled(self.h, annotator, prims, flags, out_planes, out_pitches, out_pinned)
-
-    def composite_polled(self, compositor, items, patches=None, out_planes=None, out_pitches=None, out_pinned=False, patches_on_device=False, patches_pinned=False):
-        """as Detector.composite_polled"""
-        return _composite_polled(self.h, compositor, items, patches, out_planes, out_pitches, out_pinned, patches_on_device, patches_pinned)
 
     def drain(self):
         lib().rd_detector_drain(self.h)
@@ -637,17 +600,60 @@ def rectify_coefficients(quad):
     return coef, status.value
 
 
-class Rectifier:
-    """The rd_rectifier extension: pw x ph BGR patches of up to max_quads quads per job, njobs jobs in flight (the contract: include/rectdetect_hip.h)."""
+class _Service:
+    """what Rectifier, Annotator and Compositor share: a handle made by rd_<name>_create whose jobs are waited for oldest first"""
+    _name = None
 
-    def __init__(self, pw, ph, max_quads=64, njobs=2, device=0):
+    def _create(self, *args):
         L = lib()
         if L.rd_device_count() <= 0:
             raise RuntimeError("rectdetect_amd: no HIP device visible - there is no CPU fallback")
-        self.pw, self.ph, self.max_quads, self.njobs = pw, ph, max_quads, njobs
-        self.h = L.rd_rectifier_create(device, pw, ph, max_quads, njobs)
+        self._wait_fn, self._destroy_fn = getattr(L, "rd_%s_wait" % self._name), getattr(L, "rd_%s_destroy" % self._name)
+        self.h = getattr(L, "rd_%s_create" % self._name)(*args)
         if not self.h:
-            raise ValueError("rd_rectifier_create: invalid arguments (%r)" % ((device, pw, ph, max_quads, njobs),))
+            raise ValueError("rd_%s_create: invalid arguments (%r)" % (self._name, args))
+
+    def _wait(self, nstatus=None):
+        """blocks until the oldest job is done: its number of items, or with nstatus - the most a job takes - their status bytes"""
+        if nstatus is None:
+            n = out = self._wait_fn(self.h)
+        else:
+            status = np.zeros(nstatus, np.uint8)
+            n = self._wait_fn(self.h, status.ctypes.data)
+            out = status[:n].copy()
+        if n < 0:
+            raise RuntimeError("rd_%s_wait: no job in flight" % self._name)
+        return out
+
+    def _through_pinned(self, nbytes, enqueue):
+        """the nbytes that one job, waited for, writes to pinned host memory (enqueue(address) makes the job), as a new array"""
+        p = lib().rd_host_alloc(nbytes)
+        try:
+            enqueue(p)
+            self.wait()
+            return np.frombuffer((ctypes.c_uint8 * nbytes).from_address(p), np.uint8).copy()
+        finally:
+            lib().rd_host_free(p)
+
+    def _frame_through_pinned(self, frame_bgr, *job):
+        """a numpy BGR image after one job (what enqueue takes behind iw, ih), as a new array"""
+        a = np.asarray(frame_bgr, dtype=np.uint8)
+        ih, iw = a.shape[:2]
+        return self._through_pinned(ih * iw * 3, lambda p: self.enqueue(PIX_BGR, a, None, iw, ih, *job, out_planes=(p,), out_pitches=(iw * 3,), out_pinned=True)).reshape(ih, iw, 3)
+
+    def close(self):
+        if self.h:
+            self._destroy_fn(self.h)
+            self.h = None
+
+
+class Rectifier(_Service):
+    """The rd_rectifier extension: pw x ph BGR patches of up to max_quads quads per job, njobs jobs in flight (the contract: include/rectdetect_hip.h)."""
+    _name = "rectifier"
+
+    def __init__(self, pw, ph, max_quads=64, njobs=2, device=0):
+        self.pw, self.ph, self.max_quads, self.njobs = pw, ph, max_quads, njobs
+        self._create(device, pw, ph, max_quads, njobs)
 
     def enqueue(self, fmt, planes, pitches, iw, ih, quads, out, on_device=False, pinned=False, out_pinned=False):
         """one job: patches of `quads` (n x 8 or n x 4 x 2 doubles, patch order) from an iw x ih frame in format fmt (PIX_*) into `out`, the ADDRESS of device memory or,
@@ -662,29 +668,14 @@ class Rectifier:
 
     def wait(self):
         """blocks until the oldest job is done: its status array (uint8 per quad: 1 valid, 0 invalid - an all-zero patch)"""
-        status = np.zeros(self.max_quads, np.uint8)
-        n = lib().rd_rectifier_wait(self.h, status.ctypes.data)
-        if n < 0:
-            raise RuntimeError("rd_rectifier_wait: no job in flight")
-        return status[:n].copy()
+        return self._wait(self.max_quads)
 
     def rectify(self, frame_bgr, quads):
         """convenience: the (n, ph, pw, 3) patches of `quads` from a numpy BGR image, through pinned memory (one job, waited for)"""
         a = np.asarray(frame_bgr, dtype=np.uint8)
         q, n = _quads_arg(quads)
-        nbytes = max(n, 1) * self.ph * self.pw * 3
-        p = lib().rd_host_alloc(nbytes)
-        try:
-            self.enqueue(PIX_BGR, a, None, a.shape[1], a.shape[0], q, p, out_pinned=True)
-            self.wait()
-            return np.frombuffer((ctypes.c_uint8 * nbytes).from_address(p), np.uint8)[:n * self.ph * self.pw * 3].reshape(n, self.ph, self.pw, 3).copy()
-        finally:
-            lib().rd_host_free(p)
-
-    def close(self):
-        if self.h:
-            lib().rd_rectifier_destroy(self.h)
-            self.h = None
+        got = self._through_pinned(max(n, 1) * self.ph * self.pw * 3, lambda p: self.enqueue(PIX_BGR, a, None, a.shape[1], a.shape[0], q, p, out_pinned=True))
+        return got[:n * self.ph * self.pw * 3].reshape(n, self.ph, self.pw, 3)
 
 
 def annot_limits():
@@ -715,17 +706,13 @@ def annot_segments(segs, mode=ANNOT_SEG_ALL, scale=1, max_prims=None):
     return out
 
 
-class Annotator:
+class Annotator(_Service):
     """The rd_annotator extension: up to max_prims primitives per job drawn into a frame on the device, njobs jobs in flight (the contract: include/rectdetect_hip.h)."""
+    _name = "annotator"
 
     def __init__(self, max_prims=4096, njobs=2, device=0):
-        L = lib()
-        if L.rd_device_count() <= 0:
-            raise RuntimeError("rectdetect_amd: no HIP device visible - there is no CPU fallback")
         self.max_prims, self.njobs = max_prims, njobs
-        self.h = L.rd_annotator_create(device, max_prims, njobs)
-        if not self.h:
-            raise ValueError("rd_annotator_create: invalid arguments (%r)" % ((device, max_prims, njobs),))
+        self._create(device, max_prims, njobs)
 
     def enqueue(self, fmt, planes, pitches, iw, ih, prims, flags=0, out_planes=None, out_pitches=None, on_device=False, pinned=False, out_pinned=False):
         """one job: `prims` (PRIM_DTYPE) into an iw x ih frame in format fmt (PIX_*).  planes / pitches as Detector.enqueue_planes: numpy planes (copied before the call
@@ -742,28 +729,11 @@ class Annotator:
 
     def wait(self):
         """blocks until the oldest job is done: its number of primitives"""
-        n = lib().rd_annotator_wait(self.h)
-        if n < 0:
-            raise RuntimeError("rd_annotator_wait: no job in flight")
-        return n
+        return self._wait()
 
     def annotate(self, frame_bgr, prims, flags=0):
         """convenience: a numpy BGR image with `prims` drawn into it, as a new array, through pinned memory (one job, waited for)"""
-        a = np.asarray(frame_bgr, dtype=np.uint8)
-        ih, iw = a.shape[:2]
-        nbytes = ih * iw * 3
-        p = lib().rd_host_alloc(nbytes)
-        try:
-            self.enqueue(PIX_BGR, a, None, iw, ih, prims, flags, out_planes=(p,), out_pitches=(iw * 3,), out_pinned=True)
-            self.wait()
-            return np.frombuffer((ctypes.c_uint8 * nbytes).from_address(p), np.uint8).reshape(ih, iw, 3).copy()
-        finally:
-            lib().rd_host_free(p)
-
-    def close(self):
-        if self.h:
-            lib().rd_annotator_destroy(self.h)
-            self.h = None
+        return self._frame_through_pinned(frame_bgr, prims, flags)
 
 
 def comp_limits():
@@ -816,22 +786,29 @@ def composite_tiles(items, iw, ih):
     return out
 
 
-class Compositor:
+class Compositor(_Service):
     """The rd_compositor extension: up to max_items quads per job filled with a colour or pasted with a pw x ph BGR patch, in a frame on the device, njobs jobs in
     flight (the contract: include/rectdetect_hip.h)."""
+    _name = "compositor"
 
     def __init__(self, pw=64, ph=64, max_items=256, njobs=2, device=0):
-        L = lib()
-        if L.rd_device_count() <= 0:
-            raise RuntimeError("rectdetect_amd: no HIP device visible - there is no CPU fallback")
         self.pw, self.ph, self.max_items, self.njobs = pw, ph, max_items, njobs
-        self.h = L.rd_compositor_create(device, pw, ph, max_items, njobs)
-        if not self.h:
-            raise ValueError("rd_compositor_create: invalid arguments (%r)" % ((device, pw, ph, max_items, njobs),))
+        self._create(device, pw, ph, max_items, njobs)
 
-    def _check_patches(self, a):
+    def _patches(self, patches, patches_on_device, patches_pinned):
+        """(pointer, number of patches, kind, array to keep alive) of a job's patch array: None, a numpy (n, ph, pw, 3) uint8 array (copied before the call returns), or
+        with patches_on_device / patches_pinned an (ADDRESS, n) pair"""
+        if patches is None:
+            return None, 0, 0, None
+        if patches_on_device or patches_pinned:
+            addr, n = patches
+            return (int(addr) if addr else None), int(n), 1 if patches_on_device else 2, None
+        a = np.ascontiguousarray(patches, dtype=np.uint8)
+        if a.ndim != 4 or a.shape[3] != 3:
+            raise ValueError("composite: host patches are an (n, ph, pw, 3) uint8 array, not %r" % (a.shape,))
         if a.shape[1:] != (self.ph, self.pw, 3):
             raise ValueError("composite: patches of shape %r for a compositor of %dx%d patches" % (a.shape, self.pw, self.ph))
+        return a.ctypes.data, len(a), 0, a
 
     def enqueue(self, fmt, planes, pitches, iw, ih, items, patches=None, out_planes=None, out_pitches=None, on_device=False, pinned=False, out_pinned=False,
                 patches_on_device=False, patches_pinned=False):
@@ -842,10 +819,7 @@ class Compositor:
         an argument error (nothing enqueued)."""
         ptrs, pitch_c, kind, pitch, _ = _plane_args(planes, pitches, on_device, pinned)
         it, n = _items_arg(items)
-        pp, npatches, pkind, keep = _patches_arg(patches, patches_on_device, patches_pinned)
-        if keep is not None:
-            self._check_patches(keep)
-            npatches = len(keep)
+        pp, npatches, pkind, _ = self._patches(patches, patches_on_device, patches_pinned)
         optrs, opitch = _out_args(out_planes, out_pitches)
         r = lib().rd_compositor_enqueue(self.h, int(fmt), ptrs, pitch_c, int(iw), int(ih), kind, it.ctypes.data, n, pp, npatches, pkind, optrs, opitch, 2 if out_pinned else 1)
         if r == -1:
@@ -854,29 +828,11 @@ class Compositor:
 
     def wait(self):
         """blocks until the oldest job is done: its status array (uint8 per item: 1 valid, 0 invalid - nothing written)"""
-        status = np.zeros(self.max_items, np.uint8)
-        n = lib().rd_compositor_wait(self.h, status.ctypes.data)
-        if n < 0:
-            raise RuntimeError("rd_compositor_wait: no job in flight")
-        return status[:n].copy()
+        return self._wait(self.max_items)
 
     def composite(self, frame_bgr, items, patches=None):
         """convenience: a numpy BGR image with `items` composited into it, as a new array, through pinned memory (one job, waited for)"""
-        a = np.asarray(frame_bgr, dtype=np.uint8)
-        ih, iw = a.shape[:2]
-        nbytes = ih * iw * 3
-        p = lib().rd_host_alloc(nbytes)
-        try:
-            self.enqueue(PIX_BGR, a, None, iw, ih, items, patches, out_planes=(p,), out_pitches=(iw * 3,), out_pinned=True)
-            self.wait()
-            return np.frombuffer((ctypes.c_uint8 * nbytes).from_address(p), np.uint8).reshape(ih, iw, 3).copy()
-        finally:
-            lib().rd_host_free(p)
-
-    def close(self):
-        if self.h:
-            lib().rd_compositor_destroy(self.h)
-            self.h = None
+        return self._frame_through_pinned(frame_bgr, items, patches)
 
 
 def postprocess_planes(segs, boundary, table, iw, ih, tan_aov):

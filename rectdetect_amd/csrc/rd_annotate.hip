@@ -1,44 +1,16 @@
 // rectdetect-mi355x: the annotator - rectangles' outlines and line segments drawn into frames behind the detector's poll (the contract: include/rectdetect_hip.h,
-// "annotated frames"; the kernel: rd_k_annotate.hip; the coverage test: rd_annot_cover.h).  Built like the rectifier (rd_rectify.hip): one non-blocking stream of
-// its own, one event per job in flight; no graphs, no threads, no environment switches.
-#include "rd_internal.h"
+// "annotated frames"; the kernel: rd_k_annotate.hip; the coverage test: rd_annot_cover.h; the jobs in flight, the frame's checks and its ways: rd_jobs.h).
+#include "rd_jobs.h"
 #include "rd_kernels.h"
-#include "rectdetect_hip.h"
 #include <math.h>
 #include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
 
-#define MAGIC_ANNOTATOR 0x5244414eu
 #define COORD_MIN (-1048576)
 #define COORD_MAX 1048575
 
+using namespace rdjob;
+
 namespace {
-
-struct Job {
-  hipEvent_t done;
-  rdk::AnnotRec *h_recs, *d_recs;      // this job's records: pinned staging and their place in the device array (max_prims each)
-  int n;
-};
-
-// the planes a format uses, their row bytes and rows; a frame in one of the annotator's own buffers is packed with row strides rounded up to 4 bytes
-struct Layout { int np, row[3], rows[3], pitch[3]; size_t off[3], bytes; };
-Layout layout(int fmt, int iw, int ih) {
-  Layout L;
-  memset(&L, 0, sizeof(L));
-  const int bpp = fmt == RD_PIX_BGR || fmt == RD_PIX_RGB ? 3 : 4;
-  if (fmt <= RD_PIX_RGBA) { L.np = 1; L.row[0] = iw * bpp; L.rows[0] = ih; }
-  else if (fmt == RD_PIX_NV12) { L.np = 2; L.row[0] = L.row[1] = iw; L.rows[0] = ih; L.rows[1] = ih / 2; }
-  else { L.np = 3; L.row[0] = iw; L.rows[0] = ih; L.row[1] = L.row[2] = iw / 2; L.rows[1] = L.rows[2] = ih / 2; }
-  for (int k = 0; k < L.np; k++) { L.pitch[k] = (L.row[k] + 3) & ~3; L.off[k] = L.bytes; L.bytes += (size_t)L.pitch[k] * L.rows[k]; }
-  return L;
-}
-
-hipMemoryType memory_type(const void *p) {
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return hipMemoryTypeUnregistered; }
-  return at.type;
-}
 
 bool prim_ok(const rd_annot_prim *p) {
   return p->thickness >= 1 && p->x0 >= COORD_MIN && p->x0 <= COORD_MAX && p->y0 >= COORD_MIN && p->y0 <= COORD_MAX &&
@@ -61,31 +33,13 @@ bool make_prim(rd_annot_prim *p, const double a[2], const double b[2], int scale
   return true;
 }
 
-void ensure(uint8_t **buf, size_t *have, size_t want, hipStream_t st) {
-  if (*have >= want) return;
-  RD_HIP(hipStreamSynchronize(st));      // (jobs in flight use the old one)
-  if (*buf) RD_HIP(hipFree(*buf));
-  RD_HIP(hipMalloc((void **)buf, want));
-  *have = want;
-}
-
 }  // namespace
 
 struct rd_annotator {
-  uint32_t magic;
-  int device, max_prims, njobs;
-  hipStream_t st;
-  Job *jobs;
-  rdk::AnnotRec *d_recs, *h_recs;           // njobs * max_prims records each
-  long next_enqueue, next_wait;
-  // host and pinned frames travel through `frame`, frames on their way to pinned host memory through `oframe` (both grow on demand; jobs follow one another on
-  // st, so one buffer of each serves them all)
-  uint8_t *frame, *oframe; size_t frame_bytes, oframe_bytes;
+  Ring ring;                                // (first: rd_jobs.h)
+  rdk::AnnotRec *d_recs, *h_recs;           // njobs blocks of max_prims records each, a job's at slot * max_prims: pinned staging and their place in the device array
+  DevBuf frame, oframe;                     // host and pinned frames travel through `frame`, frames on their way to pinned host memory through `oframe`
 };
-
-namespace rdrt {
-int annotator_device(const rd_annotator *a) { return a && a->magic == MAGIC_ANNOTATOR ? a->device : -1; }
-}
 
 extern "C" {
 
@@ -163,70 +117,42 @@ int rd_annot_segments(const void *lslist, int mode, int scale, rd_annot_prim *ou
 }
 
 rd_annotator *rd_annotator_create(int device, int max_prims, int njobs) {
-  if (max_prims < 1 || max_prims > (1 << 20) || njobs < 1 || njobs > 1024) return NULL;
-  if (device < 0 || device >= rd_device_count()) return NULL;
-  RD_HIP(hipSetDevice(device));
+  if (max_prims < 1 || max_prims > (1 << 20) || !ring_args_ok(device, njobs)) return NULL;
   rd_annotator *a = (rd_annotator *)calloc(1, sizeof(*a));
-  a->magic = MAGIC_ANNOTATOR;
-  a->device = device; a->max_prims = max_prims; a->njobs = njobs;
-  RD_HIP(hipStreamCreateWithFlags(&a->st, hipStreamNonBlocking));
+  ring_create(&a->ring, RD_MAGIC_ANNOTATOR, device, max_prims, njobs);
   const size_t nr = (size_t)njobs * max_prims;
   RD_HIP(hipMalloc((void **)&a->d_recs, nr * sizeof(rdk::AnnotRec)));
   RD_HIP(hipHostMalloc((void **)&a->h_recs, nr * sizeof(rdk::AnnotRec), hipHostMallocDefault));
-  a->jobs = (Job *)calloc(njobs, sizeof(Job));
-  for (int k = 0; k < njobs; k++) {
-    RD_HIP(hipEventCreateWithFlags(&a->jobs[k].done, hipEventDisableTiming));
-    a->jobs[k].h_recs = a->h_recs + (size_t)k * max_prims;
-    a->jobs[k].d_recs = a->d_recs + (size_t)k * max_prims;
-  }
   return a;
 }
 
 void rd_annotator_destroy(rd_annotator *a) {
   if (!a) return;
-  if (a->magic != MAGIC_ANNOTATOR) exitf(-1, "rd_annotator_destroy: bad handle\n");
-  RD_HIP(hipSetDevice(a->device));
-  RD_HIP(hipStreamSynchronize(a->st));
-  for (int k = 0; k < a->njobs; k++) RD_HIP(hipEventDestroy(a->jobs[k].done));
-  RD_HIP(hipStreamDestroy(a->st));
+  ring_destroy(ring_of(a, RD_MAGIC_ANNOTATOR, "rd_annotator_destroy"));
   RD_HIP(hipFree(a->d_recs));
   RD_HIP(hipHostFree(a->h_recs));
-  if (a->frame) RD_HIP(hipFree(a->frame));
-  if (a->oframe) RD_HIP(hipFree(a->oframe));
-  free(a->jobs);
-  a->magic = 0;
+  a->frame.release();
+  a->oframe.release();
   free(a);
 }
 
 long rd_annotator_enqueue(rd_annotator *a, int format, const void *const planes[3], const int pitches[3], int iw, int ih, int on_device,
                           const rd_annot_prim *prims, int n, int flags, void *const out_planes[3], const int out_pitches[3], int out_kind) {
-  if (!a || a->magic != MAGIC_ANNOTATOR) exitf(-1, "rd_annotator_enqueue: bad handle\n");
+  static const char who[] = "rd_annotator_enqueue";
+  Ring *g = ring_of(a, RD_MAGIC_ANNOTATOR, who);
   // argument errors: -1, nothing enqueued
-  if (format < RD_PIX_BGR || format > RD_PIX_I420 || !planes || !pitches || iw < 1 || ih < 1 || iw > 65536 || ih > 65536) return -1;
-  if (on_device != RD_FRAME_HOST && on_device != RD_FRAME_DEVICE && on_device != RD_FRAME_HOST_PINNED) return -1;
+  PixLayout L;
+  if (!frame_ok(format, planes, pitches, iw, ih, on_device, &L) || !dest_ok(L, out_planes, out_pitches, out_kind, on_device)) return -1;
   if (flags & ~RD_ANNOT_CLEAR) return -1;
-  if (format >= RD_PIX_NV12 && ((iw | ih) & 1)) return -1;
-  const Layout L = layout(format, iw, ih);
-  for (int k = 0; k < L.np; k++) if (!planes[k] || pitches[k] < L.row[k]) return -1;
-  const bool inplace = out_planes == NULL;
-  if (inplace) {
-    if (on_device != RD_FRAME_DEVICE) return -1;
-  } else {
-    if ((out_kind != RD_FRAME_DEVICE && out_kind != RD_FRAME_HOST_PINNED) || !out_pitches) return -1;
-    for (int k = 0; k < L.np; k++) if (!out_planes[k] || out_pitches[k] < L.row[k]) return -1;
-  }
-  if (n < 0 || n > a->max_prims || (n > 0 && !prims)) return -1;
+  if (n < 0 || n > g->per_job || (n > 0 && !prims)) return -1;
   for (int k = 0; k < n; k++) if (!prim_ok(&prims[k])) return -1;
-  RD_HIP(hipSetDevice(a->device));
-  if (!inplace)
-    for (int k = 0; k < L.np; k++)
-      if (memory_type(out_planes[k]) != (out_kind == RD_FRAME_DEVICE ? hipMemoryTypeDevice : hipMemoryTypeHost)) return -1;
-  if (a->next_enqueue - a->next_wait >= a->njobs) exitf(-1, "rd_annotator_enqueue: %d jobs already in flight (wait first)\n", a->njobs);
-  Job *j = &a->jobs[a->next_enqueue % a->njobs];
-  j->n = n;
+  RD_HIP(hipSetDevice(g->device));
+  if (!dest_memory_ok(L, out_planes, out_kind)) return -1;
+  const int slot = ring_claim(g, who, n);
+  rdk::AnnotRec *h_recs = a->h_recs + (size_t)slot * g->per_job, *d_recs = a->d_recs + (size_t)slot * g->per_job;
   for (int k = 0; k < n; k++) {      // the primitives are taken here: the caller may reuse the array when the call returns
     const rd_annot_prim *p = &prims[k];
-    rdk::AnnotRec *r = &j->h_recs[k];
+    rdk::AnnotRec *r = &h_recs[k];
     rd_annot_line_setup(&r->L, p->x0, p->y0, p->x1, p->y1, p->thickness);
     uint8_t c[3] = { p->b, p->g, p->r };
     if (format == RD_PIX_RGB || format == RD_PIX_RGBA) { c[0] = p->r; c[2] = p->b; }
@@ -234,51 +160,29 @@ long rd_annotator_enqueue(rd_annotator *a, int format, const void *const planes[
     r->col = c[0] | (c[1] << 8) | ((uint32_t)c[2] << 16);
     r->pad = 0;
   }
+  const bool inplace = out_planes == NULL, to_pinned = !inplace && out_kind == RD_FRAME_HOST_PINNED;
   if (!(inplace && n == 0 && !(flags & RD_ANNOT_CLEAR))) {      // (that job has nothing to write)
-    const uint8_t *src[3] = { NULL, NULL, NULL };
-    uint8_t *dst[3] = { NULL, NULL, NULL };
-    int spitch[3] = { 0, 0, 0 }, dpitch[3] = { 0, 0, 0 };
-    if (on_device == RD_FRAME_DEVICE) {      // read where they lie
-      for (int k = 0; k < L.np; k++) { src[k] = (const uint8_t *)planes[k]; spitch[k] = pitches[k]; }
-    } else {      // through the annotator's own buffer, one plane after the other
-      if (on_device == RD_FRAME_HOST_PINNED)
-        for (int k = 0; k < L.np; k++)
-          if (memory_type(planes[k]) != hipMemoryTypeHost)
-            exitf(-1, "rd_annotator_enqueue: RD_FRAME_HOST_PINNED needs pinned host memory (rd_host_alloc, allocatePinnedMemory, hipHostMalloc, hipHostRegister); plane %d at %p is not\n", k, planes[k]);
-      ensure(&a->frame, &a->frame_bytes, L.bytes, a->st);
-      for (int k = 0; k < L.np; k++) {
-        RD_HIP(hipMemcpy2DAsync(a->frame + L.off[k], L.pitch[k], planes[k], pitches[k], L.row[k], L.rows[k], hipMemcpyHostToDevice, a->st));
-        src[k] = a->frame + L.off[k]; spitch[k] = L.pitch[k];
-      }
-      if (on_device == RD_FRAME_HOST) RD_HIP(hipStreamSynchronize(a->st));      // (pageable memory: the caller may reuse the buffer when this call returns)
+    Planes src = planes_at(planes, pitches, L);      // a device frame: read where it lies
+    if (on_device != RD_FRAME_DEVICE) {              // through the annotator's own buffer, one plane after the other
+      a->frame.grow(g->st, L.bytes);
+      src = a->frame.packed(L);
+      bring(g->st, who, L, src, planes, pitches, on_device);
     }
-    if (inplace) {
-      for (int k = 0; k < L.np; k++) { dst[k] = (uint8_t *)planes[k]; dpitch[k] = pitches[k]; }
-    } else if (out_kind == RD_FRAME_DEVICE) {
-      for (int k = 0; k < L.np; k++) { dst[k] = (uint8_t *)out_planes[k]; dpitch[k] = out_pitches[k]; }
-    } else {
-      ensure(&a->oframe, &a->oframe_bytes, L.bytes, a->st);
-      for (int k = 0; k < L.np; k++) { dst[k] = a->oframe + L.off[k]; dpitch[k] = L.pitch[k]; }
-    }
-    if (n > 0) RD_HIP(hipMemcpyAsync(j->d_recs, j->h_recs, (size_t)n * sizeof(rdk::AnnotRec), hipMemcpyHostToDevice, a->st));
-    rdk::annotate(a->st, format, dst, dpitch, src, spitch, iw, ih, j->d_recs, n, flags & RD_ANNOT_CLEAR);
+    Planes dst = src;      // in place
+    if (to_pinned) { a->oframe.grow(g->st, L.bytes); dst = a->oframe.packed(L); }
+    else if (!inplace) dst = planes_at(out_planes, out_pitches, L);
+    if (n > 0) RD_HIP(hipMemcpyAsync(d_recs, h_recs, (size_t)n * sizeof(rdk::AnnotRec), hipMemcpyHostToDevice, g->st));
+    rdk::annotate(g->st, format, dst.p, dst.pitch, src.p, src.pitch, iw, ih, d_recs, n, flags & RD_ANNOT_CLEAR);
     rdrt::check_launch("annotated frame");
-    if (!inplace && out_kind == RD_FRAME_HOST_PINNED)
-      for (int k = 0; k < L.np; k++)      // row bytes only: the caller's pitch padding stays as it is
-        RD_HIP(hipMemcpy2DAsync(out_planes[k], out_pitches[k], dst[k], dpitch[k], L.row[k], L.rows[k], hipMemcpyDeviceToHost, a->st));
+    if (to_pinned) send(g->st, L, out_planes, out_pitches, dst);
   }
-  RD_HIP(hipEventRecord(j->done, a->st));
-  return a->next_enqueue++;
+  return ring_record(g);
 }
 
 int rd_annotator_wait(rd_annotator *a) {
-  if (!a || a->magic != MAGIC_ANNOTATOR) exitf(-1, "rd_annotator_wait: bad handle\n");
-  if (a->next_wait >= a->next_enqueue) return -1;
-  RD_HIP(hipSetDevice(a->device));
-  Job *j = &a->jobs[a->next_wait % a->njobs];
-  RD_HIP(hipEventSynchronize(j->done));
-  a->next_wait++;
-  return j->n;
+  Ring *g = ring_of(a, RD_MAGIC_ANNOTATOR, "rd_annotator_wait");
+  const int slot = ring_wait(g);
+  return slot < 0 ? -1 : g->n[slot];
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 #include "rd_internal.h"
 #include "rd_kernels.h"
 #include "rd_comp.h"
+#include "rd_jobs.h"
 #include "rd_poly_scratch.h"
 #include "rectdetect_hip.h"
 #include <stdio.h>
@@ -1302,19 +1303,9 @@ void rd_detector_destroy(rd_detector *d) {
 }
 
 // ---- hand-over of a frame (rd_detector_enqueue, rd_detector_enqueue_planes)
-// The planes a format uses, their row bytes and rows; and the layout of a host frame packed into a slot's buffers (row strides rounded up to 4 bytes, so that
-// the front kernel reads them a dword per lane; every format then still fits the 4 bytes per pixel of bgr / h_bgr).
-struct PixLayout { int np, row[3], rows[3], pitch[3]; size_t off[3], bytes; };
-static PixLayout pix_layout(int fmt, int iw, int ih) {
-  PixLayout L;
-  memset(&L, 0, sizeof(L));
-  const int bpp = fmt == RD_PIX_BGR || fmt == RD_PIX_RGB ? 3 : 4;
-  if (fmt <= RD_PIX_RGBA) { L.np = 1; L.row[0] = iw * bpp; L.rows[0] = ih; }
-  else if (fmt == RD_PIX_NV12) { L.np = 2; L.row[0] = L.row[1] = iw; L.rows[0] = ih; L.rows[1] = ih / 2; }
-  else { L.np = 3; L.row[0] = iw; L.rows[0] = ih; L.row[1] = L.row[2] = iw / 2; L.rows[1] = L.rows[2] = ih / 2; }
-  for (int k = 0; k < L.np; k++) { L.pitch[k] = (L.row[k] + 3) & ~3; L.off[k] = L.bytes; L.bytes += (size_t)L.pitch[k] * L.rows[k]; }
-  return L;
-}
+// The planes a format uses and the layout of a host frame packed into a slot's buffers: rd_jobs.h.
+using rdjob::PixLayout;
+using rdjob::pix_layout;
 // a BGR frame of rd_detector_enqueue keeps the caller's row stride on its way through the slot's buffers: one plane of ws * ih bytes
 static PixLayout bgr_layout(int ws, int ih) {
   PixLayout L;
@@ -1359,9 +1350,7 @@ static void upload_progress(void *ctx) {      // (caller's thread only)
 // is this host buffer page-locked (allocatePinnedMemory of oclhelper.h, rd_host_alloc, hipHostMalloc, hipHostRegister)?  One question to the runtime per buffer, not per frame.
 static bool host_buffer_is_pinned(rd_detector *d, const void *frame) {
   for (int k = 0; k < 2; k++) if (d->probed[k] == frame) return d->probed_pinned[k] != 0;
-  hipPointerAttribute_t at;
-  const bool pinned = hipPointerGetAttributes(&at, frame) == hipSuccess && at.type == hipMemoryTypeHost;
-  if (!pinned) (void)hipGetLastError();
+  const bool pinned = rdjob::memory_type(frame) == hipMemoryTypeHost;
   d->probed[1] = d->probed[0]; d->probed_pinned[1] = d->probed_pinned[0];
   d->probed[0] = frame; d->probed_pinned[0] = pinned ? 1 : 0;
   return pinned;
@@ -1430,8 +1419,7 @@ static long hand_over(rd_detector *d, const char *who, int fmt, const void *cons
         bool known = false;      // (one look per range, not per frame: a capture loop reuses its pages)
         for (int e = 0; e < 4 && !known; e++) known = lo >= d->pinned[e][0] && hi <= d->pinned[e][1];
         if (known) continue;
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, planes[k]) != hipSuccess || at.type != hipMemoryTypeHost) { (void)hipGetLastError(); exitf(-1, "%s: RD_FRAME_HOST_PINNED needs pinned host memory (rd_host_alloc, allocatePinnedMemory, hipHostMalloc, hipHostRegister); plane %d at %p is not\n", who, k, planes[k]); }
+        if (rdjob::memory_type(planes[k]) != hipMemoryTypeHost) { exitf(-1, "%s: RD_FRAME_HOST_PINNED needs pinned host memory (rd_host_alloc, allocatePinnedMemory, hipHostMalloc, hipHostRegister); plane %d at %p is not\n", who, k, planes[k]); }
         const unsigned e = d->pinned_next++ & 3;
         d->pinned[e][0] = lo; d->pinned[e][1] = hi;
       }
@@ -1570,61 +1558,60 @@ void *rd_detector_poll(rd_detector *d, double tanAOV) {
   return r;
 }
 
-// Rectified patches (rd_rectify.hip) from the frame of the most recently polled slot: its format, planes and row strides as hand_over left them - device pointers
-// in every case (a host or pinned frame: the copy in the slot's own buffer, which the next frame handed to this slot overwrites).  The poll has waited for the frame's
-// last kernel, so the rectifier's stream may read at once.  Nothing of the slot is written.
-long rd_detector_rectify_polled(rd_detector *d, rd_rectifier *r, const double *quads, int n, void *out, int out_kind) {
-  if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_rectify_polled: bad handle\n");
-  if (d->last_polled_slot < 0 || rdrt::rectifier_device(r) != d->device) return -1;
+// The frame of the most recently polled slot as a job of a service takes it (rd_rectify.hip, rd_annotate.hip, rd_composite.hip): format, planes and row strides as
+// hand_over left them - device pointers in every case, which a service's stream may read at once: the poll has waited for the frame's last kernel - at the size it
+// came in.  own: a host or pinned frame's copy in the slot's own buffer (bgr, or sc_bgr at scale 2), which the next frame of this slot overwrites and no job may write.
+// false: nothing polled yet, or `service` is no live service of this kind on the detector's device; cap: the most items one of its jobs takes.
+struct PolledFrame { int fmt, iw, ih, scale, cap; const void *planes[3]; const int *pitch; bool own; };
+static bool polled_frame(rd_detector *d, const char *who, const void *service, uint32_t magic, PolledFrame *f) {
+  if (!d || d->magic != MAGIC_RECT) exitf(-1, "%s: bad handle\n", who);
+  f->cap = rdjob::service_capacity(service, magic, d->device);
+  if (d->last_polled_slot < 0 || f->cap < 0) return false;
   const Slot *s = &d->slots[d->last_polled_slot];
-  const void *const planes[3] = { s->pl[0], s->pl[1], s->pl[2] };
-  if (s->scale == 2 && quads && n > 0 && n <= rdrt::rectifier_max_quads(r)) {
-    // a frame that came in at scale 2: the quads are in detector coordinates, the planes hold the source - each corner mapped to source coordinates (pixel centres
-    // at integers: detector pixel x covers source pixels 2x and 2x+1, centre 2x + 0.5), the job run on the source planes with the source's size
-    double *m = (double *)malloc((size_t)n * 8 * sizeof(double));
-    if (!m) exitf(-1, "rd_detector_rectify_polled: out of memory\n");
-    for (size_t i = 0; i < (size_t)n * 8; i++) m[i] = quads[i] * 2.0 + 0.5;
-    const long q = rd_rectifier_enqueue(r, s->fmt, planes, s->pitch, 2 * d->iw, 2 * d->ih, RD_FRAME_DEVICE, m, n, out, out_kind);
-    free(m);      // (the job holds the coefficients: rd_rectifier_enqueue evaluates them before it returns)
-    return q;
+  f->fmt = s->fmt; f->scale = s->scale; f->iw = s->scale * d->iw; f->ih = s->scale * d->ih; f->pitch = s->pitch;
+  for (int k = 0; k < 3; k++) f->planes[k] = s->pl[k];
+  f->own = s->pl[0] == s->bgr || (s->sc_bgr && s->pl[0] == s->sc_bgr);
+  return true;
+}
+// A frame that came in at scale 2 takes quads in detector coordinates: a copy of the job's n items (`size` bytes each, a quad's 8 doubles first), each corner mapped to
+// the source's (pixel centres at integers: detector pixel x covers source pixels 2x and 2x+1, centre 2x + 0.5), to be freed behind the enqueue - which takes what it
+// needs before it returns.  NULL: the job takes the caller's items (scale 1, or arguments that the service will refuse)
+static_assert(offsetof(rd_comp_item, quad) == 0, "an item begins with its quad");
+static void *mapped_to_source(const PolledFrame *f, const char *who, const void *items, int n, size_t size) {
+  if (f->scale != 2 || !items || n < 1 || n > f->cap) return NULL;
+  char *m = (char *)malloc((size_t)n * size);
+  if (!m) exitf(-1, "%s: out of memory\n", who);
+  memcpy(m, items, (size_t)n * size);
+  for (int k = 0; k < n; k++) {
+    double *q = (double *)(m + k * size);
+    for (int i = 0; i < 8; i++) q[i] = q[i] * 2.0 + 0.5;
   }
-  return rd_rectifier_enqueue(r, s->fmt, planes, s->pitch, s->scale == 2 ? 2 * d->iw : d->iw, s->scale == 2 ? 2 * d->ih : d->ih, RD_FRAME_DEVICE, quads, n, out, out_kind);
+  return m;
 }
-
-// Annotated frames (rd_annotate.hip) on the frame of the most recently polled slot, at the size it came in.  A caller's device frame may be drawn into in place; a host or
-// pinned frame lies in the slot's own buffer (bgr, or sc_bgr at scale 2), which the rectifier reads and nothing may change: such a job needs a destination.
+// Rectified patches from the polled frame; nothing of the slot is written.
+long rd_detector_rectify_polled(rd_detector *d, rd_rectifier *r, const double *quads, int n, void *out, int out_kind) {
+  PolledFrame f;
+  if (!polled_frame(d, "rd_detector_rectify_polled", r, RD_MAGIC_RECTIFIER, &f)) return -1;
+  void *m = mapped_to_source(&f, "rd_detector_rectify_polled", quads, n, 8 * sizeof(double));
+  const long q = rd_rectifier_enqueue(r, f.fmt, f.planes, f.pitch, f.iw, f.ih, RD_FRAME_DEVICE, m ? (const double *)m : quads, n, out, out_kind);
+  free(m);
+  return q;
+}
+// Annotated frames: a caller's device frame may be drawn into in place; the slot's own copy needs a destination.
 long rd_detector_annotate_polled(rd_detector *d, rd_annotator *a, const rd_annot_prim *prims, int n, int flags, void *const out_planes[3], const int out_pitches[3], int out_kind) {
-  if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_annotate_polled: bad handle\n");
-  if (d->last_polled_slot < 0 || rdrt::annotator_device(a) != d->device) return -1;
-  const Slot *s = &d->slots[d->last_polled_slot];
-  const bool own = s->pl[0] == s->bgr || (s->sc_bgr && s->pl[0] == s->sc_bgr);
-  if (own && !out_planes) return -1;
-  const void *const planes[3] = { s->pl[0], s->pl[1], s->pl[2] };
-  return rd_annotator_enqueue(a, s->fmt, planes, s->pitch, s->scale == 2 ? 2 * d->iw : d->iw, s->scale == 2 ? 2 * d->ih : d->ih, RD_FRAME_DEVICE, prims, n, flags, out_planes, out_pitches, out_kind);
+  PolledFrame f;
+  if (!polled_frame(d, "rd_detector_annotate_polled", a, RD_MAGIC_ANNOTATOR, &f) || (f.own && !out_planes)) return -1;
+  return rd_annotator_enqueue(a, f.fmt, f.planes, f.pitch, f.iw, f.ih, RD_FRAME_DEVICE, prims, n, flags, out_planes, out_pitches, out_kind);
 }
-
-// Composited quads (rd_composite.hip) on the frame of the most recently polled slot, at the size it came in; in place or into a destination by the annotator's rule
-// above.  A frame that came in at scale 2: the quads arrive in detector coordinates and are mapped to the source's as rd_detector_rectify_polled maps them.
+// Composited quads: in place or into a destination by the annotator's rule.
 long rd_detector_composite_polled(rd_detector *d, rd_compositor *c, const rd_comp_item *items, int n, const void *patches, int npatches, int patches_kind,
                                   void *const out_planes[3], const int out_pitches[3], int out_kind) {
-  if (!d || d->magic != MAGIC_RECT) exitf(-1, "rd_detector_composite_polled: bad handle\n");
-  if (d->last_polled_slot < 0 || rdrt::compositor_device(c) != d->device) return -1;
-  const Slot *s = &d->slots[d->last_polled_slot];
-  const bool own = s->pl[0] == s->bgr || (s->sc_bgr && s->pl[0] == s->sc_bgr);
-  if (own && !out_planes) return -1;
-  const void *const planes[3] = { s->pl[0], s->pl[1], s->pl[2] };
-  if (s->scale == 2 && items && n > 0 && n <= rdrt::compositor_max_items(c)) {
-    rd_comp_item *m = (rd_comp_item *)malloc((size_t)n * sizeof(rd_comp_item));
-    if (!m) exitf(-1, "rd_detector_composite_polled: out of memory\n");
-    memcpy(m, items, (size_t)n * sizeof(rd_comp_item));
-    for (int k = 0; k < n; k++)
-      for (int i = 0; i < 8; i++) m[k].quad[i] = items[k].quad[i] * 2.0 + 0.5;
-    const long q = rd_compositor_enqueue(c, s->fmt, planes, s->pitch, 2 * d->iw, 2 * d->ih, RD_FRAME_DEVICE, m, n, patches, npatches, patches_kind, out_planes, out_pitches, out_kind);
-    free(m);      // (the job holds its records: rd_compositor_enqueue makes them before it returns)
-    return q;
-  }
-  return rd_compositor_enqueue(c, s->fmt, planes, s->pitch, s->scale == 2 ? 2 * d->iw : d->iw, s->scale == 2 ? 2 * d->ih : d->ih, RD_FRAME_DEVICE, items, n, patches, npatches, patches_kind,
-                               out_planes, out_pitches, out_kind);
+  PolledFrame f;
+  if (!polled_frame(d, "rd_detector_composite_polled", c, RD_MAGIC_COMPOSITOR, &f) || (f.own && !out_planes)) return -1;
+  void *m = mapped_to_source(&f, "rd_detector_composite_polled", items, n, sizeof(rd_comp_item));
+  const long q = rd_compositor_enqueue(c, f.fmt, f.planes, f.pitch, f.iw, f.ih, RD_FRAME_DEVICE, m ? (const rd_comp_item *)m : items, n, patches, npatches, patches_kind, out_planes, out_pitches, out_kind);
+  free(m);
+  return q;
 }
 
 // The reference hands the aperture over with the poll, i.e. after the frame (oclrect_pollTask); whatever runs ahead of the poll - the

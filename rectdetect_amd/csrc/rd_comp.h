@@ -5,16 +5,9 @@
 #include <stdint.h>
 #include "rd_comp_host.h"
 
-struct rd_compositor;
-
 namespace rdk {
 // n items composited IN PLACE into one iw x ih frame in format fmt (RD_PIX_*), one launch of ntiles one-wave blocks: tiles holds the pairs tx, ty of the tiles the
 // valid items' boxes reach (rd_comp_tiles_of), recs, tiles and patches are device memory; patches: images of pw x ph BGR pixels (may be NULL when no item pastes).
 void composite(hipStream_t s, int fmt, uint8_t *const planes[3], const int pitch[3], int iw, int ih, const rd_comp_rec *recs, int n, const int32_t *tiles, int ntiles,
                const uint8_t *patches, int pw, int ph);
 }  // namespace rdk
-
-namespace rdrt {
-int compositor_device(const rd_compositor *c);         // rd_composite.hip: the device a compositor lives on (-1: not a compositor)
-int compositor_max_items(const rd_compositor *c);      // the most items one of its jobs takes (-1: not a compositor)
-}  // namespace rdrt

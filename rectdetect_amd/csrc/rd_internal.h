@@ -33,9 +33,6 @@ struct _cl_kernel { int dummy; };
     if (rd_e_ != hipSuccess) exitf(-1, "%s:%d: %s failed: %s\n", __FILE__, __LINE__, #call, hipGetErrorString(rd_e_)); \
   } while (0)
 
-struct rd_rectifier;
-struct rd_annotator;
-
 namespace rdrt {
 inline void *dptr(cl_mem m) {
   if (!m || m->magic != RD_MAGIC_MEM) exitf(-1, "rectdetect: invalid cl_mem handle\n");
@@ -51,7 +48,4 @@ void wait_list(cl_command_queue q, const cl_event *events);
 cl_event finish_op(cl_command_queue q, const cl_event *events);
 void check_launch(const char *what);
 int current_device();
-int rectifier_device(const rd_rectifier *r);      // rd_rectify.hip: the device a rectifier lives on (-1: not a rectifier)
-int rectifier_max_quads(const rd_rectifier *r);   // rd_rectify.hip: the most quads one of its jobs takes (-1: not a rectifier)
-int annotator_device(const rd_annotator *a);      // rd_annotate.hip: the device an annotator lives on (-1: not an annotator)
 }  // namespace rdrt

@@ -5,7 +5,6 @@ travel, jobs in flight, behind the poll of both detector kinds, argument errors.
 import ctypes
 import os
 import subprocess
-import sys
 from functools import lru_cache
 
 import numpy as np
@@ -14,13 +13,12 @@ import pytest
 import rectdetect_amd as ra
 from tests import annotate
 from tests import helpers
+from tests import jobframes
 from tests import pixfmt
+from tests.jobframes import FILL, L, assert_planes, cframe, into, padded, shapes
 
 pytestmark = pytest.mark.gpu
-L = ra.lib
-GUARD = 64      # bytes of 0xA5 behind every plane: nothing may write there
-PAD, FILL = 0x5A, 0xC3      # pitch padding; what a destination holds before its job
-MODES = {"inplace": ("device", None), "dev2dev": ("device", "device"), "host2pinned": ("host", "pinned"), "pinned2dev": ("pinned", "device")}
+MODES = ("inplace", "dev2dev", "host2pinned", "pinned2dev")
 LIM = ra.annot_limits()
 TW, TH, CHUNK = LIM["tile_w"], LIM["tile_h"], LIM["chunk"]
 
@@ -29,66 +27,9 @@ def golden(name):
     return np.load(os.path.join(helpers.GOLDEN, name + ".npz"), allow_pickle=False)
 
 
-def cframe(seed, iw, ih, t):
-    a = np.zeros((ih, iw, 3), np.uint8)
-    L().rd_synth_frame(a.ctypes.data, iw, ih, iw * 3, int(seed), int(t), 1)
-    return a
-
-
-def shapes(fmt, iw, ih):
-    return ra._source_shapes(fmt, iw, ih)      # [(rows, row bytes)] per plane
-
-
-def padded(fmt, iw, ih, pad, content):
-    """planes of (rows, row bytes + pad): content is a seed (random bytes), a byte value, or a list of (rows, row bytes) arrays; the padding is PAD"""
-    rng = np.random.default_rng(content) if isinstance(content, int) and content > 255 else None
-    out = []
-    for k, (rows, row) in enumerate(shapes(fmt, iw, ih)):
-        a = np.full((rows, row + pad), PAD, np.uint8)
-        a[:, :row] = rng.integers(0, 256, (rows, row), dtype=np.uint8) if rng is not None else (content if isinstance(content, int) else np.asarray(content[k]).reshape(rows, row))
-        out.append(a)
-    return out
-
-
-class Mem:
-    """device and pinned planes of a test, each with a guard behind it, freed together"""
-
-    def __init__(self):
-        self.dev, self.pin = [], []
-
-    def put(self, kind, plane):
-        buf = np.concatenate([np.ascontiguousarray(plane).reshape(-1), np.full(GUARD, 0xA5, np.uint8)])
-        if kind == "device":
-            p = L().rd_device_alloc(buf.nbytes)
-            self.dev.append(p)
-            L().rd_upload(p, buf.ctypes.data, buf.nbytes)
-        else:
-            p = L().rd_host_alloc(buf.nbytes)
-            self.pin.append(p)
-            ctypes.memmove(p, buf.ctypes.data, buf.nbytes)
-        return p
-
-    def get(self, kind, p, shape):
-        n = int(np.prod(shape))
-        a = np.zeros(n + GUARD, np.uint8)
-        if kind == "device":
-            L().rd_download(a.ctypes.data, p, a.nbytes)
-        else:
-            ctypes.memmove(a.ctypes.data, p, a.nbytes)
-        assert (a[n:] == 0xA5).all(), "bytes behind a plane were written"
-        return a[:n].reshape(shape)
-
-    def close(self):
-        for p in self.dev:
-            L().rd_device_free(p)
-        for p in self.pin:
-            L().rd_host_free(p)
-        self.dev, self.pin = [], []
-
-
 @pytest.fixture
 def mem():
-    m = Mem()
+    m = jobframes.Mem()
     yield m
     m.close()
 
@@ -100,56 +41,13 @@ def an():
     a.close()
 
 
-class Pending:
-    """one enqueued job: where its frame will be, and what must not have changed"""
-
-    def __init__(self, mem, fmt, src, iw, ih, mode, out_pad):
-        self.mem, self.fmt, self.src, self.iw, self.ih = mem, fmt, src, iw, ih
-        self.src_kind, self.out_kind = MODES[mode]
-        sh = shapes(fmt, iw, ih)
-        self.rows = [row for _, row in sh]
-        self.pitches = [p.shape[1] for p in src]
-        if self.src_kind == "host":
-            self.args, self.kw = [p[:, :row] for p, row in zip(src, self.rows)], {}
-        else:
-            self.args = [mem.put(self.src_kind, p) for p in src]
-            self.kw = {"on_device": self.src_kind == "device", "pinned": self.src_kind == "pinned"}
-        self.out_init = self.out = None
-        if self.out_kind:
-            self.out_init = padded(fmt, iw, ih, out_pad, FILL)
-            self.out = [mem.put(self.out_kind, p) for p in self.out_init]
-
+class Pending(jobframes.Pending):
     def enqueue(self, an, prims, flags):
-        if self.out_kind:
-            return an.enqueue(self.fmt, self.args, self.pitches, self.iw, self.ih, prims, flags, out_planes=self.out, out_pitches=[p.shape[1] for p in self.out_init],
-                              out_pinned=self.out_kind == "pinned", **self.kw)
         return an.enqueue(self.fmt, self.args, self.pitches, self.iw, self.ih, prims, flags, **self.kw)
-
-    def result(self):
-        """the frame's planes, padding included; guards checked; an out-of-place job must have left its source alone"""
-        if self.out_kind:
-            if self.src_kind != "host":
-                for p, a in zip(self.src, self.args):
-                    assert np.array_equal(self.mem.get(self.src_kind, a, p.shape), p), "an out-of-place job changed its source"
-            return [self.mem.get(self.out_kind, o, p.shape) for o, p in zip(self.out, self.out_init)]
-        return [self.mem.get("device", a, p.shape) for a, p in zip(self.args, self.src)]
 
 
 def expected(fmt, src, iw, ih, prims, flags, out_init=None):
-    want = annotate.draw(fmt, src, iw, ih, prims, clear=bool(flags & ra.ANNOT_CLEAR))
-    if out_init is None:
-        return want
-    exp = [o.copy() for o in out_init]      # the destination's padding stays; its rows are the drawn frame's
-    for e, w, (_, row) in zip(exp, want, shapes(fmt, iw, ih)):
-        e[:, :row] = w[:, :row]
-    return exp
-
-
-def assert_planes(got, want, what=""):
-    for k, (g, w) in enumerate(zip(got, want)):
-        if not np.array_equal(g, w):
-            ys, xs = np.nonzero(g != w)
-            raise AssertionError("%s: plane %d differs in %d bytes, first at row %d byte %d: got %d, expected %d" % (what, k, len(ys), ys[0], xs[0], g[ys[0], xs[0]], w[ys[0], xs[0]]))
+    return into(out_init, annotate.draw(fmt, src, iw, ih, prims, clear=bool(flags & ra.ANNOT_CLEAR)), fmt, iw, ih)
 
 
 def run(an, mem, fmt, src, iw, ih, prims, flags=0, mode="inplace", out_pad=3, want=None, what=""):
@@ -158,14 +56,7 @@ def run(an, mem, fmt, src, iw, ih, prims, flags=0, mode="inplace", out_pad=3, wa
     job.enqueue(an, prims, flags)
     assert an.wait() == len(prims)
     got = job.result()
-    if want is None:
-        exp = expected(fmt, src, iw, ih, prims, flags, job.out_init)
-    else:
-        exp = want
-        if job.out_init is not None:
-            exp = [o.copy() for o in job.out_init]
-            for e, w, (_, row) in zip(exp, want, shapes(fmt, iw, ih)):
-                e[:, :row] = w[:, :row]
+    exp = expected(fmt, src, iw, ih, prims, flags, job.out_init) if want is None else into(job.out_init, want, fmt, iw, ih)
     assert_planes(got, exp, what or "%s %dx%d %s" % (ra.PIX_NAMES[fmt], iw, ih, mode))
     return got
 
@@ -411,16 +302,28 @@ def test_three_jobs_in_flight(mem):
 
 def test_one_job_too_many_is_fatal():
     """in a child process: the fourth enqueue with njobs = 3 and nothing waited for ends the process with a message, as the rectifier's does"""
-    code = ("import numpy as np, rectdetect_amd as ra\n"
-            "a = ra.Annotator(max_prims=4, njobs=3)\n"
-            "d = ra.lib().rd_device_alloc(64 * 64 * 3)\n"
-            "p = np.zeros(1, ra.PRIM_DTYPE); p['x1'] = 9; p['thickness'] = 1\n"
-            "for k in range(4):\n"
-            "    a.enqueue(ra.PIX_BGR, (d,), (64 * 3,), 64, 64, p, on_device=True)\n"
-            "    print('enqueued', k, flush=True)\n")
-    r = subprocess.run([sys.executable, "-c", code], cwd=helpers.ROOT, capture_output=True, text=True, timeout=120)
-    assert r.returncode != 0 and "enqueued 2" in r.stdout and "enqueued 3" not in r.stdout, (r.returncode, r.stdout, r.stderr)
-    assert "3 jobs already in flight" in r.stderr, r.stderr
+    jobframes.assert_one_job_too_many_is_fatal("s = ra.Annotator(max_prims=4, njobs=3)\np = np.zeros(1, ra.PRIM_DTYPE); p['x1'] = 9; p['thickness'] = 1",
+                                               "s.enqueue(ra.PIX_BGR, (d,), (64 * 3,), 64, 64, p, on_device=True)", "rd_annotator_enqueue")
+
+
+def test_staging_buffers_grow_with_jobs_in_flight(mem):
+    """host frames into pinned destinations: the second job's frame is larger than the first's and enqueued while that is in flight, the third is the small one again"""
+    a2 = ra.Annotator(max_prims=64, njobs=2)
+    try:
+        jobs = []
+        for k, (fmt, iw, ih) in enumerate([(ra.PIX_BGR, 34, 18), (ra.PIX_NV12, 98, 62), (ra.PIX_BGR, 34, 18)]):
+            src = padded(fmt, iw, ih, 1 + k, 1040 + k)
+            prims = coloured([(1, 1, iw - 2, ih - 2, 1), (iw - 3, 0, 2, ih - 1, 2), (-5, ih // 2, iw + 5, ih // 2 + 1, 3), (iw - 1, 0, iw - 1, ih - 1, 1)][k % 2:])
+            jobs.append((Pending(mem, fmt, src, iw, ih, "host2pinned", 5 - k), fmt, src, iw, ih, prims))
+
+        def check(job, n):
+            pend, fmt, src, iw, ih, prims = job
+            assert n == len(prims)
+            assert_planes(pend.result(), expected(fmt, src, iw, ih, prims, 0, pend.out_init), "%s %dx%d" % (ra.PIX_NAMES[fmt], iw, ih))
+
+        jobframes.growing_jobs(a2, jobs, lambda job: job[0].enqueue(a2, job[5], 0), check)
+    finally:
+        a2.close()
 
 
 # ---------------------------------------------------------------------------------------------- 9. behind the poll

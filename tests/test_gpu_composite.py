@@ -14,80 +14,20 @@ import rectdetect_amd as ra
 from tests import annotate
 from tests import composite
 from tests import helpers
+from tests import jobframes
 from tests import pixfmt
 from tests import rectify
+from tests.jobframes import FILL, MODES, L, assert_planes, cframe, into, padded, shapes
 
 pytestmark = pytest.mark.gpu
-L = ra.lib
-GUARD = 64      # bytes of 0xA5 behind every plane: nothing may write there
-PAD, FILL = 0x5A, 0xC3      # pitch padding; what a destination holds before its job
-MODES = {"inplace": ("device", None), "dev2dev": ("device", "device"), "dev2pinned": ("device", "pinned"), "host2dev": ("host", "device"), "host2pinned": ("host", "pinned"),
-         "pinned2dev": ("pinned", "device")}
 LIM = ra.comp_limits()
 TW, TH, CHUNK = LIM["tile_w"], LIM["tile_h"], LIM["chunk"]
 PW, PH = 16, 12      # the module's compositor: neither square nor a power of two
 
 
-def cframe(seed, iw, ih, t):
-    a = np.zeros((ih, iw, 3), np.uint8)
-    L().rd_synth_frame(a.ctypes.data, iw, ih, iw * 3, int(seed), int(t), 1)
-    return a
-
-
-def shapes(fmt, iw, ih):
-    return ra._source_shapes(fmt, iw, ih)      # [(rows, row bytes)] per plane
-
-
-def padded(fmt, iw, ih, pad, content):
-    """planes of (rows, row bytes + pad): content is a seed (random bytes), a byte value, or a list of (rows, row bytes) arrays; the padding is PAD"""
-    rng = np.random.default_rng(content) if isinstance(content, int) and content > 255 else None
-    out = []
-    for k, (rows, row) in enumerate(shapes(fmt, iw, ih)):
-        a = np.full((rows, row + pad), PAD, np.uint8)
-        a[:, :row] = rng.integers(0, 256, (rows, row), dtype=np.uint8) if rng is not None else (content if isinstance(content, int) else np.asarray(content[k]).reshape(rows, row))
-        out.append(a)
-    return out
-
-
-class Mem:
-    """device and pinned buffers of a test, each with a guard behind it, freed together"""
-
-    def __init__(self):
-        self.dev, self.pin = [], []
-
-    def put(self, kind, plane):
-        buf = np.concatenate([np.ascontiguousarray(plane).reshape(-1), np.full(GUARD, 0xA5, np.uint8)])
-        if kind == "device":
-            p = L().rd_device_alloc(buf.nbytes)
-            self.dev.append(p)
-            L().rd_upload(p, buf.ctypes.data, buf.nbytes)
-        else:
-            p = L().rd_host_alloc(buf.nbytes)
-            self.pin.append(p)
-            ctypes.memmove(p, buf.ctypes.data, buf.nbytes)
-        return p
-
-    def get(self, kind, p, shape):
-        n = int(np.prod(shape))
-        a = np.zeros(n + GUARD, np.uint8)
-        if kind == "device":
-            L().rd_download(a.ctypes.data, p, a.nbytes)
-        else:
-            ctypes.memmove(a.ctypes.data, p, a.nbytes)
-        assert (a[n:] == 0xA5).all(), "bytes behind a plane were written"
-        return a[:n].reshape(shape)
-
-    def close(self):
-        for p in self.dev:
-            L().rd_device_free(p)
-        for p in self.pin:
-            L().rd_host_free(p)
-        self.dev, self.pin = [], []
-
-
 @pytest.fixture
 def mem():
-    m = Mem()
+    m = jobframes.Mem()
     yield m
     m.close()
 
@@ -99,24 +39,7 @@ def comp():
     c.close()
 
 
-class Pending:
-    """one enqueued job: where its frame will be, and what must not have changed"""
-
-    def __init__(self, mem, fmt, src, iw, ih, mode, out_pad=3):
-        self.mem, self.fmt, self.src, self.iw, self.ih = mem, fmt, src, iw, ih
-        self.src_kind, self.out_kind = MODES[mode]
-        self.rows = [row for _, row in shapes(fmt, iw, ih)]
-        self.pitches = [p.shape[1] for p in src]
-        if self.src_kind == "host":
-            self.args, self.kw = [p[:, :row] for p, row in zip(src, self.rows)], {}
-        else:
-            self.args = [mem.put(self.src_kind, p) for p in src]
-            self.kw = {"on_device": self.src_kind == "device", "pinned": self.src_kind == "pinned"}
-        self.out_init = self.out = None
-        if self.out_kind:
-            self.out_init = padded(fmt, iw, ih, out_pad, FILL)
-            self.out = [mem.put(self.out_kind, p) for p in self.out_init]
-
+class Pending(jobframes.Pending):
     def enqueue(self, comp, items, patches=None, patches_kind="host"):
         kw = dict(self.kw)
         if patches is not None and patches_kind != "host":
@@ -124,37 +47,7 @@ class Pending:
             self.patch_ptr = self.mem.put(patches_kind, self.patch_src)
             patches = (self.patch_ptr, len(self.patch_src))
             kw["patches_on_device" if patches_kind == "device" else "patches_pinned"] = True
-        if self.out_kind:
-            kw.update(out_planes=self.out, out_pitches=[p.shape[1] for p in self.out_init], out_pinned=self.out_kind == "pinned")
         return comp.enqueue(self.fmt, self.args, self.pitches, self.iw, self.ih, items, patches, **kw)
-
-    def result(self):
-        """the frame's planes, padding included; guards checked; an out-of-place job must have left its source alone, every job its patches"""
-        if getattr(self, "patch_ptr", None):
-            assert np.array_equal(self.mem.get(self.patch_kind, self.patch_ptr, self.patch_src.shape), self.patch_src), "the job changed its patches"
-        if self.out_kind:
-            if self.src_kind != "host":
-                for p, a in zip(self.src, self.args):
-                    assert np.array_equal(self.mem.get(self.src_kind, a, p.shape), p), "an out-of-place job changed its source"
-            return [self.mem.get(self.out_kind, o, p.shape) for o, p in zip(self.out, self.out_init)]
-        return [self.mem.get("device", a, p.shape) for a, p in zip(self.args, self.src)]
-
-
-def into(out_init, want, fmt, iw, ih):
-    """what a destination holds after the job: its own padding, the composited frame's rows"""
-    if out_init is None:
-        return want
-    exp = [o.copy() for o in out_init]
-    for e, w, (_, row) in zip(exp, want, shapes(fmt, iw, ih)):
-        e[:, :row] = w[:, :row]
-    return exp
-
-
-def assert_planes(got, want, what=""):
-    for k, (g, w) in enumerate(zip(got, want)):
-        if not np.array_equal(g, w):
-            ys, xs = np.nonzero(g != w)
-            raise AssertionError("%s: plane %d differs in %d bytes, first at row %d byte %d: got %d, expected %d" % (what, k, len(ys), ys[0], xs[0], g[ys[0], xs[0]], w[ys[0], xs[0]]))
 
 
 def run(comp, mem, fmt, src, iw, ih, items, patches=None, mode="inplace", out_pad=3, patches_kind="host", want=None, what=""):
@@ -415,6 +308,35 @@ def test_three_jobs_in_flight(mem):
             c3.wait()
     finally:
         c3.close()
+
+
+def test_one_job_too_many_is_fatal():
+    """in a child process: the fourth enqueue with njobs = 3 and nothing waited for ends the process with a message, as the annotator's does"""
+    jobframes.assert_one_job_too_many_is_fatal("s = ra.Compositor(8, 8, max_items=1, njobs=3)\nit = ra.comp_items([[(4, 4), (40, 4), (40, 40), (4, 40)]])",
+                                               "s.enqueue(ra.PIX_BGR, (d,), (64 * 3,), 64, 64, it, on_device=True)", "rd_compositor_enqueue")
+
+
+def test_staging_buffers_grow_with_jobs_in_flight(mem):
+    """host frames into pinned destinations: the second job's frame is larger than the first's and takes three host patches where that took one, enqueued while
+    it is in flight; the third is the small one again"""
+    c2 = ra.Compositor(PW, PH, max_items=16, njobs=2)
+    try:
+        jobs = []
+        for k, (fmt, iw, ih, npatches) in enumerate([(ra.PIX_BGR, 34, 18, 1), (ra.PIX_NV12, 98, 62, 3), (ra.PIX_BGR, 34, 18, 1)]):
+            src = padded(fmt, iw, ih, 1 + k, 3850 + k)
+            items = mixed_items(iw, ih, 85 + k, n=4 + 2 * npatches, npatches=npatches)
+            assert sorted(set(items["patch"].tolist())) == list(range(-1, npatches))
+            jobs.append((Pending(mem, fmt, src, iw, ih, "host2pinned", 5 - k), fmt, src, iw, ih, items, random_patches(95 + k, n=npatches)))
+
+        def check(job, status):
+            pend, fmt, src, iw, ih, items, patches = job
+            want, wstatus = composite.draw(fmt, src, iw, ih, items, patches)
+            assert status.tolist() == wstatus.tolist() and wstatus.any()
+            assert_planes(pend.result(), into(pend.out_init, want, fmt, iw, ih), "%s %dx%d" % (ra.PIX_NAMES[fmt], iw, ih))
+
+        jobframes.growing_jobs(c2, jobs, lambda job: job[0].enqueue(c2, job[5], job[6]), check)
+    finally:
+        c2.close()
 
 
 # ---------------------------------------------------------------------------------------------- 9. argument errors

@@ -11,94 +11,22 @@ import pytest
 import rectdetect_amd as ra
 from rectdetect_amd import synth
 from tests import helpers
+from tests import jobframes
 from tests import pixfmt
 from tests import rectify
+from tests.jobframes import L, cframe
 
 pytestmark = pytest.mark.gpu
 TAN36 = float(np.tan(36.0 / 180.0 * np.pi))
-L = ra.lib
-GUARD = 64      # bytes of 0xA5 behind every output buffer: nothing may write there
 
 
 def golden(name):
     return np.load(os.path.join(helpers.GOLDEN, name + ".npz"), allow_pickle=False)
 
 
-def cframe(seed, iw, ih, t):
-    a = np.zeros((ih, iw, 3), np.uint8)
-    L().rd_synth_frame(a.ctypes.data, iw, ih, iw * 3, int(seed), int(t), 1)
-    return a
-
-
-class Mem:
-    """device and pinned allocations of a test, freed together"""
-
-    def __init__(self):
-        self.dev, self.pin = [], []
-
-    def device(self, nbytes):
-        p = L().rd_device_alloc(nbytes)
-        self.dev.append(p)
-        return p
-
-    def pinned(self, nbytes):
-        p = L().rd_host_alloc(nbytes)
-        self.pin.append(p)
-        return p
-
-    def place(self, kind, planes, pad=0):
-        """planes as a `kind` frame with rows pad bytes longer than they need be: (what Rectifier.enqueue takes as planes, pitches, keyword arguments)"""
-        args, pitches = [], []
-        for p in planes:
-            p = np.ascontiguousarray(p)
-            rows, row = p.shape[0], p.size // p.shape[0]
-            img = np.full((rows, row + pad), 0x5A, np.uint8)
-            img[:, :row] = p.reshape(rows, row)
-            pitches.append(row + pad)
-            if kind == "host":
-                args.append(img[:, :row])
-            elif kind == "device":
-                d = self.device(img.nbytes)
-                L().rd_upload(d, img.ctypes.data, img.nbytes)
-                args.append(d)
-            else:
-                h = self.pinned(img.nbytes)
-                ctypes.memmove(h, img.ctypes.data, img.nbytes)
-                args.append(h)
-        return args, pitches, {"on_device": kind == "device", "pinned": kind == "pinned"}
-
-    def out(self, kind, nbytes):
-        """an output buffer of nbytes + GUARD bytes filled with 0xA5"""
-        fill = np.full(nbytes + GUARD, 0xA5, np.uint8)
-        if kind == "device":
-            p = self.device(fill.nbytes)
-            L().rd_upload(p, fill.ctypes.data, fill.nbytes)
-        else:
-            p = self.pinned(fill.nbytes)
-            ctypes.memmove(p, fill.ctypes.data, fill.nbytes)
-        return p
-
-    def fetch(self, kind, p, nbytes):
-        """the nbytes of an output buffer; its guard must be untouched"""
-        a = np.zeros(nbytes + GUARD, np.uint8)
-        if kind == "device":
-            L().rd_download(a.ctypes.data, p, a.nbytes)
-        else:
-            ctypes.memmove(a.ctypes.data, p, a.nbytes)
-        assert (a[nbytes:] == 0xA5).all(), "bytes behind the job's patches were written"
-        return a[:nbytes]
-
-    def close(self):
-        for p in self.dev:
-            L().rd_device_free(p)
-        for p in self.pin:
-            L().rd_host_free(p)
-        self.dev, self.pin = [], []
-
-
 @pytest.fixture
 def mem():
-    m = Mem()
+    m = jobframes.Mem()
     yield m
     m.close()
 
@@ -272,6 +200,38 @@ def test_jobs_in_flight_come_back_in_order(njobs, mem):
         assert checked == len(subsets)
         with pytest.raises(RuntimeError):
             rect.wait()      # nothing in flight
+    finally:
+        rect.close()
+
+
+def test_one_job_too_many_is_fatal():
+    """in a child process: the fourth enqueue with njobs = 3 and nothing waited for ends the process with a message"""
+    jobframes.assert_one_job_too_many_is_fatal("s = ra.Rectifier(8, 8, max_quads=1, njobs=3)\no = ra.lib().rd_device_alloc(8 * 8 * 3)\nq = [[(4, 4), (40, 4), (40, 40), (4, 40)]]",
+                                               "s.enqueue(ra.PIX_BGR, (d,), (64 * 3,), 64, 64, q, o, on_device=True)", "rd_rectifier_enqueue")
+
+
+def test_staging_buffers_grow_with_jobs_in_flight(mem):
+    """host frames, pinned output: the second job's frame is larger than the first's and enqueued while that is in flight, the third is the small one again"""
+    pw, ph = 16, 12
+    rect = ra.Rectifier(pw, ph, max_quads=3, njobs=2)
+    try:
+        jobs = []
+        for k, (fmt, iw, ih, nq) in enumerate([(ra.PIX_BGR, 34, 18, 1), (ra.PIX_NV12, 98, 62, 3), (ra.PIX_BGR, 34, 18, 2)]):
+            planes, bgr = pixfmt.convert(noise_frame(iw, ih, 50 + k), fmt)
+            w, h = float(iw), float(ih)
+            quads = np.array([[(2.5, 1.25), (w - 4.0, 3.0), (w - 5.5, h - 2.0), (4.0, h - 3.5)], [(-6.0, -4.0), (w * 0.6, -2.5), (w * 0.5, h * 0.7), (-3.0, h * 0.5)],
+                              [(w * 0.4, h * 0.3), (w + 7.0, h * 0.2), (w + 3.0, h + 5.0), (w * 0.3, h + 2.0)]])[:nq]
+            args, pitches, kw = mem.place("host", planes, 3 - k)
+            jobs.append((fmt, args, pitches, iw, ih, quads, mem.out("pinned", nq * pw * ph * 3), kw, bgr))
+
+        def check(job, status):
+            fmt, _, _, iw, ih, quads, out, _, bgr = job
+            want, wstatus = rectify.patches(bgr, quads, pw, ph)
+            assert wstatus.all()
+            got = mem.fetch("pinned", out, len(quads) * pw * ph * 3).reshape(len(quads), ph, pw, 3)
+            assert_patches(got, status, want, wstatus, "%s %dx%d" % (ra.PIX_NAMES[fmt], iw, ih))
+
+        jobframes.growing_jobs(rect, jobs, lambda job: rect.enqueue(*job[:7], out_pinned=True, **job[7]), check)
     finally:
         rect.close()
 
