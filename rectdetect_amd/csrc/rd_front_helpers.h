@@ -46,4 +46,30 @@ __device__ __forceinline__ float bicubic_lds(const float *t, float x, float y, i
   return cubic1(r[0], r[1], r[2], r[3], fy);
 }
 
+// cubic1's row polynomial with the position taken out: for the four cells p0..p3 that start at a column, {x, y, z, w} are the three bracketed terms of
+// cubic1 and p1, so that cubic1(p0, p1, p2, p3, f) == ((x * f + y) * f + z) * f * 0.5f + w bit for bit (same operations in the same order)
+__device__ __forceinline__ float4 cubic_coef(float p0, float p1, float p2, float p3) {
+  const float v = p1 - p2, w = p3 - p0;
+  return make_float4(v * 3.0f + w, -4.0f * v + (p0 - p1 - w), p2 - p0, p1);
+}
+
+// bicubic_lds on a tile of cubic_coef cells (pitch CF_PITCH, the cell of start column x0 - 3 and row y0 - 3 first): one 128-bit read per row
+#define CF_PITCH 68
+__device__ __forceinline__ float bicubic(const float4 *t, float x, float y, int x0, int y0) {
+  const int ix = (int)x, iy = (int)y;
+  const float fx = x - ix, fy = y - iy;
+  const float4 *q = t + (iy - 1 - (y0 - 3)) * CF_PITCH + (ix - 1 - (x0 - 3));
+  float r[4];
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    const float4 c = q[k * CF_PITCH];
+    float u = c.x;
+    u = u * fx + c.y;
+    u = u * fx + c.z;
+    u = u * fx * 0.5f + c.w;
+    r[k] = u;
+  }
+  return cubic1(r[0], r[1], r[2], r[3], fy);
+}
+
 }  // namespace

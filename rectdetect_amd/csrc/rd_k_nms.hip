@@ -24,6 +24,15 @@ const dim3 block2(64, 4);
 // suppresses from LDS exactly like k_thinthres.  A strength cell outside the frame is the strength AT ITS MIRRORED POSITION (what
 // k_thinthres' staging reads), not the formula applied to mirrored neighbours: border tiles evaluate such a cell around the mirrored centre.
 // Same operations in the same order per value as the three kernels; TAPS = 1 also writes the three intermediate planes (tests, debug planes).
+// The suppression does not sample the strength tile itself.  The row polynomial of a bicubic sample depends on the sample's position only through
+// its fraction: its four terms (cubic_coef, rd_front_helpers.h) belong to the four strength cells that start at a column, and every (row, start
+// column) is sampled dozens of times per tile.  So once the strength tile is complete the block expands it ONCE into a coefficient tile - one float4
+// per strength row and start column x0 - 3 .. x0 + 64, GN_SH x CF_PITCH cells - and a sample is four 128-bit reads and three multiply-adds per row
+// (bicubic) where sampling the strength cells took sixteen reads and ten operations per row; the values are those of cubic1, bit for bit.  LDS:
+// the coefficient tile takes the place of the Lab tile, which nothing reads after the strength phase; the strength tile is dead once it is expanded
+// (a pixel's own strength is the w of the cell that starts one column to its left), and the list of local maxima lives in what the coefficient
+// tile leaves of the Lab tile plus the strength tile: GN_LCAP entries.  A maximum that finds the list full (flat content: every pixel is one) is
+// finished on the spot by the lane that found it, with the same arithmetic.
 #ifndef GN_ROWS
 #define GN_ROWS 16
 #endif
@@ -36,6 +45,12 @@ const dim3 block2(64, 4);
 #endif
 #define GN_NT (64 * GN_TY)
 #define GN_K (GN_ROWS / GN_TY)         // pixels per thread: a column of GN_K rows
+#define GN_LAB (4 * GN_LH * GN_LW)     // floats of the Lab tile
+#define GN_STR (GN_SH * TT_PITCH)      // floats of the strength tile, which follows it
+#ifndef GN_LCAP
+#define GN_LCAP 540                    // entries (20 bytes) of the list of maxima, behind the coefficient tile
+#endif
+static_assert(GN_SH * CF_PITCH * 16 + GN_LCAP * 20 <= (GN_LAB + GN_STR) * 4, "coefficient tile and list of maxima share the Lab and strength tiles' memory");
 struct GnTaps { uint32_t *plab1; float2 *vxy; float *strength; };
 
 template <int TAPS>
@@ -43,11 +58,15 @@ __global__ __launch_bounds__(GN_NT) void k_grad_nms(float *__restrict__ out, P3c
   const rd_tile rd_b = rd_block_tile(gdim);
   if (rd_b.x < 0) return;
   RD_ZSHIFTZ(rd_b.z, zs, out, bl.p[0], bl.p[1], bl.p[2], taps.plab1, taps.vxy, taps.strength);
-  // [0] raw L, [1..3] the re-packed fields as floats; after the strength is known the same memory holds the list of local maxima
-  __shared__ float lab[4][GN_LH * GN_LW];
-  __shared__ float str[GN_SH * TT_PITCH];
+  // the Lab tile ([0] raw L, [1..3] the re-packed fields as floats), then the strength tile; after the strength is known the same memory holds the
+  // coefficient tile and, behind it, the list of local maxima
+  __shared__ __attribute__((aligned(16))) float smem[GN_LAB + GN_STR];
   __shared__ int nlst;
-  static_assert(4 * GN_LH * GN_LW * 4 >= 64 * GN_ROWS * 20, "the list of maxima lives in the Lab tile's memory");
+  float (*const lab)[GN_LH * GN_LW] = (float (*)[GN_LH * GN_LW])smem;
+  float *const str = smem + GN_LAB;
+  float4 *const cf = (float4 *)smem;
+  float4 *const lst = cf + GN_SH * CF_PITCH;
+  int *const lpix = (int *)(lst + GN_LCAP);
   const int x0 = rd_b.x * 64, y0 = rd_b.y * GN_ROWS;
   const int tx = threadIdx.x, ty = rd_ty(), tid = ty * 64 + tx;
   if (tid == 0) nlst = 0;
@@ -166,9 +185,23 @@ __global__ __launch_bounds__(GN_NT) void k_grad_nms(float *__restrict__ out, P3c
     }
   }
   __syncthreads();
+  // ---- coefficient tile: a wave takes every fourth row of the strength tile, its lanes the start columns 0..63; the 4 start columns left over are a
+  // cell per thread.  (Cells made of strength cells that a border tile never wrote are read by no pixel of the frame, like those.)
+  {
+    constexpr int NR = (GN_SH + GN_TY - 1) / GN_TY;
+#pragma unroll
+    for (int i = 0; i < NR; i++) {
+      const int r = ty + GN_TY * i;
+      if (r < GN_SH) { const float *p = &str[r * TT_PITCH + tx]; cf[r * CF_PITCH + tx] = cubic_coef(p[0], p[1], p[2], p[3]); }
+    }
+    if (tid < 4 * GN_SH) {
+      const int r = tid >> 2, c = 64 + (tid & 3);
+      const float *p = &str[r * TT_PITCH + c];
+      cf[r * CF_PITCH + c] = cubic_coef(p[0], p[1], p[2], p[3]);
+    }
+  }
+  __syncthreads();
   // ---- suppression (iu:456-471), as k_thinthres: inner samples for every pixel, outer samples for the local maxima only (worked off as a list)
-  float4 *lst = (float4 *)&lab[0][0];
-  int *lpix = (int *)(lst + 64 * GN_ROWS);
   const int x = x0 + tx;
 #pragma unroll
   for (int k = 0; k < GN_K; k++) {
@@ -179,9 +212,9 @@ __global__ __launch_bounds__(GN_NT) void k_grad_nms(float *__restrict__ out, P3c
     float am1 = 0, ap1 = 0;
     const float2 v = dir[k];
     if (inside) {
-      const float a0 = str[(r + 3) * TT_PITCH + tx + 3];
-      am1 = bicubic_lds(str, x - 1 * v.x, y - 1 * v.y, x0, y0);
-      ap1 = bicubic_lds(str, x + 1 * v.x, y + 1 * v.y, x0, y0);
+      const float a0 = cf[(r + 3) * CF_PITCH + tx + 2].w;
+      am1 = bicubic(cf, x - 1 * v.x, y - 1 * v.y, x0, y0);
+      ap1 = bicubic(cf, x + 1 * v.x, y + 1 * v.y, x0, y0);
       peak = am1 <= a0 && a0 >= ap1;
       if (!peak) out[y * iw + x] = 0.0f;
     }
@@ -191,18 +224,27 @@ __global__ __launch_bounds__(GN_NT) void k_grad_nms(float *__restrict__ out, P3c
       int b = 0;
       if (tx == leader) b = atomicAdd(&nlst, __popcll(m));
       b = __shfl(b, leader);
-      if (peak) { const int i = b + __popcll(m & ((1ull << tx) - 1)); lst[i] = make_float4(am1, ap1, v.x, v.y); lpix[i] = r * 64 + tx; }
+      if (peak) {
+        const int i = b + __popcll(m & ((1ull << tx) - 1));
+        if (i < GN_LCAP) { lst[i] = make_float4(am1, ap1, v.x, v.y); lpix[i] = r * 64 + tx; }
+        else {      // the list is full: this lane finishes its maximum itself
+          const float a0 = cf[(r + 3) * CF_PITCH + tx + 2].w;
+          const float am2 = bicubic(cf, x - 2 * v.x, y - 2 * v.y, x0, y0);
+          const float ap2 = bicubic(cf, x + 2 * v.x, y + 2 * v.y, x0, y0);
+          out[y * iw + x] = am2 + am1 + a0 + ap1 + ap2;
+        }
+      }
     }
   }
   __syncthreads();
-  const int n = nlst;
+  const int n = nlst < GN_LCAP ? nlst : GN_LCAP;
   for (int i = tid; i < n; i += GN_NT) {
     const float4 e = lst[i];
     const int c = lpix[i], r = c >> 6, cx = c & 63;
     const int xx = x0 + cx, yy = y0 + r;
-    const float a0 = str[(r + 3) * TT_PITCH + cx + 3];
-    const float am2 = bicubic_lds(str, xx - 2 * e.z, yy - 2 * e.w, x0, y0);
-    const float ap2 = bicubic_lds(str, xx + 2 * e.z, yy + 2 * e.w, x0, y0);
+    const float a0 = cf[(r + 3) * CF_PITCH + cx + 2].w;
+    const float am2 = bicubic(cf, xx - 2 * e.z, yy - 2 * e.w, x0, y0);
+    const float ap2 = bicubic(cf, xx + 2 * e.z, yy + 2 * e.w, x0, y0);
     out[yy * iw + xx] = am2 + e.x + a0 + e.y + ap2;
   }
 }
