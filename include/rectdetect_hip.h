@@ -450,6 +450,92 @@ int rd_compositor_wait(rd_compositor *c, uint8_t *status_out);
 long rd_detector_composite_polled(rd_detector *d, rd_compositor *c, const rd_comp_item *items, int n, const void *patches, int npatches, int patches_kind,
                                   void *const out_planes[3], const int out_pitches[3], int out_kind);
 
+/* ---- matched quads: WHICH known thing is inside a quad - a screen, a card, a poster, a sign, a fiducial - decided on the device (rd_k_match.hip, rd_match.hip,
+ * rd_match_host.c).  A matcher holds a library of templates; a job returns, per quad, the best template, its orientation, its score and the runner-up: a few dozen
+ * bytes instead of a patch.  Everything is defined in integers plus a handful of correctly rounded double operations, so that an independent restatement
+ * (tests/match.py, numpy int64 / float64) reproduces every value.
+ *
+ * Signature of a quad - parameters: a grid G in {8, 16, 32, 64} and an oversampling m in {1, 2, 4}:
+ *   1. the rectifier's patch of the quad at pw = ph = G*m - "rectified patches" above, byte for byte: coefficients, s = (i+0.5)/pw, the 8.8 blend, the conversion
+ *      of every tap of an NV12 / I420 frame, the clamps;
+ *   2. per patch pixel, in int32:  grey = (29*B + 150*G + 77*R + 128) >> 8                                     (0 .. 255)
+ *   3. per cell (i, j) of the G x G grid, over the m x m patch pixels (i*m .. i*m+m-1, j*m .. j*m+m-1):
+ *        cell = (sum of the greys + m*m/2) >> log2(m*m);   a = cell - 128 as int8                              (-128 .. 127)
+ *   4. the signature is the D = G*G values a in row-major order, rows along t: value number j*G + i is cell (i, j);
+ *   5. alongside, in integers:  sa = sum of a,  saa = sum of a*a.
+ * An invalid quad (the rectifier's status 0) has no signature.
+ *
+ * Library.  A matcher holds up to max_templates templates, numbered from 0 in the order they were added.  A template is the signature of a quad in an image the
+ * caller hands over (rd_matcher_add); a NULL quad is the whole image: corners (-0.5,-0.5) (iw-0.5,-0.5) (iw-0.5,ih-0.5) (-0.5,ih-0.5).  Template k occupies the
+ * library's columns 4k .. 4k+3: column 4k+r is the template's signature S turned r quarter turns as a pure permutation of its cells,
+ *   rot(S)[j][i] = S[G-1-i][j]     (row j, column i)     applied r times
+ * - the picture turned clockwise on screen (y down) by r quarter turns; nothing is resampled.  A quad whose best column is 4k+r therefore shows template k with
+ * the template's FIRST corner (its patch corner (0,0)) at the quad's corner number r, and the template's corners follow in the quad's own order: the quad's corners
+ * r, r+1, r+2, r+3 (mod 4) are the template's 0, 1, 2, 3 - the start corner a caller permutes to for an upright patch.  Every column keeps sb = sum of b and
+ * sbb = sum of b*b (the same for the four columns of a template).  A template with D*sbb - sb*sb == 0 (a flat image) or from an invalid quad is refused.
+ *
+ * Scores - for quad q (signature a) and column c (signature b), all exact:
+ *   dot = sum of a_i * b_i                       int32   (|dot| <= 4096 * 2^14 = 2^26)
+ *   num = D*dot - sa*sb                          int64   (magnitude below 2^39)
+ *   va  = D*saa - sa*sa;   vb = D*sbb - sb*sb    int64   (0 <= va, vb < 2^39: every conversion to double below is exact)
+ * Selection - on the device, in double, uncontracted, in this order:
+ *   key_c = ((double)num * fabs((double)num)) / (double)vb_c
+ * The best column is the one with the greatest key, the LOWEST column among equal keys.  The runner-up is the best column, by the same rule, among the columns
+ * whose template differs from the best's (the best's other three rotations never are the runner-up); there is none when the library holds one template.
+ * Score - on the HOST, in plain C from the integers the device returned (rd_match_score, rd_match_host.c; the device never takes a square root):
+ *   score = (double)num / sqrt((double)va * (double)vb)                 - the correlation coefficient of the two signatures, in [-1, 1] up to rounding.
+ *
+ * The record of a quad:
+ *   status  0: an invalid quad;  1: matched;  2: a flat signature (va == 0: no correlation exists);  3: an empty library.  Tested in the order 0, 3, 2.
+ *   tmpl, rot, dot      the best column 4*tmpl + rot and its dot
+ *   tmpl2, rot2, dot2   the runner-up's; -1, 0, 0 when there is none
+ *   sa, saa             the quad's sums
+ *   score, score2       as above from the best's and the runner-up's integers; score2 = 0.0 when there is no runner-up
+ * With a status other than 1 every other field is zero. */
+typedef struct { int32_t status, tmpl, rot, dot, tmpl2, rot2, dot2, sa; int64_t saa; double score, score2; } rd_match;   /* 56 bytes */
+#define RD_MATCH_DOTS 1               /* flags of a job: keep the whole dot matrix for rd_matcher_wait */
+#define RD_MATCH_MAX_TEMPLATES 4096
+#define RD_MATCH_MAX_QUADS 1024
+
+/* host helpers; none needs a GPU */
+/* Completes a record the device made: score from (dot, sa, saa) and the best column's sb, sbb, score2 from (dot2, sa, saa) and sb2, sbb2 (ignored when tmpl2 < 0:
+ * score2 = 0.0) for a matcher of grid `grid` (D = grid * grid).  A record whose status is not 1 gets every other field zeroed. */
+void rd_match_score(rd_match *rec, int grid, int32_t sb, int64_t sbb, int32_t sb2, int64_t sbb2);
+/* out[0]: the legal grids ORed together (8 | 16 | 32 | 64), out[1]: the legal oversamplings ORed together (1 | 2 | 4), out[2] = RD_MATCH_MAX_TEMPLATES,
+ * out[3] = RD_MATCH_MAX_QUADS */
+void rd_match_limits(int32_t out[4]);
+
+/* A matcher scores up to max_quads quads per job against up to max_templates templates, up to njobs jobs in flight, on one stream of its own.  NULL on bad arguments
+ * (a grid or an oversampling other than the above, max_templates < 1 or > RD_MATCH_MAX_TEMPLATES, max_quads < 1 or > RD_MATCH_MAX_QUADS, njobs < 1 or > 1024, no such
+ * device).  Device memory: the library (4 * max_templates * D bytes) and the dot matrix (max_quads x 4 * max_templates int32, both rounded up to 16). */
+typedef struct rd_matcher rd_matcher;
+rd_matcher *rd_matcher_create(int device, int grid, int oversample, int max_templates, int max_quads, int njobs);
+void rd_matcher_destroy(rd_matcher *m);      /* waits for the jobs in flight */
+/* Adds a template: the signature of `quad` (8 doubles, patch order; NULL: the whole image) in an iw x ih image in pixel format `format` (planes / pitches / on_device
+ * as for rd_rectifier_enqueue; a pinned image that is not pinned memory is fatal).  Waits for the matcher's stream - jobs already enqueued were scored against the
+ * library as it was - and returns when the template is in the library: the image may be reused.  Returns the template's number; -1 for an argument error (the frame
+ * checks of rd_rectifier_enqueue; a full library); -2 for a flat template or an invalid quad.  Nothing changes on -1 and -2. */
+int rd_matcher_add(rd_matcher *m, int format, const void *const planes[3], const int pitches[3], int iw, int ih, int on_device, const double *quad);
+int rd_matcher_templates(rd_matcher *m);      /* how many templates the library holds */
+/* test tap: the D bytes of column 4 * tmpl + rot to `out` and its sb, sbb to sums[0], sums[1] (either may be NULL); waits for the matcher's stream.  0, or -1 when
+ * there is no such column. */
+int rd_matcher_signature(rd_matcher *m, int tmpl, int rot, int8_t *out, int32_t sums[2]);
+/* One job: the records of n quads (8 doubles each, patch order) of one iw x ih frame in pixel format `format`.  Frame kinds, their lifetimes and the argument checks
+ * are rd_rectifier_enqueue's: RD_FRAME_HOST (copied before the call returns), RD_FRAME_DEVICE (read in place until the job's wait), RD_FRAME_HOST_PINNED (memory that
+ * is not pinned is fatal).  The caller hands over no output buffer: results travel to pinned memory of the job and rd_matcher_wait copies them out.  flags:
+ * RD_MATCH_DOTS keeps the job's dot matrix too (its pinned block is allocated with the first job that asks).  The job is scored against the library as it is NOW:
+ * T = rd_matcher_templates at this call.  n == 0 is a legal job.  Returns the job's sequence number, or -1 with nothing enqueued for an argument error: the frame's
+ * (as the rectifier), flag bits other than RD_MATCH_DOTS, n < 0, n > max_quads, n > 0 with quads NULL.  A call with njobs jobs already in flight is fatal. */
+long rd_matcher_enqueue(rd_matcher *m, int format, const void *const planes[3], const int pitches[3], int iw, int ih, int on_device, const double *quads, int n, int flags);
+/* the oldest job: blocks until it is done, completes its n records (rd_match_score) into `out` (may be NULL) and returns n.  dots_out: NULL, or - for a job enqueued
+ * with RD_MATCH_DOTS - space for n x 4T int32, T the job's: dots_out[q * 4T + c] = dot of quad q and column c (a row of zeros for an invalid quad).  -1: no job in
+ * flight. */
+int rd_matcher_wait(rd_matcher *m, rd_match *out, int32_t *dots_out);
+/* One job from the frame of the most recently polled slot of d (either kind of detector), as rd_detector_rectify_polled: no second transfer of a host frame; quads
+ * of a frame that came in at scale 2 in DETECTOR coordinates, each corner mapped X = x * 2.0 + 0.5, Y = y * 2.0 + 0.5, the signature taken from the full-size source.
+ * Returns as rd_matcher_enqueue; -1 also when nothing has been polled yet or d and m are on different devices. */
+long rd_detector_match_polled(rd_detector *d, rd_matcher *m, const double *quads, int n, int flags);
+
 /* ---- synthetic frames (csrc/rd_synth.c) */
 int rd_synth_num_quads(int iw, int ih);
 void rd_synth_frame(uint8_t *bgr, int iw, int ih, int ws, uint64_t seed, int t, int noise);

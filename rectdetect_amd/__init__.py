@@ -12,6 +12,8 @@ Mirrors of the reference programs' call sequences:
   * :class:`PolylineDetector` - its polyline kind: poly.cpp / vidpoly.cpp per frame, several frames in flight
   * :class:`Rectifier` - the ``rd_rectifier`` extension: what is inside detected quads as upright patches of fixed size
   * :class:`Annotator` - the ``rd_annotator`` extension: rectangles' outlines and line segments drawn into frames on the device
+  * :class:`Compositor` - the ``rd_compositor`` extension: a colour or an image written into the quads of a frame on the device
+  * :class:`Matcher` - the ``rd_matcher`` extension: which template of a library is inside each quad, decided on the device
 """
 import ctypes
 import os
@@ -31,6 +33,11 @@ assert RECT_DTYPE.itemsize == 176 and LS_DTYPE.itemsize == 56 and PRIM_DTYPE.ite
 ANNOT_CLEAR = 1
 COMP_ITEM_DTYPE = np.dtype([("quad", "<f8", (4, 2)), ("patch", "<i4"), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("pad", "u1")])      # rd_comp_item, 72 bytes
 COMP_FILL = -1
+# the record of a matched quad (rd_match; the contract is in include/rectdetect_hip.h, "matched quads")
+MATCH_DTYPE = np.dtype([("status", "<i4"), ("tmpl", "<i4"), ("rot", "<i4"), ("dot", "<i4"), ("tmpl2", "<i4"), ("rot2", "<i4"), ("dot2", "<i4"), ("sa", "<i4"),
+                        ("saa", "<i8"), ("score", "<f8"), ("score2", "<f8")])
+assert MATCH_DTYPE.itemsize == 56
+MATCH_DOTS = 1
 ANNOT_SEG_ALL, ANNOT_SEG_CHAINS = 0, 1
 
 # pixel formats of enqueue_planes (rd_detector_enqueue_planes; the conversion contract is in include/rectdetect_hip.h)
@@ -122,6 +129,17 @@ def _declare(L):
         "rd_compositor_enqueue": (ctypes.c_long, [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ci, ci, vp, ci, vp, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci]),
         "rd_compositor_wait": (ci, [vp, vp]),
         "rd_detector_composite_polled": (ctypes.c_long, [vp, vp, vp, ci, vp, ci, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci]),
+        # matched quads (rd_match.hip, rd_match_host.c)
+        "rd_match_score": (None, [vp, ci, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int64]),
+        "rd_match_limits": (None, [vp]),
+        "rd_matcher_create": (vp, [ci, ci, ci, ci, ci, ci]),
+        "rd_matcher_destroy": (None, [vp]),
+        "rd_matcher_add": (ci, [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ci, ci, vp]),
+        "rd_matcher_templates": (ci, [vp]),
+        "rd_matcher_signature": (ci, [vp, ci, ci, vp, vp]),
+        "rd_matcher_enqueue": (ctypes.c_long, [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ci, ci, vp, ci, ci]),
+        "rd_matcher_wait": (ci, [vp, vp, vp]),
+        "rd_detector_match_polled": (ctypes.c_long, [vp, vp, vp, ci, ci]),
         "rd_synth_frame": (None, [vp, ci, ci, ci, ctypes.c_uint64, ci, ci]),
         "rd_synth_num_quads": (ci, [ci, ci]),
         # reference API (oclhelper.h / raw cl*)
@@ -438,6 +456,18 @@ class _PolledJobs:
         r = lib().rd_detector_composite_polled(self.h, compositor.h, it.ctypes.data, n, pp, npatches, pkind, optrs, opitch, 2 if out_pinned else 1)
         if r == -1:
             raise ValueError("rd_detector_composite_polled: invalid arguments (nothing polled yet, a host frame without out_planes, %d items, %d patches)" % (n, npatches))
+        return r
+
+
+    def match_polled(self, matcher, quads, flags=0):
+        """the records of `quads` (n x 8 or n x 4 x 2 doubles, patch order) in the frame of the most recently polled slot as one job of `matcher` (take it with
+        matcher.wait()); a host frame is read from the detector's own copy, which lasts until the next enqueue here.  A frame that came in at scale 2 takes quads in
+        detector coordinates.  ValueError on an argument error (nothing enqueued)."""
+        q, n = _quads_arg(quads)
+        r = lib().rd_detector_match_polled(self.h, matcher.h, q.ctypes.data, n, int(flags))
+        if r == -1:
+            raise ValueError("rd_detector_match_polled: invalid arguments (nothing polled yet, %d quads, flags %r)" % (n, flags))
+        matcher._jobs.append((n, matcher.templates(), int(flags)))
         return r
 
 
@@ -833,6 +863,91 @@ class Compositor(_Service):
     def composite(self, frame_bgr, items, patches=None):
         """convenience: a numpy BGR image with `items` composited into it, as a new array, through pinned memory (one job, waited for)"""
         return self._frame_through_pinned(frame_bgr, items, patches)
+
+
+def match_limits():
+    """{"grids", "oversamplings", "max_templates", "max_quads"} of the matcher (rd_match_limits); runs without a GPU"""
+    out = np.zeros(4, np.int32)
+    lib().rd_match_limits(out.ctypes.data)
+    bits = lambda v: tuple(1 << k for k in range(31) if v >> k & 1)
+    return {"grids": bits(int(out[0])), "oversamplings": bits(int(out[1])), "max_templates": int(out[2]), "max_quads": int(out[3])}
+
+
+def match_score(rec, grid, sb, sbb, sb2=0, sbb2=0):
+    """a MATCH_DTYPE record completed on the host (rd_match_score): score and score2 from its integers and the sums of the best column and of the runner-up's; a
+    record whose status is not 1 gets every other field zeroed.  Returns a new record; runs without a GPU"""
+    r = np.array(rec, dtype=MATCH_DTYPE).reshape(1).copy()
+    lib().rd_match_score(r.ctypes.data, int(grid), int(sb), int(sbb), int(sb2), int(sbb2))
+    return r[0]
+
+
+class Matcher(_Service):
+    """The rd_matcher extension: a library of up to max_templates templates, up to max_quads quads per job scored against it on the device, njobs jobs in flight
+    (the contract: include/rectdetect_hip.h, "matched quads")."""
+    _name = "matcher"
+
+    def __init__(self, grid=32, oversample=4, max_templates=64, max_quads=64, njobs=2, device=0):
+        self.grid, self.oversample, self.max_templates, self.max_quads, self.njobs = grid, oversample, max_templates, max_quads, njobs
+        self._jobs = []      # (n, T at enqueue, flags) of the jobs in flight, oldest first: what wait() needs to size its arrays
+        self._create(device, grid, oversample, max_templates, max_quads, njobs)
+
+    def templates(self):
+        return lib().rd_matcher_templates(self.h)
+
+    def add(self, fmt, planes, pitches, iw, ih, quad=None, on_device=False, pinned=False):
+        """a template from `quad` (8 doubles, patch order; None: the whole image) of an iw x ih image in format fmt (planes / pitches as Detector.enqueue_planes): its
+        number.  ValueError on an argument error or a full library, ArithmeticError for a flat template or an invalid quad (nothing added)."""
+        ptrs, pitch_c, kind, pitch, _ = _plane_args(planes, pitches, on_device, pinned)
+        q = None if quad is None else np.ascontiguousarray(quad, dtype=np.float64).reshape(8)
+        r = lib().rd_matcher_add(self.h, int(fmt), ptrs, pitch_c, int(iw), int(ih), kind, None if q is None else q.ctypes.data)
+        if r == -1:
+            raise ValueError("rd_matcher_add: invalid arguments or a full library (format %r, pitches %r, %dx%d, %d templates)" % (fmt, pitch, iw, ih, self.templates()))
+        if r == -2:
+            raise ArithmeticError("rd_matcher_add: a flat template or an invalid quad")
+        return r
+
+    def add_image(self, image_bgr, quad=None):
+        """convenience: add() of a numpy BGR image"""
+        a = np.asarray(image_bgr, dtype=np.uint8)
+        return self.add(PIX_BGR, a, None, a.shape[1], a.shape[0], quad)
+
+    def signature(self, tmpl, rot=0):
+        """test tap: (the grid x grid int8 signature of column 4 * tmpl + rot, sb, sbb) (rd_matcher_signature)"""
+        out, sums = np.zeros((self.grid, self.grid), np.int8), np.zeros(2, np.int32)
+        if lib().rd_matcher_signature(self.h, int(tmpl), int(rot), out.ctypes.data, sums.ctypes.data) != 0:
+            raise IndexError("rd_matcher_signature: no column %r, %r" % (tmpl, rot))
+        return out, int(sums[0]), int(sums[1])
+
+    def enqueue(self, fmt, planes, pitches, iw, ih, quads, flags=0, on_device=False, pinned=False):
+        """one job: the records of `quads` (n x 8 or n x 4 x 2 doubles, patch order) of an iw x ih frame in format fmt (PIX_*).  planes / pitches as
+        Detector.enqueue_planes: numpy planes (copied before the call returns; pitches may be None), or with on_device / pinned their addresses, read in place until the
+        job's wait().  flags: MATCH_DOTS keeps the dot matrix.  Returns the job's sequence number; ValueError on an argument error (nothing enqueued)."""
+        ptrs, pitch_c, kind, pitch, _ = _plane_args(planes, pitches, on_device, pinned)
+        q, n = _quads_arg(quads)
+        r = lib().rd_matcher_enqueue(self.h, int(fmt), ptrs, pitch_c, int(iw), int(ih), kind, q.ctypes.data, n, int(flags))
+        if r == -1:
+            raise ValueError("rd_matcher_enqueue: invalid arguments (format %r, pitches %r, %dx%d, %d quads, flags %r)" % (fmt, pitch, iw, ih, n, flags))
+        self._jobs.append((n, self.templates(), int(flags)))
+        return r
+
+    def wait(self, dots=False):
+        """blocks until the oldest job is done: its MATCH_DTYPE records; with dots=True (a job enqueued with MATCH_DOTS) also its (n, 4T) int32 dot matrix"""
+        if not self._jobs:
+            raise RuntimeError("rd_matcher_wait: no job in flight")
+        n, T, flags = self._jobs.pop(0)
+        recs = np.zeros(max(n, 1), MATCH_DTYPE)
+        want = dots and (flags & MATCH_DOTS)
+        d = np.zeros((max(n, 1), max(4 * T, 1)), np.int32) if want else None
+        got = lib().rd_matcher_wait(self.h, recs.ctypes.data, d.ctypes.data if want else None)
+        if got != n:
+            raise RuntimeError("rd_matcher_wait: %d records, expected %d" % (got, n))
+        return (recs[:n], d[:n, :4 * T] if want else None) if dots else recs[:n]
+
+    def match(self, frame_bgr, quads):
+        """convenience: the records of `quads` in a numpy BGR image (one job, waited for)"""
+        a = np.asarray(frame_bgr, dtype=np.uint8)
+        self.enqueue(PIX_BGR, a, None, a.shape[1], a.shape[0], quads)
+        return self.wait()
 
 
 def postprocess_planes(segs, boundary, table, iw, ih, tan_aov):

@@ -1558,7 +1558,7 @@ void *rd_detector_poll(rd_detector *d, double tanAOV) {
   return r;
 }
 
-// The frame of the most recently polled slot as a job of a service takes it (rd_rectify.hip, rd_annotate.hip, rd_composite.hip): format, planes and row strides as
+// The frame of the most recently polled slot as a job of a service takes it (rd_rectify.hip, rd_annotate.hip, rd_composite.hip, rd_match.hip): format, planes and row strides as
 // hand_over left them - device pointers in every case, which a service's stream may read at once: the poll has waited for the frame's last kernel - at the size it
 // came in.  own: a host or pinned frame's copy in the slot's own buffer (bgr, or sc_bgr at scale 2), which the next frame of this slot overwrites and no job may write.
 // false: nothing polled yet, or `service` is no live service of this kind on the detector's device; cap: the most items one of its jobs takes.
@@ -1595,6 +1595,15 @@ long rd_detector_rectify_polled(rd_detector *d, rd_rectifier *r, const double *q
   void *m = mapped_to_source(&f, "rd_detector_rectify_polled", quads, n, 8 * sizeof(double));
   const long q = rd_rectifier_enqueue(r, f.fmt, f.planes, f.pitch, f.iw, f.ih, RD_FRAME_DEVICE, m ? (const double *)m : quads, n, out, out_kind);
   free(m);
+  return q;
+}
+// Matched quads of the polled frame; nothing of the slot is written.
+long rd_detector_match_polled(rd_detector *d, rd_matcher *m, const double *quads, int n, int flags) {
+  PolledFrame f;
+  if (!polled_frame(d, "rd_detector_match_polled", m, RD_MAGIC_MATCHER, &f)) return -1;
+  void *mq = mapped_to_source(&f, "rd_detector_match_polled", quads, n, 8 * sizeof(double));
+  const long q = rd_matcher_enqueue(m, f.fmt, f.planes, f.pitch, f.iw, f.ih, RD_FRAME_DEVICE, mq ? (const double *)mq : quads, n, flags);
+  free(mq);
   return q;
 }
 // Annotated frames: a caller's device frame may be drawn into in place; the slot's own copy needs a destination.

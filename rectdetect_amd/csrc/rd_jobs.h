@@ -1,5 +1,5 @@
-// rectdetect-mi355x: what the services behind the detector's poll share on the host - the rectifier (rd_rectify.hip), the annotator (rd_annotate.hip) and the
-// compositor (rd_composite.hip): the layout of a frame's planes, a device buffer that grows, the ring of jobs in flight on a stream of the service's own, the checks
+// rectdetect-mi355x: what the services behind the detector's poll share on the host - the rectifier (rd_rectify.hip), the annotator (rd_annotate.hip), the
+// compositor (rd_composite.hip) and the matcher (rd_match.hip): the layout of a frame's planes, a device buffer that grows, the ring of jobs in flight on a stream of the service's own, the checks
 // of a frame's and a destination's arguments, and a frame's way to the device and back to pinned memory.  Helpers that a service's enqueue calls, top to bottom;
 // nothing here knows a kernel, a record or what a job's items are.  No graphs, no threads, no environment switches.
 #pragma once
@@ -66,6 +66,7 @@ struct DevBuf {
 #define RD_MAGIC_RECTIFIER 0x52445246u
 #define RD_MAGIC_ANNOTATOR 0x5244414eu
 #define RD_MAGIC_COMPOSITOR 0x5244434fu
+#define RD_MAGIC_MATCHER 0x52444d41u
 struct Ring {
   uint32_t magic;
   int device, per_job, njobs;

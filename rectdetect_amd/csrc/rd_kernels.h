@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <atomic>
 #include "rd_annot_cover.h"
+#include "rectdetect_hip.h"
 
 // Group launches (small frames, rd_api.hip): launchers of the frame path take `nz` frames per launch and `zs`, the byte pitch between the planes
 // of consecutive frame slots (rd_device.h: RD_ZSHIFT); the defaults launch one frame.
@@ -151,6 +152,17 @@ void polyline_ids(hipStream_t s, const PolyFrame *frames, int nb, int n);
 struct RectifyQuad { double c[8]; int status; int pad; };
 // n patches of pw x ph BGR pixels, patch k at out + k * pw * ph * 3, from one iw x ih frame in format fmt (RD_PIX_*; planes / pitch as the caller's), one launch (quad = blockIdx.z)
 void rectify(hipStream_t s, uint8_t *out, int fmt, const uint8_t *const planes[3], const int pitch[3], int iw, int ih, const RectifyQuad *quads, int n, int pw, int ph);
+
+// ---- rd_k_match.hip: matched quads (the contract: rectdetect_hip.h, "matched quads")
+// the signatures of n quads of one frame: quad k's G * G int8 values at sig + k * G * G (zeros for an invalid quad), its sa, saa ADDED to sums[2k], sums[2k+1]
+// (cleared by the caller); G in {8, 16, 32, 64}, m in {1, 2, 4}
+void match_signatures(hipStream_t s, int8_t *sig, int *sums, int fmt, const uint8_t *const planes[3], const int pitch[3], int iw, int ih, const RectifyQuad *quads, int n, int G, int m);
+// dots[q * ld + c] = signature q . column c for q < n rounded up to 16, c < ncols rounded up to 16: sig, lib and dots hold the padding rows and columns
+void match_dots(hipStream_t s, int *dots, int ld, const int8_t *sig, int n, const int8_t *lib, int ncols, int D);
+// the records of n quads, without their scores; colsums: sb, sbb per column
+void match_pick(hipStream_t s, rd_match *recs, const int *dots, int ld, const int *colsums, int ncols, const int *sums, const RectifyQuad *quads, int n, int D);
+// the four columns of a template (lib4: 4 * G * G bytes) from its signature
+void match_rotations(hipStream_t s, int8_t *lib4, const int8_t *sig, int G);
 
 // ---- rd_k_annotate.hip: annotated frames (the contract: rectdetect_hip.h, "annotated frames")
 // what a job uploads per primitive: its line record (rd_annot_cover.h) and its colour - the three bytes a covered pixel gets, in the order the frame's format
