@@ -196,6 +196,22 @@ void *rd_postprocess_planes_device(int device, const void *segs, const int32_t *
  * Runs without a GPU. */
 void rd_post_device_limits(int32_t out[8]);
 
+/* test tap: the polyline stage alone (oclpolyline_execute's kernels, rd_k_poly.hip) on a caller's mask, in the form the caller names, so that the capacity edges of
+ * its single-block kernel and crafted lists can be tested.  Uploads `mask` (iw * ih ints, zero / non-zero) to `device`, runs the stage and the id plane once, on a
+ * stream and scratch of its own, then frees everything.  ring_nonzero: the value the 2-px frame ring of the bridging step's output takes (the reference leaves
+ * that ring stale).  form 0 = the multi-launch form (what oclpolyline_execute runs), form 1 = the single-block kernel the detectors try first.  Out: lslist_out =
+ * lslist_bytes bytes of the list (record 0 = header), ids_out = iw * ih ints, ctr_out = the stage's 64 counters ("polyctr" of rd_detector_debug_plane): [0] chain
+ * pixels, [1] chains K, [2 + r] split candidates of round r (form 0), [24] live pixels, [25] != 0: the single-block kernel gave up - nothing repeats the stage
+ * here, the list and the id plane are then not meaningful -, [39..45] 100 MHz time stamps of the single-block kernel's phases ([43], [44]: around the end-point join).
+ * Returns 0, or -1 without touching the device for a null pointer, a plane smaller than 5 x 5 or larger than 65535 x 32767, a form other than 0 / 1, a negative
+ * size_thre, or lslist_bytes outside [112, 16 * iw * ih].  Needs a GPU (fatal without one); not called by the frame path. */
+int rd_polyline_planes_device(int device, const int32_t *mask, int iw, int ih, int ring_nonzero, float minerror, int size_thre, int lslist_bytes, int form,
+                              void *lslist_out, int32_t *ids_out, int32_t ctr_out[64]);
+/* the fixed capacities of the single-block kernel: out[0] live pixels (chain pixels of chains longer than size_thre), [1] records, header included (the largest
+ * id is one less; at most [1] - 2 initial chains), [2] split candidates in one round, [3] bits of a record id in the kernel's per-pixel word.  A frame beyond any
+ * of them is flagged and repeated in multi-launch form, which has no such bounds.  Runs without a GPU. */
+void rd_polyline_limits(int32_t out[4]);
+
 /* ---- rectified patches: what is INSIDE a quad, as an upright image of fixed size (rd_k_rectify.hip, rd_rectify.hip).
  * The reference only draws outlines (rect.cpp, vidrect.cpp), so the arithmetic is defined here - exactly, so that an independent restatement (tests/rectify.py,
  * numpy float64) reproduces every byte.

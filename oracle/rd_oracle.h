@@ -18,6 +18,8 @@ typedef struct {
   int *sub_label;   /* labels after the numbering-continuity split (tmpBig at oclpolyline.c:280) */
   int *ids0;        /* compact ids before subdivision (lsIdOut at oclpolyline.c:295) */
   int converged;    /* out: always 1 here (union-find); kept for symmetry with fixtures */
+  void *before_join; /* the list (lslist_bytes bytes) as the end-point join finds it: after refine_pass2, before refine_pass3 (oclpolyline.c:305) */
+  int candidates[15]; /* out: records handed out in each subdivision round (rounds that were not evaluated keep the caller's value) */
 } rdo_poly_dbg_t;
 
 const uint16_t *rdo_lut(int which, int *n);

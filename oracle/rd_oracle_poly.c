@@ -269,8 +269,9 @@ void rdo_polyline(void *lslist, int lslist_bytes, int *ids, const int *in, int r
 
   int *dist = C;
   void *old = malloc((size_t)lslist_bytes);
-  int moved_prev = 1;
+  int moved_prev = 1;   /* (a round after one that moved no pixel and left no candidate without a record finds what that one found: the reference's 15 rounds are cut short there) */
   for (int it = 1; it <= 15 && moved_prev; it++) {
+    int ncand = 0, unplaced = 0;
     /* pass 1: distance of every chain pixel to its segment's chord, per-segment maximum (pl:509-540) */
     for (int p = 0; p < N; p++) {
       const int g = ids[p];
@@ -302,7 +303,8 @@ void rdo_polyline(void *lslist, int lslist_bytes, int *ids, const int *in, int r
       if (dist2f((float)x, (float)y, gp[g].x1, gp[g].y1) < 1) continue;
       const int gr = gp[g].rightPtr;
       const int gn = ++hdr[0];
-      if (!FITS(gn)) continue;
+      ncand++;
+      if (!FITS(gn)) { unplaced = 1; continue; }
       ls[gn].startIndex = n; ls[gn].endIndex = gp[g].endIndex;
       ls[gn].x0 = (float)x; ls[gn].y0 = (float)y; ls[gn].x1 = gp[g].x1; ls[gn].y1 = gp[g].y1;
       ls[gn].leftPtr = g; ls[gn].rightPtr = gp[g].rightPtr;
@@ -317,12 +319,15 @@ void rdo_polyline(void *lslist, int lslist_bytes, int *ids, const int *in, int r
       if (g == 0 || !FITS(g) || ls[g].polyid == 0) continue;
       if (ls[g].endIndex < number[p]) { ids[p] = ls[g].rightPtr; moved = 1; }
     }
-    moved_prev = moved;
+    moved_prev = moved || unplaced;
+    if (dbg) dbg->candidates[it - 1] = ncand;
   }
   free(old);
 
   /* ---------------------------------------------------------------- :299-306 refine, pl:680-809 */
-  const int nseg = hdr[0];
+  /* (a list too short for every record: the header counts the ids handed out, the records stop where FITS stops) */
+  int nseg = hdr[0];
+  while (nseg > 0 && !FITS(nseg)) nseg--;
   lsx_t *sx = (lsx_t *)calloc((size_t)nseg + 2, sizeof(lsx_t));
   for (int g = 1; g <= nseg; g++) {
     if (ls[g].polyid == 0) continue;
@@ -355,6 +360,7 @@ void rdo_polyline(void *lslist, int lslist_bytes, int *ids, const int *in, int r
     ls[g].x0 += (float)sx[g].vx * as1; ls[g].y0 += (float)sx[g].vy * as1;
     ls[g].x1 += (float)sx[g].vx * (as0 + as1); ls[g].y1 += (float)sx[g].vy * (as0 + as1);
   }
+  if (dbg && dbg->before_join) memcpy(dbg->before_join, lslist, (size_t)lslist_bytes);
   for (int g = 1; g <= nseg; g++) {                                                                       /* pl:772-809, ascending g (H15) */
     if (ls[g].polyid == 0) continue;
     const int h = ls[g].rightPtr;

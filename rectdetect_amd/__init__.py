@@ -93,6 +93,8 @@ def _declare(L):
         "rd_postprocess_planes": (vp, [vp, vp, vp, ci, ci, cd]),
         "rd_postprocess_planes_device": (vp, [ci, vp, vp, vp, ci, ci, cd, vp]),
         "rd_post_device_limits": (None, [vp]),
+        "rd_polyline_planes_device": (ci, [ci, vp, ci, ci, ci, cf, ci, ci, ci, vp, vp, vp]),
+        "rd_polyline_limits": (None, [vp]),
         "rd_probe_pixels": (None, [cf, cf, cf, cf, ci, ci, vp]),
         "rd_post_run": (vp, [vp, ci, vp, ci, ci, cd]),
         "rd_post_helpers_configure": (None, [ci]),
@@ -977,3 +979,29 @@ def postprocess_planes_device(segs, boundary, table, iw, ih, tan_aov, device=0):
     info = np.zeros(8, np.int32)
     ptr = lib().rd_postprocess_planes_device(int(device), segs.ctypes.data, boundary.ctypes.data, table.ctypes.data, iw, ih, float(tan_aov), info.ctypes.data)
     return (_take_rects(ptr) if ptr else None), info
+
+
+POLY_LIMIT_NAMES = ("PP_LIVE", "PP_MAXSEG", "PP_MAXCAND", "PP_ID_BITS")
+
+
+def polyline_limits():
+    """The fixed capacities of the polyline stage's single-block kernel (rd_polyline_limits) by name; runs without a GPU."""
+    out = np.zeros(4, np.int32)
+    lib().rd_polyline_limits(out.ctypes.data)
+    return dict(zip(POLY_LIMIT_NAMES, (int(v) for v in out)))
+
+
+def polyline_planes_device(mask, ring_nonzero, minerror, size_thre, lslist_bytes=None, form=0, device=0):
+    """The polyline stage alone (rd_polyline_planes_device) on a 2-D mask: (list, ids, ctr).  form 0 = multi-launch, 1 = the single-block kernel, which does
+    not fall back: ctr[25] != 0 says it gave up.  list holds the header and the records lslist_bytes has room for (default: 16 bytes per pixel).  Needs a GPU."""
+    mask = np.ascontiguousarray(mask, dtype=np.int32)
+    ih, iw = mask.shape
+    nbytes = iw * ih * 16 if lslist_bytes is None else int(lslist_bytes)
+    raw = np.zeros((nbytes + 3) // 4, np.int32)
+    ids = np.zeros(iw * ih, np.int32)
+    ctr = np.zeros(64, np.int32)
+    if lib().rd_polyline_planes_device(int(device), mask.ctypes.data, iw, ih, int(ring_nonzero), float(minerror), int(size_thre), nbytes, int(form),
+                                       raw.ctypes.data, ids.ctypes.data, ctr.ctypes.data) != 0:
+        raise ValueError("rd_polyline_planes_device: invalid arguments")
+    n = min(int(raw[0]), nbytes // 56 - 1)
+    return raw[: 14 * (max(n, 0) + 1)].view(LS_DTYPE).copy(), ids, ctr

@@ -1900,4 +1900,40 @@ void *rd_postprocess_planes_device(int device, const void *segs, const int32_t *
   return ret;
 }
 
+// ---- test taps of the polyline stage (neither is on the frame path)
+void rd_polyline_limits(int32_t out[4]) { rdk::poly_limits(out); }
+
+// oclpolyline_execute's twin with the form of the stage chosen by the caller: the caller's 0/1 plane through rdk::polyline and rdk::polyline_ids,
+// once, on a stream and scratch of its own.  form 1 is the single-block kernel alone: where it gives up (ctr_out[25]) nothing repeats the stage,
+// the caller sees the flag and whatever list the kernel left.
+int rd_polyline_planes_device(int device, const int32_t *mask, int iw, int ih, int ring_nonzero, float minerror, int size_thre, int lslist_bytes, int form,
+                              void *lslist_out, int32_t *ids_out, int32_t ctr_out[64]) {
+  // (the stage's scratch is sized for lists of up to 16 bytes per pixel, what every caller in the reference passes; two records are the least a list holds)
+  if (!mask || !lslist_out || !ids_out || !ctr_out || iw < 5 || ih < 5 || iw > 0xffff || ih > 0x7fff || (form != 0 && form != 1) || size_thre < 0 ||
+      lslist_bytes < 2 * 56 || (long long)lslist_bytes > (long long)iw * ih * 16) return -1;
+  RD_HIP(hipSetDevice(device));
+  const size_t N = (size_t)iw * ih;
+  int *d_mask = dnew<int>(N), *d_ids = dnew<int>(N);
+  char *d_ls = dnew<char>((size_t)lslist_bytes + 56);
+  rdk::PolyScratch *ps = rdk::poly_scratch_create(iw, ih);
+  hipStream_t st = NULL;
+  RD_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  RD_HIP(hipMemcpyAsync(d_mask, mask, N * sizeof(int), hipMemcpyHostToDevice, st));
+  RD_HIP(hipMemsetAsync(d_ls, 0, (size_t)lslist_bytes + 56, st));
+  rdk::PolyFrame f;
+  memset(&f, 0, sizeof(f));
+  f.ps = *ps; f.in = d_mask; f.lslist = d_ls; f.ids = d_ids;
+  rdk::polyline(st, &f, 1, lslist_bytes, ring_nonzero ? 1 : 0, minerror, size_thre, iw, ih, form);
+  rdk::polyline_ids(st, &f, 1, (int)N);
+  rdrt::check_launch("rd_polyline_planes_device");
+  RD_HIP(hipMemcpyAsync(lslist_out, d_ls, (size_t)lslist_bytes, hipMemcpyDeviceToHost, st));
+  RD_HIP(hipMemcpyAsync(ids_out, d_ids, N * sizeof(int), hipMemcpyDeviceToHost, st));
+  RD_HIP(hipMemcpyAsync(ctr_out, rdk::poly_scratch_counters(ps), 64 * sizeof(int), hipMemcpyDeviceToHost, st));
+  RD_HIP(hipStreamSynchronize(st));
+  RD_HIP(hipStreamDestroy(st));
+  rdk::poly_scratch_destroy(ps);
+  dfree(d_ls); dfree(d_ids); dfree(d_mask);
+  return 0;
+}
+
 }  // extern "C"

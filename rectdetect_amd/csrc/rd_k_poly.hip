@@ -596,7 +596,8 @@ __device__ __forceinline__ void d_seg_finish(const rdk::PolyFrames &FRS, int lsb
       ls[g].polyid = g;
     } else ls[g].polyid = 0;
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0) { const int maxrec = lsbytes / 56; *(int *)ls = K < maxrec - 1 ? K : (maxrec >= 2 ? maxrec - 2 : 0); }
+  // header = the largest id with a record (pl:439-472 raises it under the same FITS test as the record): FITS(g) <=> g <= (lsbytes - 1) / 56 - 1
+  if (blockIdx.x == 0 && threadIdx.x == 0) { const int top = lsbytes >= 57 ? (lsbytes - 1) / 56 - 1 : 0; *(int *)ls = K < top ? K : top; }
 }
 __global__ void k_seg_finish(const rdk::PolyFrames FRS, int lsbytes, int iw) { d_seg_finish(FRS, lsbytes, iw); }
 
@@ -774,33 +775,47 @@ __global__ void k_refine2(const rdk::PolyFrames FRS, int maxrec) { d_refine2(FRS
 
 // pl:772-809.  Segment g joins its end point with the start point of its right neighbour h, and h's own step reads that
 // start point, so the result depends on the order of the steps; the canonical order is ascending g.
-// Steps of non-adjacent segments commute, hence the serial result is obtained by letting a segment run as soon as every
-// neighbour with a smaller id has run and keeping neighbours with larger ids waiting: one block, rounds separated by
-// barriers; `done` lives in global scratch.
+// Two steps commute unless one writes a point the other touches: step g writes g's end and h's start and reads both
+// records whole.  The list is not always a clean chain: when two pixels tie for a segment's maximum in a subdivision
+// round, the earlier one in raster order leaves an orphan record whose rightPtr is h while h's leftPtr is another
+// record - then two steps have the SAME right neighbour and leftPtr does not name every step that writes g's start.
+// So the steps are ordered by rightPtr alone: first[x] = the smallest unfinished step whose right neighbour is x (one
+// atomicMin pass per round), and step g runs in a round when
+//   it is the smallest unfinished step with right neighbour h                 (first[h] == g),
+//   no unfinished step with a smaller id has g as its right neighbour          (first[g] > g),
+//   h's own step, if its id is smaller, is finished                            (h > g or done[h] == 1).
+// The smallest unfinished step always passes, so every round makes progress and the result is the serial one.
+// One block, three barriers per round (first[] complete / verdicts complete / steps complete); `done` and `first` live in global scratch.
+// progress[round & 1] says whether the round ran a step: two flags, so that the one a round is about to set can be cleared while the
+// slowest thread may still be reading the other.
 __device__ __forceinline__ void d_refine3(const rdk::PolyFrames &FRS, int maxrec) {
   RD_FRAME;
   ls_rec *ls = (ls_rec *)FRM.lslist;
-  __shared__ int progress;
+  __shared__ int progress[2];
   const int n0 = *(const int *)ls;
   const int n = n0 < maxrec - 1 ? n0 : maxrec - 1;
   int *done = s.dist;   // free at this point; n <= cap
-  for (int g = threadIdx.x + 1; g <= n; g += 1024) done[g] = (ls[g].polyid == 0 || ls[g].rightPtr == 0) ? 1 : 0;
+  int *first = s.flag;  // free since the chain ends were found; n <= cap
+  for (int g = threadIdx.x; g <= n; g += 1024) { done[g] = (g == 0 || ls[g].polyid == 0 || ls[g].rightPtr == 0) ? 1 : 0; first[g] = 0x7fffffff; }
+  if (threadIdx.x == 0) { progress[0] = 0; progress[1] = 0; }
   __syncthreads();
   for (int iter = 0; iter <= n; iter++) {
-    if (threadIdx.x == 0) progress = 0;
+    for (int g = threadIdx.x + 1; g <= n; g += 1024) if (!done[g]) atomicMin(&first[ls[g].rightPtr], g);
     __syncthreads();
+    if (threadIdx.x == 0) progress[(iter + 1) & 1] = 0;   // (the next round's; every thread has read it for the last time before the barrier above)
     // decide with the flags as they are at the start of the round
     for (int g = threadIdx.x + 1; g <= n; g += 1024) {
       if (done[g]) continue;
-      const int h = ls[g].rightPtr, l = ls[g].leftPtr;
-      // every step that touches g's or h's coordinates and has a smaller id must be finished:
-      //   left neighbour l (writes g.start), h itself (reads/writes h.start, h.end), h's right neighbour does not touch g or h.start
-      const bool l_ok = l <= 0 || l > g || l > n || done[l] == 1;
-      const bool h_ok = h > g || h > n || done[h] == 1;
-      if (l_ok && h_ok) done[g] = 2;   // runs in this round
+      const int h = ls[g].rightPtr;
+      const bool f_ok = first[h] == g;
+      const bool l_ok = first[g] > g;
+      const bool h_ok = h > g || done[h] == 1;
+      if (f_ok && l_ok && h_ok) done[g] = 2;   // runs in this round
     }
     __syncthreads();
+    // the steps of the round; nothing reads done[] or first[] in this phase, so both are brought up to date for the next round on the way
     for (int g = threadIdx.x + 1; g <= n; g += 1024) {
+      first[g] = 0x7fffffff;
       if (done[g] != 2) continue;
       const int h = ls[g].rightPtr;
       const float v0 = ls[g].x0, v1 = ls[g].y0, v2 = ls[g].x1, v3 = ls[g].y1;
@@ -818,13 +833,11 @@ __device__ __forceinline__ void d_refine3(const rdk::PolyFrames &FRS, int maxrec
         if (e0 > 10 && e1 > 10) { wx = (v2 + u0) * 0.5f; wy = (v3 + u1) * 0.5f; }
       }
       ls[g].x1 = wx; ls[g].y1 = wy; ls[h].x0 = wx; ls[h].y0 = wy;
-      progress = 1;
+      done[g] = 1;
+      progress[iter & 1] = 1;
     }
     __syncthreads();
-    for (int g = threadIdx.x + 1; g <= n; g += 1024) if (done[g] == 2) done[g] = 1;
-    __syncthreads();
-    if (!progress) break;
-    __syncthreads();
+    if (!progress[iter & 1]) break;
   }
 }
 __global__ __launch_bounds__(1024) void k_refine3(const rdk::PolyFrames FRS, int maxrec) { d_refine3(FRS, maxrec); }
@@ -845,7 +858,7 @@ struct pp_lds {
   int start_i[PP_MAXSEG], end_i[PP_MAXSEG];
   int done[PP_MAXSEG];
   int cand[PP_MAXCAND * 8];
-  int ncand, count, fail, progress;
+  int ncand, count, fail, progress[2];
 };
 
 __device__ __noinline__ int2 pp_move_dist(pp_lds &L, int pk, int xyv, int dreg, bool move_only, int rnd13, int round) {
@@ -952,7 +965,7 @@ __global__ __launch_bounds__(PP_T) void k_poly_persistent(const rdk::PolyFrames 
   }
   for (int g = tid; g < PP_MAXSEG; g += PP_T) L.done[g] = 0;   // during the rounds: round in which the segment has to be looked at again
   for (int g = tid; g <= K; g += PP_T) { ls_rec z = {}; L.rec[g] = z; L.start_i[g] = -1; L.end_i[g] = 0x7fffffff; }
-  if (tid == 0) { L.ncand = 0; L.count = K; L.fail = 0; L.progress = 0; }
+  if (tid == 0) { L.ncand = 0; L.count = K; L.fail = 0; L.progress[0] = 0; L.progress[1] = 0; }
   __syncthreads();
 
   if (tid == 0) s.ctr[40] = (int)wall_clock64();
@@ -1039,7 +1052,8 @@ __global__ __launch_bounds__(PP_T) void k_poly_persistent(const rdk::PolyFrames 
       }
     }
     __syncthreads();
-    if (tid == 0) { const int C = L.ncand < PP_MAXCAND ? L.ncand : PP_MAXCAND; L.count = (L.count + C < PP_MAXSEG - 1) ? L.count + C : PP_MAXSEG - 1; L.ncand = 0; }
+    // (the count stops where the records stop - the last id the test above lets through -, so that the copy-out at the end stays inside the caller's list)
+    if (tid == 0) { const int C = L.ncand < PP_MAXCAND ? L.ncand : PP_MAXCAND; const int top = PP_MAXSEG - 1 < maxrec - 2 ? PP_MAXSEG - 1 : maxrec - 2; L.count = (L.count + C < top) ? L.count + C : top; L.ncand = 0; }
     __syncthreads();
   }
 
@@ -1075,21 +1089,25 @@ __global__ __launch_bounds__(PP_T) void k_poly_persistent(const rdk::PolyFrames 
   }
   __syncthreads();
   if (tid == 0) s.ctr[43] = (int)wall_clock64();
-  // end-point joining in dependency order (see k_refine3)
-  for (int g = tid + 1; g <= n; g += PP_T) L.done[g] = (L.rec[g].polyid == 0 || L.rec[g].rightPtr == 0) ? 1 : 0;
+  // end-point joining in dependency order (see d_refine3)
+  int *first = L.start_i;   // free since the initial segments
+  for (int g = tid; g <= n; g += PP_T) { L.done[g] = (g == 0 || L.rec[g].polyid == 0 || L.rec[g].rightPtr == 0) ? 1 : 0; first[g] = 0x7fffffff; }
   __syncthreads();
-  for (int iter = 0; iter <= n; iter++) {
-    if (tid == 0) L.progress = 0;
+  for (int iter = 0; iter <= n; iter++) {      // (L.progress[0..1] are 0 since the start of the kernel)
+    for (int g = tid + 1; g <= n; g += PP_T) if (!L.done[g]) atomicMin(&first[L.rec[g].rightPtr], g);
     __syncthreads();
+    if (tid == 0) L.progress[(iter + 1) & 1] = 0;
     for (int g = tid + 1; g <= n; g += PP_T) {
       if (L.done[g]) continue;
-      const int h = L.rec[g].rightPtr, l = L.rec[g].leftPtr;
-      const bool l_ok = l <= 0 || l > g || l > n || L.done[l] == 1;
-      const bool h_ok = h > g || h > n || L.done[h] == 1;
-      if (l_ok && h_ok) L.done[g] = 2;
+      const int h = L.rec[g].rightPtr;
+      const bool f_ok = first[h] == g;
+      const bool l_ok = first[g] > g;
+      const bool h_ok = h > g || L.done[h] == 1;
+      if (f_ok && l_ok && h_ok) L.done[g] = 2;
     }
     __syncthreads();
     for (int g = tid + 1; g <= n; g += PP_T) {
+      first[g] = 0x7fffffff;
       if (L.done[g] != 2) continue;
       const int h = L.rec[g].rightPtr;
       const float v0 = L.rec[g].x0, v1 = L.rec[g].y0, v2 = L.rec[g].x1, v3 = L.rec[g].y1;
@@ -1107,13 +1125,11 @@ __global__ __launch_bounds__(PP_T) void k_poly_persistent(const rdk::PolyFrames 
         if (e0 > 10 && e1 > 10) { wx = (v2 + u0) * 0.5f; wy = (v3 + u1) * 0.5f; }
       }
       L.rec[g].x1 = wx; L.rec[g].y1 = wy; L.rec[h].x0 = wx; L.rec[h].y0 = wy;
-      L.progress = 1;
+      L.done[g] = 1;
+      L.progress[iter & 1] = 1;
     }
     __syncthreads();
-    for (int g = tid + 1; g <= n; g += PP_T) if (L.done[g] == 2) L.done[g] = 1;
-    __syncthreads();
-    if (!L.progress) break;
-    __syncthreads();
+    if (!L.progress[iter & 1]) break;
   }
 
   if (tid == 0) s.ctr[44] = (int)wall_clock64();
@@ -1178,6 +1194,10 @@ PolyScratch *poly_scratch_create(int iw, int ih) {
 }
 
 const int *poly_scratch_counters(const PolyScratch *ps) { return ps->ctr; }
+
+// the fixed capacities of k_poly_persistent (tests build masks that sit on each of them)
+static_assert(PP_MAXSEG <= (1 << 11), "a record id must fit the id field of the packed per-pixel word");
+void poly_limits(int out[4]) { out[0] = PP_T * PP_PX; out[1] = PP_MAXSEG; out[2] = PP_MAXCAND; out[3] = 11; }
 
 void poly_scratch_destroy(PolyScratch *ps) {
   if (!ps) return;

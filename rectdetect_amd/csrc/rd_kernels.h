@@ -140,6 +140,7 @@ void post_device(hipStream_t s, const PolyFrame *frames, int nb, int max_records
 PolyScratch *poly_scratch_create(int iw, int ih);
 void poly_scratch_destroy(PolyScratch *ps);
 const int *poly_scratch_counters(const PolyScratch *ps);   // device pointer: [0] chain pixels, [1] chains, [2+r] split candidates of round r
+void poly_limits(int out[4]);    // the single-block kernel's PP_T * PP_PX live pixels, PP_MAXSEG records, PP_MAXCAND candidates per round, bits of a record id
 // frames: nb descriptors (host memory); frames[z].ring_src: plane whose 2-px frame ring supplies the stale ring values (null -> ring_const)
 void polyline(hipStream_t s, const PolyFrame *frames, int nb, int lslist_bytes, int ring_const, float minerror, int sizeThre, int iw, int ih, int mode);
 // poly kind: counters + the first `records` records of each frame's list (header included) into frames[z].pack (pinned host memory)
