@@ -212,6 +212,37 @@ int rd_polyline_planes_device(int device, const int32_t *mask, int iw, int ih, i
  * of them is flagged and repeated in multi-launch form, which has no such bounds.  Runs without a GPU. */
 void rd_polyline_limits(int32_t out[4]);
 
+/* test tap: the region stage alone (oclrect.c:325-342: region merge, region sizes, absorption of small regions, region boundaries and their components - rd_k_rect.hip,
+ * rd_k_label.hip) on planes of the caller, so that its launch budgets, fixed capacities and fallback paths can be tested on crafted planes.  Runs once on `device`, on a
+ * stream, planes and scratch of its own, then frees everything.  All planes are iw * ih ints.
+ * stage 0, from the merge's inputs: pix = the quantised colour, mask = the merge mask (zero / non-zero), edge = the strong-edge plane (> 0: strong edge).  Runs exactly what
+ *   a frame runs.  launches = an even budget in 2..128 for the merge, or 0 for the frame path's behaviour: 20 launches, and where the last of them still changed something
+ *   the ladder of 32, 64, 128 - the frame path's own function.  region0_in / rsize_in are not read.
+ * stage 1, from the absorption's inputs: region0_in = a label per pixel, each in [0, iw * ih), rsize_in = the size of every label (indexed by label, each in [0, 2^26)).
+ *   Runs the absorption and the boundary stages.  pix / mask / edge / launches are not read.
+ * Either stage repeats the absorption on its slow path where the fast path's status word asks for it, as the frame path does; force_slow != 0 does so regardless (as
+ * RD_ABSORB_FORCE_SLOW does for a detector).
+ * Out: region0_out (labels after the merge), rsize_out (junction counts + region sizes, by label), region_out (labels after the absorption), boundarysrc_out (boundary
+ * marks), boundary_out (components of the marks), and info: [0..127] the merge's flag per launch of the final budget (!= 0: that launch changed something), [128] the
+ * budget that was final (0 in stage 1), [129] 1 = the merge settled within it, 0 = the planes are what that many launches made of them, [130..133] the absorption's
+ * status words of the fast path ([0] != 0: it gave up, [1] undecided pixels the tile kernel left, [2] sweeps and [3] steps of the tail), [134] the slow path ran, [135] its
+ * launches of the rounds, [136..143] 0.
+ * Returns 0, or -1 without touching the device for a null pointer among the planes the stage reads or writes, a frame rd_detector_create refuses (under 16 x 16, or 2^25
+ * pixels and more), an odd or out-of-range `launches`, a stage other than 0 / 1, a label outside [0, iw * ih) or a size outside [0, 2^26).  Needs a GPU (fatal without
+ * one); not called by the frame path. */
+#define RD_REGION_INFO_INTS 144
+int rd_region_planes_device(int device, int stage, int iw, int ih, const int32_t *pix, const int32_t *mask, const int32_t *edge, int launches,
+                            const int32_t *region0_in, const int32_t *rsize_in, int force_slow,
+                            int32_t *region0_out, int32_t *rsize_out, int32_t *region_out, int32_t *boundarysrc_out, int32_t *boundary_out, int32_t info[RD_REGION_INFO_INTS]);
+/* the constants of the region stage that crafted planes are built from: out[0] the largest budget of launches a frame's merge starts with, [1..4] the budgets of the ladder
+ * a frame still changing in its last launch climbs (0: no further step), [5] the most launches of the merge (the definition's limit), [6] undecided pixels the absorption's
+ * single-block tail holds, [7] its sweeps at most, [8] its threads (pixels per thread: the smallest of [19..25] that covers the count), [9] halo of the absorption's tile
+ * kernel, [10] small-region cells a tile can own, [11] x [12] the merge's tile, [13] x [14] the absorption's, [15] the absorption threshold (regions up to this size are
+ * absorbed), [16] launches after which the slow absorption calls a missing fixed point an internal error and [17] records of undecided pixels the fast path has room for,
+ * both for an iw x ih frame (0 if iw or ih is not positive), [18] rounds of the tile kernel, [19..25] the tail's pixels-per-thread variants, [26] bits of a region size in
+ * the tail's words, [27..31] 0.  Runs without a GPU. */
+void rd_region_limits(int iw, int ih, int32_t out[32]);
+
 /* ---- rectified patches: what is INSIDE a quad, as an upright image of fixed size (rd_k_rectify.hip, rd_rectify.hip).
  * The reference only draws outlines (rect.cpp, vidrect.cpp), so the arithmetic is defined here - exactly, so that an independent restatement (tests/rectify.py,
  * numpy float64) reproduces every byte.

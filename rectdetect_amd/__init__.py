@@ -95,6 +95,8 @@ def _declare(L):
         "rd_post_device_limits": (None, [vp]),
         "rd_polyline_planes_device": (ci, [ci, vp, ci, ci, ci, cf, ci, ci, ci, vp, vp, vp]),
         "rd_polyline_limits": (None, [vp]),
+        "rd_region_planes_device": (ci, [ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp]),
+        "rd_region_limits": (None, [ci, ci, vp]),
         "rd_probe_pixels": (None, [cf, cf, cf, cf, ci, ci, vp]),
         "rd_post_run": (vp, [vp, ci, vp, ci, ci, cd]),
         "rd_post_helpers_configure": (None, [ci]),
@@ -1005,3 +1007,48 @@ def polyline_planes_device(mask, ring_nonzero, minerror, size_thre, lslist_bytes
         raise ValueError("rd_polyline_planes_device: invalid arguments")
     n = min(int(raw[0]), nbytes // 56 - 1)
     return raw[: 14 * (max(n, 0) + 1)].view(LS_DTYPE).copy(), ids, ctr
+
+
+REGION_INFO_INTS = 144
+
+
+def region_limits(iw=0, ih=0):
+    """The constants of the region stage that crafted planes are built from (rd_region_limits) by name; slow_bound and reccap are those of an iw x ih frame.
+    Runs without a GPU."""
+    out = np.zeros(32, np.int32)
+    lib().rd_region_limits(int(iw), int(ih), out.ctypes.data)
+    v = [int(x) for x in out]
+    return {"first_budget": v[0], "ladder": [b for b in v[1:5] if b], "max_launches": v[5], "AT_CAP": v[6], "AT_SWEEPS": v[7], "AT_NT": v[8], "AB_HK": v[9], "AB_OWNED": v[10],
+            "merge_tile": (v[11], v[12]), "absorb_tile": (v[13], v[14]), "thre": v[15], "slow_bound": v[16], "reccap": v[17], "tile_rounds": v[18],
+            "EPT": [e for e in v[19:26] if e], "size_bits": v[26]}
+
+
+class RegionPlanes:
+    """What rd_region_planes_device returns: the five planes (2-D) and the info block by name."""
+
+    def __init__(self, shape, planes, info):
+        self.region0, self.rsize, self.region, self.boundarysrc, self.boundary = (p.reshape(shape) for p in planes)
+        m = 128
+        self.info = info
+        self.budget, self.settled = int(info[m]), bool(info[m + 1])
+        self.flags = info[: self.budget].copy()
+        self.status = [int(v) for v in info[m + 2: m + 6]]
+        self.slow, self.slow_launches = bool(info[m + 6]), int(info[m + 7])
+
+
+def region_planes_device(pix=None, mask=None, edge=None, launches=0, region0=None, rsize=None, force_slow=False, device=0):
+    """The region stage alone (rd_region_planes_device) on 2-D planes: stage 0 from (pix, mask, edge) with a budget of `launches` (0: as the frame path does), or
+    stage 1 from (region0, rsize).  Returns a RegionPlanes.  Needs a GPU."""
+    stage = 0 if region0 is None else 1
+    ins = [np.ascontiguousarray(a, dtype=np.int32) for a in ((pix, mask, edge) if stage == 0 else (region0, rsize))]
+    ih, iw = ins[0].shape
+    n = iw * ih
+    if any(a.size != n for a in ins):
+        raise ValueError("region_planes_device: planes of different sizes")
+    outs = [np.zeros(n, np.int32) for _ in range(5)]
+    info = np.zeros(REGION_INFO_INTS, np.int32)
+    z = [None] * 3
+    args = ([a.ctypes.data for a in ins] + [int(launches), None, None]) if stage == 0 else (z + [0] + [a.ctypes.data for a in ins])
+    if lib().rd_region_planes_device(int(device), stage, iw, ih, *args, int(bool(force_slow)), *[o.ctypes.data for o in outs], info.ctypes.data) != 0:
+        raise ValueError("rd_region_planes_device: invalid arguments")
+    return RegionPlanes((ih, iw), outs, info)

@@ -643,7 +643,7 @@ static void frame_regions(rd_detector *d, Slot *s, hipStream_t st, int nz, size_
   rdk::region_merge(st, s->region0, s->scratch2, (const int *)s->quant, s->mmbits, s->strongbits, iw, ih, s->rounds,
                     s->rsize, &marked, nz, zs);   // H2: the sizes start from the junction counts (evaluated by the first kernel)
   rdk::region_size(st, s->rsize, s->region0, N, d2scratch + N, marked, nz, zs);      // (also strips the rounds' marks from the labels)
-  rdk::despeckle2(st, s->region, s->region0, d2scratch, s->rsize, 16, iw, ih, 1, s->scratch2 + N + RD_REGION_STATUS_AT, nz, zs);   // (status words: they travel to the host with the round flags)
+  rdk::despeckle2(st, s->region, s->region0, d2scratch, s->rsize, RD_ABSORB_THRE, iw, ih, 1, s->scratch2 + N + RD_REGION_STATUS_AT, nz, zs);   // (status words: they travel to the host with the round flags)
 
   // region boundaries and their components (oclrect.c:340-342)
   rdk::label8_boundary(st, s->boundary, s->boundarysrc, s->region, iw, ih, s->table, s->claim, s->tlist, nz, zs, RD_BOUNDARY_FLATTEN);   // (also undoes the previous frame's vote-table entries)
@@ -669,7 +669,7 @@ static void redo_votes(rd_detector *d, Slot *s, hipStream_t st) {
 static void frame_absorb_slow(rd_detector *d, Slot *s) {
   if (!s->st_redo) s->st_redo = make_redo_stream();
   hipStream_t st = s->st_redo;
-  rdk::despeckle2_slow(st, s->region, s->region0, s->d2s, s->rsize, 16, d->iw, d->ih);
+  rdk::despeckle2_slow(st, s->region, s->region0, s->d2s, s->rsize, RD_ABSORB_THRE, d->iw, d->ih);
   rdk::label8_boundary(st, s->boundary, s->boundarysrc, s->region, d->iw, d->ih, s->table, s->claim, s->tlist, 1, 0, RD_BOUNDARY_FLATTEN);
   redo_votes(d, s, st);
   RD_HIP(hipStreamSynchronize(st));
@@ -973,18 +973,30 @@ static void sparse_flush(rd_detector *d, int si) {
 static void wait_event_outside_captures(rd_detector *d, hipEvent_t ev);
 static void slot_fetch(Slot *s, void *dst, const void *src, size_t bytes);
 
+// The ladder of a frame whose region merge was still changing in the last launch of its first budget: the region stages again with as many launches as it takes
+// (32 first - the frames that exceed a budget of 12-14 need 13-20 as a rule, and every launch after the settling one still costs a dispatch of the whole grid -
+// then 64, then the definition's limit of RD_REGION_MAX_LAUNCHES = 128: region_ladder_next).  still_after(budget) runs the stages with that budget and returns the
+// flag of the budget's last launch.  The one decision of the frame path (slot_finish_device) and of the stage's test tap (rd_region_planes_device).
+struct LadderEnd { int budget, settled; };      // the budget that was final; settled = 0: the frame keeps what RD_REGION_MAX_LAUNCHES launches made of it
+template <typename F> static LadderEnd region_ladder(F still_after) {
+  LadderEnd e = { 0, 0 };
+  for (int budget = rdk::region_ladder_next(RD_REGION_FIRST_BUDGET); budget && !e.settled; budget = rdk::region_ladder_next(budget)) {
+    e.budget = budget;
+    e.settled = still_after(budget) == 0;
+  }
+  return e;
+}
+
 // What remains to be done on the device for a finished slot, once per frame (on the polling thread or on the slot's worker): the two
 // rare repeats and the bookkeeping of the round budget.
 static void slot_finish_device(rd_detector *d, Slot *s) {
-  if (s->rounds <= 20 && s->h_ctr[32 + s->rounds - 1] != 0) {   // the region merge was still changing in its last launch: again with as many launches as it takes
-    // (32 first - the frames that exceed a budget of 12-14 need 13-20 as a rule, and every launch after the settling one still costs a
-    //  dispatch of the whole grid - then 64, then the definition's limit of RD_REGION_MAX_LAUNCHES = 128)
+  if (s->rounds <= RD_REGION_FIRST_BUDGET && s->h_ctr[32 + s->rounds - 1] != 0) {   // the region merge was still changing in its last launch: again with as many launches as it takes (region_ladder)
     // (on a stream of the slot's own: the slot's regular stream is one of the four that carry the groups, and the repeat would wait there behind a whole group of
     //  other frames; nothing but this frame's result depends on it - the frame is finished, ev_done has been waited for)
     static const bool redo_inline = RD_LAB_INT("RD_REDO_ON_MAIN_STREAM", 0) != 0;
     if (!s->st_redo && !redo_inline) s->st_redo = make_redo_stream();
     hipStream_t rst = redo_inline ? s->st : s->st_redo;
-    for (int budget = 32; budget <= RD_REGION_MAX_LAUNCHES; budget *= 2) {
+    const LadderEnd end = region_ladder([&](int budget) {
       s->rounds = budget;
       pthread_mutex_lock(&d->launch_mu);
       frame_regions(d, s, rst, 1, 0);
@@ -994,9 +1006,9 @@ static void slot_finish_device(rd_detector *d, Slot *s) {
       wait_event_outside_captures(d, s->ev_redo);
       int still = 0;
       slot_fetch(s, &still, s->scratch2 + d->N + budget - 1, sizeof(int));      // the flag of the budget's last launch
-      if (!still) break;
-      if (budget == RD_REGION_MAX_LAUNCHES) __atomic_add_fetch(&d->n_unsettled, 1, __ATOMIC_RELAXED);      // (the definition's limit: the frame keeps what that many launches made of it - counter 6)
-    }
+      return still;
+    });
+    if (!end.settled) __atomic_add_fetch(&d->n_unsettled, 1, __ATOMIC_RELAXED);      // (the definition's limit: the frame keeps what that many launches made of it - counter 6)
     __atomic_add_fetch(&d->n_redo_rounds, 1, __ATOMIC_RELAXED);
   }
   if (s->h_ctr[52] != 0 || (d->force_redo & 2)) {   // the absorption's fast path gave up on this frame: finish it the long way
@@ -1933,6 +1945,104 @@ int rd_polyline_planes_device(int device, const int32_t *mask, int iw, int ih, i
   RD_HIP(hipStreamDestroy(st));
   rdk::poly_scratch_destroy(ps);
   dfree(d_ls); dfree(d_ids); dfree(d_mask);
+  return 0;
+}
+
+// ---- test taps of the region stage (neither is on the frame path)
+void rd_region_limits(int iw, int ih, int32_t out[32]) { rdk::region_limits(iw, ih, out); }
+
+// an int plane (non-zero / positive = set) as the bit plane the region kernels read: ceil(iw / 64) words per row, bits beyond the row's end clear
+static void pack_bit_plane(unsigned long long *bits, const int32_t *plane, int iw, int ih, int positive_only) {
+  const int wpr = (iw + 63) / 64;
+  memset(bits, 0, ((size_t)wpr * ih + 8) * sizeof(*bits));
+  for (int y = 0; y < ih; y++)
+    for (int x = 0; x < iw; x++) {
+      const int v = plane[(size_t)y * iw + x];
+      if (positive_only ? v > 0 : v != 0) bits[(size_t)y * wpr + (x >> 6)] |= 1ull << (x & 63);
+    }
+}
+
+// frame_regions' twin on planes of the caller: stage 0 = region_merge, region_size, despeckle2, label8_boundary from the merge's inputs, with a budget of the caller's or
+// (launches = 0) the frame path's - RD_REGION_FIRST_BUDGET launches, then region_ladder -; stage 1 = despeckle2, label8_boundary from the absorption's inputs.  Either way
+// the slow absorption (frame_absorb_slow's two calls) where the status word asks for it or the caller forces it.  Once, on a stream, planes and scratch of its own.
+int rd_region_planes_device(int device, int stage, int iw, int ih, const int32_t *pix, const int32_t *mask, const int32_t *edge, int launches,
+                            const int32_t *region0_in, const int32_t *rsize_in, int force_slow,
+                            int32_t *region0_out, int32_t *rsize_out, int32_t *region_out, int32_t *boundarysrc_out, int32_t *boundary_out, int32_t info[RD_REGION_INFO_INTS]) {
+  if (!region0_out || !rsize_out || !region_out || !boundarysrc_out || !boundary_out || !info || (stage != 0 && stage != 1)) return -1;
+  if (iw < 16 || ih < 16 || (long long)iw * ih >= (1ll << 25)) return -1;      // (rd_detector_create's limits)
+  const size_t N = (size_t)iw * ih;
+  if (stage == 0) {
+    if (!pix || !mask || !edge || launches < 0 || (launches & 1) || launches == 1 || launches > RD_REGION_MAX_LAUNCHES) return -1;
+  } else {
+    if (!region0_in || !rsize_in) return -1;
+    for (size_t p = 0; p < N; p++)
+      if (region0_in[p] < 0 || (size_t)region0_in[p] >= N || rsize_in[p] < 0 || rsize_in[p] >= (1 << 26)) return -1;      // (labels index the size table; the tail's words hold sizes in 26 bits)
+  }
+  RD_HIP(hipSetDevice(device));
+  const int n = (int)N, nentry = n * 4 / 5;
+  const size_t nbits = (size_t)((iw + 63) / 64) * ih + 8;
+  int *d_pix = dnew<int>(N), *d_region0 = dnew<int>(N), *d_rsize = dnew<int>(N), *d_region = dnew<int>(N), *d_bsrc = dnew<int>(N), *d_boundary = dnew<int>(N);
+  int *d_scratch2 = dnew<int>(N * 3 + 256), *d_d2s = dnew<int>(RD_D2_SCRATCH_INTS(N)), *d_table = dnew<int>(N * 4), *d_claim = dnew<int>(N), *d_tlist = dnew<int>(N);
+  unsigned long long *d_mm = dnew<unsigned long long>(nbits), *d_sb = dnew<unsigned long long>(nbits);
+  int *flags = d_scratch2 + N, *status = flags + RD_REGION_STATUS_AT;
+  hipStream_t st = NULL;
+  RD_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  rdk::reduce_ls_init(st, d_table, d_claim, d_tlist, nentry);
+  RD_HIP(hipMemsetAsync(flags, 0, 256 * sizeof(int), st));
+  for (int i = 0; i < RD_REGION_INFO_INTS; i++) info[i] = 0;
+  int budget = 0, settled = 1;
+  if (stage == 0) {
+    unsigned long long *h_bits = (unsigned long long *)malloc(nbits * sizeof(*h_bits));
+    if (!h_bits) exitf(-1, "rd_region_planes_device: out of memory\n");
+    RD_HIP(hipMemcpyAsync(d_pix, pix, N * sizeof(int), hipMemcpyHostToDevice, st));
+    pack_bit_plane(h_bits, mask, iw, ih, 0);
+    RD_HIP(hipMemcpyAsync(d_mm, h_bits, nbits * sizeof(*h_bits), hipMemcpyHostToDevice, st));
+    RD_HIP(hipStreamSynchronize(st));      // (the one host buffer packs both planes)
+    pack_bit_plane(h_bits, edge, iw, ih, 1);
+    RD_HIP(hipMemcpyAsync(d_sb, h_bits, nbits * sizeof(*h_bits), hipMemcpyHostToDevice, st));
+    RD_HIP(hipStreamSynchronize(st));
+    free(h_bits);
+    auto still_after = [&](int b) {      // frame_regions with b launches of the merge; the flag of the last one
+      int marked = 0, still = 0;
+      rdk::region_merge(st, d_region0, d_scratch2, d_pix, d_mm, d_sb, iw, ih, b, d_rsize, &marked, 1, 0);
+      rdk::region_size(st, d_rsize, d_region0, n, d_d2s + N, marked, 1, 0);
+      rdk::despeckle2(st, d_region, d_region0, d_d2s, d_rsize, RD_ABSORB_THRE, iw, ih, 1, status, 1, 0);
+      rdk::label8_boundary(st, d_boundary, d_bsrc, d_region, iw, ih, d_table, d_claim, d_tlist, 1, 0, RD_BOUNDARY_FLATTEN);
+      rdrt::check_launch("rd_region_planes_device");
+      RD_HIP(hipMemcpyAsync(&still, flags + b - 1, sizeof(int), hipMemcpyDeviceToHost, st));
+      RD_HIP(hipStreamSynchronize(st));
+      return still;
+    };
+    budget = launches ? launches : RD_REGION_FIRST_BUDGET;
+    settled = still_after(budget) == 0;
+    if (!launches && !settled) { const LadderEnd e = region_ladder(still_after); budget = e.budget; settled = e.settled; }
+  } else {
+    RD_HIP(hipMemcpyAsync(d_region0, region0_in, N * sizeof(int), hipMemcpyHostToDevice, st));
+    RD_HIP(hipMemcpyAsync(d_rsize, rsize_in, N * sizeof(int), hipMemcpyHostToDevice, st));
+    rdk::despeckle2(st, d_region, d_region0, d_d2s, d_rsize, RD_ABSORB_THRE, iw, ih, 0, status, 1, 0);
+    rdk::label8_boundary(st, d_boundary, d_bsrc, d_region, iw, ih, d_table, d_claim, d_tlist, 1, 0, RD_BOUNDARY_FLATTEN);
+    rdrt::check_launch("rd_region_planes_device");
+  }
+  RD_HIP(hipMemcpyAsync(info, flags, (size_t)RD_REGION_MAX_LAUNCHES * sizeof(int), hipMemcpyDeviceToHost, st));
+  RD_HIP(hipMemcpyAsync(info + RD_REGION_MAX_LAUNCHES + 2, status, 4 * sizeof(int), hipMemcpyDeviceToHost, st));
+  RD_HIP(hipStreamSynchronize(st));
+  info[RD_REGION_MAX_LAUNCHES] = budget; info[RD_REGION_MAX_LAUNCHES + 1] = settled;
+  if (info[RD_REGION_MAX_LAUNCHES + 2] != 0 || force_slow) {      // as frame_absorb_slow
+    info[RD_REGION_MAX_LAUNCHES + 7] = rdk::despeckle2_slow(st, d_region, d_region0, d_d2s, d_rsize, RD_ABSORB_THRE, iw, ih);
+    rdk::label8_boundary(st, d_boundary, d_bsrc, d_region, iw, ih, d_table, d_claim, d_tlist, 1, 0, RD_BOUNDARY_FLATTEN);
+    rdrt::check_launch("rd_region_planes_device, slow absorption");
+    info[RD_REGION_MAX_LAUNCHES + 6] = 1;
+  }
+  if (!RD_BOUNDARY_FLATTEN) rdk::label8_flatten(st, d_boundary, n);      // (a tuning build leaves the components as a forest, as on the frame path: flattened where the plane is looked at)
+  RD_HIP(hipMemcpyAsync(region0_out, d_region0, N * sizeof(int), hipMemcpyDeviceToHost, st));
+  RD_HIP(hipMemcpyAsync(rsize_out, d_rsize, N * sizeof(int), hipMemcpyDeviceToHost, st));
+  RD_HIP(hipMemcpyAsync(region_out, d_region, N * sizeof(int), hipMemcpyDeviceToHost, st));
+  RD_HIP(hipMemcpyAsync(boundarysrc_out, d_bsrc, N * sizeof(int), hipMemcpyDeviceToHost, st));
+  RD_HIP(hipMemcpyAsync(boundary_out, d_boundary, N * sizeof(int), hipMemcpyDeviceToHost, st));
+  RD_HIP(hipStreamSynchronize(st));
+  RD_HIP(hipStreamDestroy(st));
+  dfree(d_sb); dfree(d_mm); dfree(d_tlist); dfree(d_claim); dfree(d_table); dfree(d_d2s); dfree(d_scratch2);
+  dfree(d_boundary); dfree(d_bsrc); dfree(d_region); dfree(d_rsize); dfree(d_region0); dfree(d_pix);
   return 0;
 }
 

@@ -967,7 +967,10 @@ __global__ __launch_bounds__(64 * RR_TY) void k_region_round(int *X, int *Y, con
       if (d >= 0 && d < RR_TY * RR_PX * iw) {        // (below 2^24 for every frame this library accepts rows of: exact in single precision up to the correction)
         int row = (int)((float)d * inv_iw), col = d - row * iw;
         if (col < 0) { row--; col += iw; } else if (col >= iw) { row++; col -= iw; }
-        inside = col < 64 && row < RR_TY * RR_PX;
+        // (col counts from the tile's first column and wraps: a parent LEFT of the tile, a row further down, lands on col = iw + its distance - in the frame's last, partial
+        //  tile column that is below 64 for parents in the frame's first 64 - iw % 64 columns, on a cell beyond the frame's right edge whose proposal nobody collects: the cell
+        //  must be a pixel of the frame.  Frames up to 64 + 10 wide reach it - tests/regioncases.py, cascade_n33_h70)
+        inside = col < 64 && row < RR_TY * RR_PX && bx * 64 + col < iw;
         cell = row * 64 + col;
       }
       if (todo[k] && inside) atomicMin(&tmin[cell], g[k]);
@@ -1309,6 +1312,7 @@ __global__ __launch_bounds__(256) void k_despeckle2_active(int *__restrict__ nxt
 #define AB_NT 512
 #endif
 #define AB_R 4                              // small-region cells per thread (more in a tile: its small-region pixels go to the tail)
+#define AB_ROUNDS (AB_HK + 8)               // rounds of the tile kernel at most (region_limits reports it)
 #define AB_INEXACT 0x40000000u
 typedef unsigned long long ab_word;         // a cell: (size of its label | AB_INEXACT) << 32 | label  (one 64-bit LDS word: readers always see a consistent pair)
 __device__ __forceinline__ ab_word ab_pack(int lab, unsigned t) { return ((ab_word)t << 32) | (unsigned)lab; }
@@ -1401,8 +1405,8 @@ __global__ __launch_bounds__(AB_NT) void k_absorb_tile(int *__restrict__ out, in
       t = ab_t(w4) & ~AB_INEXACT; if (t > rs[k]) { rs[k] = t; rl[k] = ab_lab(w4); }
     }
     __syncthreads();
-    // rounds: a cell whose four predecessors are exact takes its final value and becomes exact; until nothing moves any more, AB_HK + 8 rounds at most
-    for (int round = 0; round < AB_HK + 8; round++) {      // (longer chains - the runs along the frame's outermost rows and columns - are the tail's: it settles them in log steps, here a pixel per round)
+    // rounds: a cell whose four predecessors are exact takes its final value and becomes exact; until nothing moves any more, AB_ROUNDS rounds at most
+    for (int round = 0; round < AB_ROUNDS; round++) {      // (longer chains - the runs along the frame's outermost rows and columns - are the tail's: it settles them in log steps, here a pixel per round)
       bool progress = false;
 #pragma unroll
       for (int k = 0; k < AB_R; k++) {
@@ -1641,19 +1645,25 @@ __device__ __forceinline__ void at_body(ab_word *W, int *__restrict__ out, const
   if (tid == 0) { status[4] = (int)(t1 - t0); status[5] = (int)(t2 - t1); status[6] = (int)(t3 - t2); status[7] = (int)(wall_clock64() - t3); }
 }
 
+// the variants k_absorb_tail picks from - the smallest with EPT * AT_NT >= n; the last one covers AT_CAP (region_limits reports the same list)
+#define AT_NEPT 7
+static constexpr int kAtEpt[AT_NEPT] = { 2, 3, 4, 5, 6, 8, 16 };
+static_assert(kAtEpt[AT_NEPT - 1] * AT_NT > AT_CAP, "the last variant covers every count the tail accepts");
 __global__ __launch_bounds__(AT_NT) void k_absorb_tail(int *__restrict__ out, const int *__restrict__ list, int reccap, const int *__restrict__ count, const int *__restrict__ size, int nsteps, int *status, size_t zs) {
   RD_ZSHIFT(zs, out, list, count, size, status);
   extern __shared__ __attribute__((aligned(16))) ab_word at_lds[];
   const int n = *count;
   if (threadIdx.x == 0) { status[1] = n; status[0] = n > reccap ? 1 : 0; status[2] = 0; }
   if (n == 0 || n > reccap) return;
-  if (n <= 2 * AT_NT) at_body<2>(at_lds, out, list, n, size, nsteps, status);
-  else if (n <= 3 * AT_NT) at_body<3>(at_lds, out, list, n, size, nsteps, status);
-  else if (n <= 4 * AT_NT) at_body<4>(at_lds, out, list, n, size, nsteps, status);
-  else if (n <= 5 * AT_NT) at_body<5>(at_lds, out, list, n, size, nsteps, status);
-  else if (n <= 6 * AT_NT) at_body<6>(at_lds, out, list, n, size, nsteps, status);
-  else if (n <= 8 * AT_NT) at_body<8>(at_lds, out, list, n, size, nsteps, status);
-  else at_body<16>(at_lds, out, list, n, size, nsteps, status);
+  // (one branch per entry of kAtEpt, written out: walking the list with a recursive template gave the kernel another register allocation)
+  static_assert(AT_NEPT == 7, "one branch per variant");
+  if (n <= kAtEpt[0] * AT_NT) at_body<kAtEpt[0]>(at_lds, out, list, n, size, nsteps, status);
+  else if (n <= kAtEpt[1] * AT_NT) at_body<kAtEpt[1]>(at_lds, out, list, n, size, nsteps, status);
+  else if (n <= kAtEpt[2] * AT_NT) at_body<kAtEpt[2]>(at_lds, out, list, n, size, nsteps, status);
+  else if (n <= kAtEpt[3] * AT_NT) at_body<kAtEpt[3]>(at_lds, out, list, n, size, nsteps, status);
+  else if (n <= kAtEpt[4] * AT_NT) at_body<kAtEpt[4]>(at_lds, out, list, n, size, nsteps, status);
+  else if (n <= kAtEpt[5] * AT_NT) at_body<kAtEpt[5]>(at_lds, out, list, n, size, nsteps, status);
+  else at_body<kAtEpt[6]>(at_lds, out, list, n, size, nsteps, status);
 }
 
 // (rc:373-390, the region-boundary marks, are computed inside the labelling kernel: rd_k_label.hip, k_label_tile<true>)
@@ -2051,10 +2061,13 @@ void region_size(hipStream_t s, int *out, int *label, int n, int *zero_me, int m
 // counter) zeroed by the caller when count_is_zero; out must not alias in.  status (device, 3 ints): [0] != 0 <=> the two launches
 // could not finish the frame (more than AT_CAP undecided pixels, or the tail did not settle): `out` then still holds undecided
 // words (negative) and the caller runs despeckle2_slow(); [1] undecided pixels left by the tile kernel, [2] sweeps of the tail.
+// records of undecided pixels the fast path has room for in a frame of n pixels: the 3N ints of the slow path's work lists, and no more than the tail holds
+static inline int absorb_reccap(size_t n) { return 3 * n / AB_REC < (size_t)AT_CAP ? (int)(3 * n / AB_REC) : AT_CAP; }
+
 void despeckle2(hipStream_t s, int *out, const int *in, int *scratch, const int *size, int thre, int iw, int ih, int count_is_zero, int *status, int nz, size_t zs) {
   const int n = iw * ih;
   int *count = scratch + (size_t)n, *list = count + 16 + (size_t)n;       // (the list: the 3N ints of the slow path's work lists)
-  const int reccap = (int)(3 * (size_t)n / AB_REC) < AT_CAP ? (int)(3 * (size_t)n / AB_REC) : AT_CAP;
+  const int reccap = absorb_reccap((size_t)n);
   int nsteps = 1;
   while ((1 << nsteps) < (iw > ih ? iw : ih)) nsteps++;
   if (!count_is_zero) { if (nz != 1) { fprintf(stderr, "despeckle2: a group launch needs count_is_zero\n"); abort(); } (void)hipMemsetAsync(count, 0, sizeof(int), s); }
@@ -2068,7 +2081,7 @@ void despeckle2(hipStream_t s, int *out, const int *in, int *scratch, const int 
 // changes nothing (the fixed point of the rounds is the serial result; chains of dependent pixels can be thousands long on frames
 // that consist of small regions only, so this takes as many launches as it takes).  Synchronises `s` every few launches: for the
 // frames the fast path gives up on, outside captured graphs.  Same scratch as despeckle2().
-void despeckle2_slow(hipStream_t s, int *out, const int *in, int *scratch, const int *size, int thre, int iw, int ih) {
+int despeckle2_slow(hipStream_t s, int *out, const int *in, int *scratch, const int *size, int thre, int iw, int ih) {
   const int n = iw * ih;
   int *tmp = scratch, *count = scratch + (size_t)n, *stamp = count + 16, *lists = stamp + (size_t)n;
   (void)hipMemsetAsync(count, 0, 16 * sizeof(int), s);
@@ -2089,10 +2102,31 @@ void despeckle2_slow(hipStream_t s, int *out, const int *in, int *scratch, const
     (void)hipStreamSynchronize(s);
     if (pending == 0) break;
     // (a dependency chain moves at least one pixel right or one row down per link: iw + 2 * ih bounds its length, and every launch settles two links)
-    if (r > iw + 2 * ih + 16) { fprintf(stderr, "despeckle2_slow: no fixed point after %d launches (internal error)\n", r); abort(); }
+    if (r > despeckle2_slow_bound(iw, ih)) { fprintf(stderr, "despeckle2_slow: no fixed point after %d launches (internal error)\n", r); abort(); }
   }
   // (launches with an odd number write `tmp`, and the last one had: the result moves to `out`)
   if (cur != out) (void)hipMemcpyAsync(out, cur, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, s);
+  return r;
+}
+
+// [0] first budget, [1..4] the ladder's budgets (0: no more), [5] most launches of the merge, [6] AT_CAP, [7] AT_SWEEPS, [8] AT_NT, [9] AB_HK, [10] AB_R * AB_NT, [11] x [12] the merge's
+// tile, [13] x [14] the absorption's, [15] the absorption threshold, [16] despeckle2_slow's launch bound and [17] despeckle2's reccap at iw x ih, [18] rounds of k_absorb_tile,
+// [19..25] the EPT variants of k_absorb_tail, [26] bits of a size in the tail's words, [27..31] 0
+void region_limits(int iw, int ih, int out[32]) {
+  for (int i = 0; i < 32; i++) out[i] = 0;
+  out[0] = RD_REGION_FIRST_BUDGET;
+  for (int k = 1, b = region_ladder_next(RD_REGION_FIRST_BUDGET); k <= 4 && b; k++, b = region_ladder_next(b)) out[k] = b;
+  out[5] = RD_REGION_MAX_LAUNCHES; out[6] = AT_CAP; out[7] = AT_SWEEPS; out[8] = AT_NT; out[9] = AB_HK; out[10] = AB_R * AB_NT;
+  out[11] = 64; out[12] = RR_TY * RR_PX; out[13] = AB_TW; out[14] = AB_TH; out[15] = RD_ABSORB_THRE;
+  if (iw > 0 && ih > 0) {
+    out[16] = despeckle2_slow_bound(iw, ih);
+    out[17] = absorb_reccap((size_t)iw * ih);
+  }
+  out[18] = AB_ROUNDS;
+  for (int k = 0; k < AT_NEPT; k++) out[19 + k] = kAtEpt[k];
+  static_assert(AT_NEPT <= 7, "out[19..25]");
+  out[26] = 26;
+  static_assert((AT_XMASK >> 26) == 0 && (AT_XMASK >> 25) == 1, "AT_XMASK is 26 bits wide");
 }
 
 // table: nentry*5 ints, claim: nentry ints, tlist: nentry+1 ints; all three are set up once by reduce_ls_init and kept

@@ -105,7 +105,7 @@ void despeckle(hipStream_t s, uint32_t *out, const uint32_t *in, const float *ed
 void merge_mask(hipStream_t s, unsigned long long *out, const unsigned long long *bits, int iw, int ih, int nz = 1, size_t zs = 0);   // out: bit plane, ceil(iw / 64) words per row
 // oclrect.cl:289-334 with the work-items of a launch concurrent (rd_k_rect.hip: k_region_init = the links and launch 0, k_region_round = the others).
 // mask / edge: the merge mask and the strong mask as bit planes.
-// launches: even, 2..64 (launches after one that changed nothing return at once; flag r of scratch[N + r] = launch r changed something);
+// launches: even, 2..RD_REGION_MAX_LAUNCHES (launches after one that changed nothing return at once; flag r of scratch[N + r] = launch r changed something);
 // size_out (optional) <- the junction counts of the strong mask (what the reference's size plane holds when the counting starts: quirk H2), for region_size;
 // scratch: 3N + 256 ints; *marked <- 1: `label` is left as label << 3 | mark words, which region_size(…, marked) turns into plain labels
 void region_merge(hipStream_t s, int *label, int *scratch, const int *pix, const unsigned long long *mask, const unsigned long long *edge, int iw, int ih, int launches,
@@ -120,7 +120,16 @@ void region_size(hipStream_t s, int *out, int *label, int n, int *zero_me, int m
 // absorption of small regions (oclrect.cl:348-371) exactly as the reference's serial raster order gives it.  out != in; scratch: RD_D2_SCRATCH_INTS(N) ints
 // (scratch[N] = 0 already if count_is_zero); status: 3 device ints, [0] != 0 <=> not finished (out holds negative words): run despeckle2_slow()
 void despeckle2(hipStream_t s, int *out, const int *in, int *scratch, const int *size, int thre, int iw, int ih, int count_is_zero, int *status, int nz = 1, size_t zs = 0);
-void despeckle2_slow(hipStream_t s, int *out, const int *in, int *scratch, const int *size, int thre, int iw, int ih);   // the same result for any input; synchronises s (not for captured streams)
+int despeckle2_slow(hipStream_t s, int *out, const int *in, int *scratch, const int *size, int thre, int iw, int ih);   // the same result for any input; synchronises s (not for captured streams); returns its launches of the rounds
+// launches of the rounds after which despeckle2_slow() calls a frame without a fixed point an internal error (a dependency chain moves at least one pixel right or
+// one row down per link: iw + 2 * ih bounds its length, and every launch settles two links)
+static inline int despeckle2_slow_bound(int iw, int ih) { return iw + 2 * ih + 16; }
+#define RD_REGION_FIRST_BUDGET 20      // the largest budget a frame is launched with (rd_api.hip: kRoundBudgets); a frame still changing in its last launch climbs the ladder (region_ladder)
+// the budget after `budget` on that ladder: 32, then doubled up to the definition's limit; 0: there is none
+static inline int region_ladder_next(int budget) { const int b = budget < 32 ? 32 : budget * 2; return b <= RD_REGION_MAX_LAUNCHES ? b : 0; }
+#define RD_ABSORB_THRE 16              // regions of at most this many pixels (junction counts included: quirk H2) are absorbed (oclrect.c:337)
+// the constants the crafted cases of the region stage are built from (rd_region_limits; the header documents the order)
+void region_limits(int iw, int ih, int out[32]);
 struct PolyScratch;
 struct PolyFrame;      // rd_poly_scratch.h: per-frame descriptor of the sparse stages; launches cover nb <= RD_MAXB frames (frame = blockIdx.z), descriptors in HOST memory
 void reduce_ls_init(hipStream_t s, int *table, int *claim, int *tlist, int nentry);   // once per allocation
