@@ -48,10 +48,7 @@ void rd_annot_limits(int32_t out[4]) {
 }
 
 void rd_annot_yuv(uint8_t b, uint8_t g, uint8_t r, uint8_t yuv[3]) {
-  const int B = b, G = g, R = r;
-  yuv[0] = (uint8_t)(((66 * R + 129 * G + 25 * B + 128) >> 8) + 16);
-  yuv[1] = (uint8_t)(((-38 * R - 74 * G + 112 * B + 128) >> 8) + 128);
-  yuv[2] = (uint8_t)(((112 * R - 94 * G - 18 * B + 128) >> 8) + 128);
+  yuv[0] = (uint8_t)rdpix::bgr_y(b, g, r); yuv[1] = (uint8_t)rdpix::bgr_u(b, g, r); yuv[2] = (uint8_t)rdpix::bgr_v(b, g, r);
 }
 
 int rd_annot_covers(const rd_annot_prim *p, int x, int y) {
@@ -155,24 +152,24 @@ long rd_annotator_enqueue(rd_annotator *a, int format, const void *const planes[
     rdk::AnnotRec *r = &h_recs[k];
     rd_annot_line_setup(&r->L, p->x0, p->y0, p->x1, p->y1, p->thickness);
     uint8_t c[3] = { p->b, p->g, p->r };
-    if (format == RD_PIX_RGB || format == RD_PIX_RGBA) { c[0] = p->r; c[2] = p->b; }
-    else if (format >= RD_PIX_NV12) rd_annot_yuv(p->b, p->g, p->r, c);
+    if (rdpix::rb_swapped(format)) { c[0] = p->r; c[2] = p->b; }
+    else if (rdpix::is_yuv(format)) rd_annot_yuv(p->b, p->g, p->r, c);
     r->col = c[0] | (c[1] << 8) | ((uint32_t)c[2] << 16);
     r->pad = 0;
   }
   const bool inplace = out_planes == NULL, to_pinned = !inplace && out_kind == RD_FRAME_HOST_PINNED;
   if (!(inplace && n == 0 && !(flags & RD_ANNOT_CLEAR))) {      // (that job has nothing to write)
-    Planes src = planes_at(planes, pitches, L);      // a device frame: read where it lies
+    PixFrame src = planes_at(planes, pitches, L);      // a device frame: read where it lies
     if (on_device != RD_FRAME_DEVICE) {              // through the annotator's own buffer, one plane after the other
       a->frame.grow(g->st, L.bytes);
       src = a->frame.packed(L);
       bring(g->st, who, L, src, planes, pitches, on_device);
     }
-    Planes dst = src;      // in place
+    PixFrame dst = src;      // in place
     if (to_pinned) { a->oframe.grow(g->st, L.bytes); dst = a->oframe.packed(L); }
     else if (!inplace) dst = planes_at(out_planes, out_pitches, L);
     if (n > 0) RD_HIP(hipMemcpyAsync(d_recs, h_recs, (size_t)n * sizeof(rdk::AnnotRec), hipMemcpyHostToDevice, g->st));
-    rdk::annotate(g->st, format, dst.p, dst.pitch, src.p, src.pitch, iw, ih, d_recs, n, flags & RD_ANNOT_CLEAR);
+    rdk::annotate(g->st, format, dst, src, d_recs, n, flags & RD_ANNOT_CLEAR);
     rdrt::check_launch("annotated frame");
     if (to_pinned) send(g->st, L, out_planes, out_pitches, dst);
   }

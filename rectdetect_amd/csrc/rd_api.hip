@@ -1495,7 +1495,7 @@ long rd_detector_enqueue_planes(rd_detector *d, int format, const void *const pl
   // argument errors: -1, nothing enqueued
   if (format < RD_PIX_BGR || format > RD_PIX_I420 || !planes || !pitches) return -1;
   if (on_device != RD_FRAME_HOST && on_device != RD_FRAME_DEVICE && on_device != RD_FRAME_HOST_PINNED) return -1;
-  if (format >= RD_PIX_NV12 && ((d->iw | d->ih) & 1)) return -1;
+  if (rdpix::is_yuv(format) && ((d->iw | d->ih) & 1)) return -1;
   const PixLayout L = pix_layout(format, d->iw, d->ih);
   for (int k = 0; k < L.np; k++) if (!planes[k] || pitches[k] < L.row[k]) return -1;
   if (format == RD_PIX_BGR) return rd_detector_enqueue(d, planes[0], pitches[0], on_device);

@@ -4,10 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "rd_comp_host.h"
+#include "rd_pix.h"
 
 namespace rdk {
-// n items composited IN PLACE into one iw x ih frame in format fmt (RD_PIX_*), one launch of ntiles one-wave blocks: tiles holds the pairs tx, ty of the tiles the
+// n items composited IN PLACE into one frame in format fmt (RD_PIX_*), one launch of ntiles one-wave blocks: tiles holds the pairs tx, ty of the tiles the
 // valid items' boxes reach (rd_comp_tiles_of), recs, tiles and patches are device memory; patches: images of pw x ph BGR pixels (may be NULL when no item pastes).
-void composite(hipStream_t s, int fmt, uint8_t *const planes[3], const int pitch[3], int iw, int ih, const rd_comp_rec *recs, int n, const int32_t *tiles, int ntiles,
-               const uint8_t *patches, int pw, int ph);
+void composite(hipStream_t s, int fmt, const rdpix::PixFrame &frame, const rd_comp_rec *recs, int n, const int32_t *tiles, int ntiles, const uint8_t *patches, int pw, int ph);
 }  // namespace rdk

@@ -122,7 +122,7 @@ long rd_compositor_enqueue(rd_compositor *c, int format, const void *const plane
   }
   const bool inplace = out_planes == NULL, to_pinned = !inplace && out_kind == RD_FRAME_HOST_PINNED;
   if (!(inplace && ntiles == 0)) {      // (that job has nothing to write)
-    Planes dst = planes_at(planes, pitches, L);      // in place
+    PixFrame dst = planes_at(planes, pitches, L);      // in place
     if (to_pinned) { c->oframe.grow(g->st, L.bytes); dst = c->oframe.packed(L); }
     else if (!inplace) dst = planes_at(out_planes, out_pitches, L);
     if (!inplace) bring(g->st, who, L, dst, planes, pitches, on_device);      // the source's pixels straight to where the job runs
@@ -141,7 +141,7 @@ long rd_compositor_enqueue(rd_compositor *c, int format, const void *const plane
         }
       }
       RD_HIP(hipMemcpyAsync(j->d_blk, j->h_blk, recs_bytes + (size_t)ntiles * 2 * sizeof(int32_t), hipMemcpyHostToDevice, g->st));
-      rdk::composite(g->st, format, dst.p, dst.pitch, iw, ih, (const rd_comp_rec *)j->d_blk, n, (const int32_t *)(j->d_blk + recs_bytes), ntiles, dpatches, c->pw, c->ph);
+      rdk::composite(g->st, format, dst, (const rd_comp_rec *)j->d_blk, n, (const int32_t *)(j->d_blk + recs_bytes), ntiles, dpatches, c->pw, c->ph);
       rdrt::check_launch("composited quads");
     }
     if (to_pinned) send(g->st, L, out_planes, out_pitches, dst);

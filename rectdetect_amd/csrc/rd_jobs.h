@@ -4,7 +4,7 @@
 // nothing here knows a kernel, a record or what a job's items are.  No graphs, no threads, no environment switches.
 #pragma once
 #include "rd_internal.h"
-#include "rectdetect_hip.h"
+#include "rd_pix.h"
 #include <stdlib.h>
 #include <string.h>
 
@@ -13,14 +13,13 @@ namespace rdjob {
 
 // the planes a format uses, their row bytes and rows; and the layout of a frame packed into a buffer of the library's own (row strides rounded up to 4 bytes, so
 // that kernels read them a dword per lane; every format then still fits 4 bytes per pixel)
-struct PixLayout { int np, row[3], rows[3], pitch[3]; size_t off[3], bytes; };
+struct PixLayout { int iw, ih, np, row[3], rows[3], pitch[3]; size_t off[3], bytes; };
 inline PixLayout pix_layout(int fmt, int iw, int ih) {
   PixLayout L;
   memset(&L, 0, sizeof(L));
-  const int bpp = fmt == RD_PIX_BGR || fmt == RD_PIX_RGB ? 3 : 4;
-  if (fmt <= RD_PIX_RGBA) { L.np = 1; L.row[0] = iw * bpp; L.rows[0] = ih; }
-  else if (fmt == RD_PIX_NV12) { L.np = 2; L.row[0] = L.row[1] = iw; L.rows[0] = ih; L.rows[1] = ih / 2; }
-  else { L.np = 3; L.row[0] = iw; L.rows[0] = ih; L.row[1] = L.row[2] = iw / 2; L.rows[1] = L.rows[2] = ih / 2; }
+  L.iw = iw; L.ih = ih; L.np = rdpix::planes(fmt);
+  L.row[0] = iw * rdpix::bpp(fmt); L.rows[0] = ih;
+  for (int k = 1; k < L.np; k++) { L.row[k] = L.np == 2 ? iw : iw / 2; L.rows[k] = ih / 2; }      // 4:2:0 chroma: U, V interleaved in one plane, or a plane each
   for (int k = 0; k < L.np; k++) { L.pitch[k] = (L.row[k] + 3) & ~3; L.off[k] = L.bytes; L.bytes += (size_t)L.pitch[k] * L.rows[k]; }
   return L;
 }
@@ -35,11 +34,11 @@ inline hipMemoryType memory_type(const void *p) {
 // is p what a caller that says `kind` (RD_FRAME_DEVICE or RD_FRAME_HOST_PINNED) must hand over?
 inline bool is_kind(const void *p, int kind) { return memory_type(p) == (kind == RD_FRAME_DEVICE ? hipMemoryTypeDevice : hipMemoryTypeHost); }
 
-// a frame where a job reads or writes it: device planes and their row strides
-struct Planes { uint8_t *p[3]; int pitch[3]; };
-inline Planes planes_at(const void *const planes[3], const int pitches[3], const PixLayout &L) {      // where the caller's lie
-  Planes f = { { NULL, NULL, NULL }, { 0, 0, 0 } };
-  for (int k = 0; k < L.np; k++) { f.p[k] = (uint8_t *)planes[k]; f.pitch[k] = pitches[k]; }
+// a frame where a job reads or writes it (device planes): where the caller's lie
+using rdpix::PixFrame;
+inline PixFrame planes_at(const void *const planes[3], const int pitches[3], const PixLayout &L) {
+  PixFrame f = { { NULL, NULL, NULL }, { 0, 0, 0 }, L.iw, L.ih };
+  for (int k = 0; k < L.np; k++) { f.pl[k] = (uint8_t *)planes[k]; f.pitch[k] = pitches[k]; }
   return f;
 }
 
@@ -54,9 +53,9 @@ struct DevBuf {
     bytes = want;
   }
   void release() { if (p) RD_HIP(hipFree(p)); p = NULL; bytes = 0; }
-  Planes packed(const PixLayout &L) const {      // a frame packed into it
-    Planes f = { { NULL, NULL, NULL }, { 0, 0, 0 } };
-    for (int k = 0; k < L.np; k++) { f.p[k] = p + L.off[k]; f.pitch[k] = L.pitch[k]; }
+  PixFrame packed(const PixLayout &L) const {      // a frame packed into it
+    PixFrame f = { { NULL, NULL, NULL }, { 0, 0, 0 }, L.iw, L.ih };
+    for (int k = 0; k < L.np; k++) { f.pl[k] = p + L.off[k]; f.pitch[k] = L.pitch[k]; }
     return f;
   }
 };
@@ -129,7 +128,7 @@ inline int ring_wait(Ring *r) {
 inline bool frame_ok(int format, const void *const planes[3], const int pitches[3], int iw, int ih, int on_device, PixLayout *L) {
   if (format < RD_PIX_BGR || format > RD_PIX_I420 || !planes || !pitches || iw < 1 || ih < 1 || iw > 65536 || ih > 65536) return false;
   if (on_device != RD_FRAME_HOST && on_device != RD_FRAME_DEVICE && on_device != RD_FRAME_HOST_PINNED) return false;
-  if (format >= RD_PIX_NV12 && ((iw | ih) & 1)) return false;
+  if (rdpix::is_yuv(format) && ((iw | ih) & 1)) return false;
   *L = pix_layout(format, iw, ih);
   for (int k = 0; k < L->np; k++) if (!planes[k] || pitches[k] < L->row[k]) return false;
   return true;
@@ -149,19 +148,19 @@ inline bool dest_memory_ok(const PixLayout &L, void *const out_planes[3], int ou
 
 // ---- a frame's moves, row bytes only: pitch padding is neither read nor written
 // the caller's frame - host, pinned or device memory - to device planes on st; who: the entry point, for the fatal message about planes that are not pinned
-inline void bring(hipStream_t st, const char *who, const PixLayout &L, const Planes &to, const void *const planes[3], const int pitches[3], int on_device) {
+inline void bring(hipStream_t st, const char *who, const PixLayout &L, const PixFrame &to, const void *const planes[3], const int pitches[3], int on_device) {
   if (on_device == RD_FRAME_HOST_PINNED)
     for (int k = 0; k < L.np; k++)
       if (memory_type(planes[k]) != hipMemoryTypeHost)
         exitf(-1, "%s: RD_FRAME_HOST_PINNED needs pinned host memory (rd_host_alloc, allocatePinnedMemory, hipHostMalloc, hipHostRegister); plane %d at %p is not\n", who, k, planes[k]);
   for (int k = 0; k < L.np; k++)
-    RD_HIP(hipMemcpy2DAsync(to.p[k], to.pitch[k], planes[k], pitches[k], L.row[k], L.rows[k], on_device == RD_FRAME_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    RD_HIP(hipMemcpy2DAsync(to.pl[k], to.pitch[k], planes[k], pitches[k], L.row[k], L.rows[k], on_device == RD_FRAME_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
   if (on_device == RD_FRAME_HOST) RD_HIP(hipStreamSynchronize(st));      // (pageable memory: the caller may reuse the buffer when this call returns)
 }
 // device planes to the caller's pinned planes on st: the caller's pitch padding stays as it is
-inline void send(hipStream_t st, const PixLayout &L, void *const out_planes[3], const int out_pitches[3], const Planes &from) {
+inline void send(hipStream_t st, const PixLayout &L, void *const out_planes[3], const int out_pitches[3], const PixFrame &from) {
   for (int k = 0; k < L.np; k++)
-    RD_HIP(hipMemcpy2DAsync(out_planes[k], out_pitches[k], from.p[k], from.pitch[k], L.row[k], L.rows[k], hipMemcpyDeviceToHost, st));
+    RD_HIP(hipMemcpy2DAsync(out_planes[k], out_pitches[k], from.pl[k], from.pitch[k], L.row[k], L.rows[k], hipMemcpyDeviceToHost, st));
 }
 
 }  // namespace rdjob

@@ -18,10 +18,12 @@
 #include <stdlib.h>
 #include "rd_device.h"
 #include "rd_kernels.h"
-#include "rectdetect_hip.h"
 
 namespace {
 
+using namespace rdpix;
+
+// a job's two frames, of one size, as one kernel argument
 struct AnnotFrame { uint8_t *dst[3]; const uint8_t *src[3]; int dpitch[3], spitch[3]; int iw, ih; };
 
 constexpr int TW = rdk::ANNOT_TILE_W, TH = rdk::ANNOT_TILE_H, PXW = 4, PXH = 2, NT = (TW / PXW) * (TH / PXH);
@@ -81,7 +83,7 @@ template <int BPP, int NC, int NEL> __device__ __forceinline__ void put_row(uint
 template <int FMT> __global__ __launch_bounds__(NT) void k_annotate(AnnotFrame F, const rdk::AnnotRec *recs, int n, int inplace, int clear) {
   __shared__ rdk::AnnotRec s_list[NT];
   __shared__ int s_cnt[NT / 64];
-  constexpr bool YUV = FMT >= RD_PIX_NV12;
+  constexpr bool YUV = is_yuv(FMT);
   const int tid = threadIdx.y * (TW / PXW) + threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH, tx1 = min(tx0 + TW, F.iw) - 1, ty1 = min(ty0 + TH, F.ih) - 1;      // the tile, inside the frame
   const int x0 = tx0 + threadIdx.x * PXW, y0 = ty0 + threadIdx.y * PXH;      // this thread's pixels: x0 .. x0 + 3, y0 .. y0 + 1
@@ -130,7 +132,7 @@ template <int FMT> __global__ __launch_bounds__(NT) void k_annotate(AnnotFrame F
   if (npx <= 0) return;
   const bool ip = inplace != 0, cl = clear != 0;
   if (!YUV) {
-    constexpr int BPP = (FMT == RD_PIX_BGR || FMT == RD_PIX_RGB) ? 3 : 4;
+    constexpr int BPP = bpp(FMT);
 #pragma unroll
     for (int j = 0; j < PXH; j++)
       if (y0 + j < F.ih)
@@ -154,22 +156,15 @@ template <int FMT> __global__ __launch_bounds__(NT) void k_annotate(AnnotFrame F
 
 namespace rdk {
 
-void annotate(hipStream_t s, int fmt, uint8_t *const dst[3], const int dpitch[3], const uint8_t *const src[3], const int spitch[3], int iw, int ih, const AnnotRec *recs, int n, int clear) {
-  if (iw <= 0 || ih <= 0) return;
-  const int inplace = dst[0] == src[0];
+void annotate(hipStream_t s, int fmt, const PixFrame &dst, const PixFrame &src, const AnnotRec *recs, int n, int clear) {
+  if (dst.iw <= 0 || dst.ih <= 0) return;
+  const int inplace = dst.pl[0] == src.pl[0];
   if (inplace && !clear && n <= 0) return;      // nothing to write
-  AnnotFrame F;
-  for (int k = 0; k < 3; k++) { F.dst[k] = dst[k]; F.src[k] = src[k]; F.dpitch[k] = dpitch[k]; F.spitch[k] = spitch[k]; }
-  F.iw = iw; F.ih = ih;
-  const dim3 block(TW / PXW, TH / PXH), grid((iw + TW - 1) / TW, (ih + TH - 1) / TH);
-  switch (fmt) {
-    case RD_PIX_BGR: hipLaunchKernelGGL(k_annotate<RD_PIX_BGR>, grid, block, 0, s, F, recs, n, inplace, clear); break;
-    case RD_PIX_RGB: hipLaunchKernelGGL(k_annotate<RD_PIX_RGB>, grid, block, 0, s, F, recs, n, inplace, clear); break;
-    case RD_PIX_BGRA: hipLaunchKernelGGL(k_annotate<RD_PIX_BGRA>, grid, block, 0, s, F, recs, n, inplace, clear); break;
-    case RD_PIX_RGBA: hipLaunchKernelGGL(k_annotate<RD_PIX_RGBA>, grid, block, 0, s, F, recs, n, inplace, clear); break;
-    case RD_PIX_NV12: hipLaunchKernelGGL(k_annotate<RD_PIX_NV12>, grid, block, 0, s, F, recs, n, inplace, clear); break;
-    case RD_PIX_I420: hipLaunchKernelGGL(k_annotate<RD_PIX_I420>, grid, block, 0, s, F, recs, n, inplace, clear); break;
-    default: fprintf(stderr, "rdk::annotate: unknown pixel format %d\n", fmt); abort();      // (the entry points refuse it first)
+  const AnnotFrame F = { { dst.pl[0], dst.pl[1], dst.pl[2] }, { src.pl[0], src.pl[1], src.pl[2] }, { dst.pitch[0], dst.pitch[1], dst.pitch[2] },
+                         { src.pitch[0], src.pitch[1], src.pitch[2] }, dst.iw, dst.ih };
+  const dim3 block(TW / PXW, TH / PXH), grid((F.iw + TW - 1) / TW, (F.ih + TH - 1) / TH);
+  if (!dispatch(fmt, [&](auto f) { hipLaunchKernelGGL(k_annotate<f.value>, grid, block, 0, s, F, recs, n, inplace, clear); })) {
+    fprintf(stderr, "rdk::annotate: unknown pixel format %d\n", fmt); abort();      // (the entry points refuse it first)
   }
 }
 

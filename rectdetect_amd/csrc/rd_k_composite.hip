@@ -16,22 +16,13 @@
 #include <stdlib.h>
 #include "rd_device.h"
 #include "rd_comp.h"
-#include "rectdetect_hip.h"
 
 namespace {
 
-struct CompFrame { uint8_t *pl[3]; int pitch[3]; int iw, ih; };
+using namespace rdpix;
 
 constexpr int TW = RD_COMP_TILE_W, TH = RD_COMP_TILE_H, PXW = 4, PXH = 2;
 static_assert((TW / PXW) * (TH / PXH) == 64 && RD_COMP_CHUNK == 64, "one wave per tile, a lane per item of a chunk");
-
-// floor(v * 256) clamped to [0, hi] in double (anything not above 0, a NaN too, gives 0), then an integer: the rectifier's
-__device__ __forceinline__ int fix8(double v, double hi) {
-  double q = floor(v * 256.0);
-  q = q > 0.0 ? q : 0.0;
-  q = q < hi ? q : hi;
-  return (int)q;
-}
 
 // the colour b | g << 8 | r << 16 of patch `p` (pw x ph BGR bytes) at (s, t) of the unit square
 __device__ __forceinline__ uint32_t paste(const uint8_t *p, int pw, int ph, double s, double t) {
@@ -42,22 +33,13 @@ __device__ __forceinline__ uint32_t paste(const uint8_t *p, int pw, int ph, doub
   const uint8_t *r0 = p + (size_t)y0 * pw * 3, *r1 = p + (size_t)y1 * pw * 3;
   uint32_t col = 0;
 #pragma unroll
-  for (int c = 0; c < 3; c++) {
-    const int top = r0[x0 * 3 + c] * (256 - fx) + r0[x1 * 3 + c] * fx;
-    const int bot = r1[x0 * 3 + c] * (256 - fx) + r1[x1 * 3 + c] * fx;
-    col |= (uint32_t)((top * (256 - fy) + bot * fy + 32768) >> 16) << (8 * c);
-  }
+  for (int c = 0; c < 3; c++) col |= (uint32_t)blend8(lerp8(r0[x0 * 3 + c], r0[x1 * 3 + c], fx), lerp8(r1[x0 * 3 + c], r1[x1 * 3 + c], fx), fy) << (8 * c);
   return col;
 }
 
-// rd_annot_yuv
-__device__ __forceinline__ int yuv_y(int B, int G, int R) { return ((66 * R + 129 * G + 25 * B + 128) >> 8) + 16; }
-__device__ __forceinline__ int yuv_u(int B, int G, int R) { return ((-38 * R - 74 * G + 112 * B + 128) >> 8) + 128; }
-__device__ __forceinline__ int yuv_v(int B, int G, int R) { return ((112 * R - 94 * G - 18 * B + 128) >> 8) + 128; }
-
-template <int FMT> __global__ __launch_bounds__(64) void k_composite(CompFrame F, const rd_comp_rec *__restrict__ recs, int n, const int2 *__restrict__ tiles,
+template <int FMT> __global__ __launch_bounds__(64) void k_composite(PixFrame F, const rd_comp_rec *__restrict__ recs, int n, const int2 *__restrict__ tiles,
                                                                       const uint8_t *__restrict__ patches, int pw, int ph) {
-  constexpr bool YUV = FMT >= RD_PIX_NV12;
+  constexpr bool YUV = is_yuv(FMT);
   const int2 tile = tiles[blockIdx.x];
   const int lane = threadIdx.x;
   const int tx0 = tile.x * TW, ty0 = tile.y * TH, tx1 = min(tx0 + TW, F.iw) - 1, ty1 = min(ty0 + TH, F.ih) - 1;      // the tile, inside the frame
@@ -134,8 +116,8 @@ template <int FMT> __global__ __launch_bounds__(64) void k_composite(CompFrame F
   const uint32_t cov = inframe & ~open;
   if (!cov) return;
   if (!YUV) {
-    constexpr int BPP = (FMT == RD_PIX_BGR || FMT == RD_PIX_RGB) ? 3 : 4;
-    constexpr bool SWAP = FMT == RD_PIX_RGB || FMT == RD_PIX_RGBA;
+    constexpr int BPP = bpp(FMT);
+    constexpr bool SWAP = rb_swapped(FMT);
 #pragma unroll
     for (int j = 0; j < PXH; j++) {
       uint8_t *row = F.pl[0] + (size_t)(y0 + j) * F.pitch[0] + (size_t)x0 * BPP;
@@ -156,7 +138,7 @@ template <int FMT> __global__ __launch_bounds__(64) void k_composite(CompFrame F
       for (int i = 0; i < PXW; i++) {
         if (!(cov & (1u << (j * PXW + i)))) continue;
         const uint32_t c = col[j][i];
-        row[i] = (uint8_t)yuv_y(c & 255, (c >> 8) & 255, (c >> 16) & 255);
+        row[i] = (uint8_t)bgr_y(c & 255, (c >> 8) & 255, (c >> 16) & 255);
       }
     }
     const int cy = y0 >> 1;
@@ -173,7 +155,7 @@ template <int FMT> __global__ __launch_bounds__(64) void k_composite(CompFrame F
         }
       if (!cnt) continue;
       const int h = cnt >> 1, mb = (sb + h) / cnt, mg = (sg + h) / cnt, mr = (sr + h) / cnt;
-      const uint8_t U = (uint8_t)yuv_u(mb, mg, mr), V = (uint8_t)yuv_v(mb, mg, mr);
+      const uint8_t U = (uint8_t)bgr_u(mb, mg, mr), V = (uint8_t)bgr_v(mb, mg, mr);
       const int cx = (x0 >> 1) + q;
       if (FMT == RD_PIX_NV12) {
         uint8_t *uv = F.pl[1] + (size_t)cy * F.pitch[1] + (size_t)cx * 2;
@@ -190,22 +172,12 @@ template <int FMT> __global__ __launch_bounds__(64) void k_composite(CompFrame F
 
 namespace rdk {
 
-void composite(hipStream_t s, int fmt, uint8_t *const planes[3], const int pitch[3], int iw, int ih, const rd_comp_rec *recs, int n, const int32_t *tiles, int ntiles,
-               const uint8_t *patches, int pw, int ph) {
+void composite(hipStream_t s, int fmt, const PixFrame &F, const rd_comp_rec *recs, int n, const int32_t *tiles, int ntiles, const uint8_t *patches, int pw, int ph) {
   if (n <= 0 || ntiles <= 0) return;
-  CompFrame F;
-  for (int k = 0; k < 3; k++) { F.pl[k] = planes[k]; F.pitch[k] = pitch[k]; }
-  F.iw = iw; F.ih = ih;
   const int2 *t = (const int2 *)tiles;
   const dim3 block(64), grid(ntiles);
-  switch (fmt) {
-    case RD_PIX_BGR: hipLaunchKernelGGL(k_composite<RD_PIX_BGR>, grid, block, 0, s, F, recs, n, t, patches, pw, ph); break;
-    case RD_PIX_RGB: hipLaunchKernelGGL(k_composite<RD_PIX_RGB>, grid, block, 0, s, F, recs, n, t, patches, pw, ph); break;
-    case RD_PIX_BGRA: hipLaunchKernelGGL(k_composite<RD_PIX_BGRA>, grid, block, 0, s, F, recs, n, t, patches, pw, ph); break;
-    case RD_PIX_RGBA: hipLaunchKernelGGL(k_composite<RD_PIX_RGBA>, grid, block, 0, s, F, recs, n, t, patches, pw, ph); break;
-    case RD_PIX_NV12: hipLaunchKernelGGL(k_composite<RD_PIX_NV12>, grid, block, 0, s, F, recs, n, t, patches, pw, ph); break;
-    case RD_PIX_I420: hipLaunchKernelGGL(k_composite<RD_PIX_I420>, grid, block, 0, s, F, recs, n, t, patches, pw, ph); break;
-    default: fprintf(stderr, "rdk::composite: unknown pixel format %d\n", fmt); abort();      // (the entry points refuse it first)
+  if (!dispatch(fmt, [&](auto f) { hipLaunchKernelGGL(k_composite<f.value>, grid, block, 0, s, F, recs, n, t, patches, pw, ph); })) {
+    fprintf(stderr, "rdk::composite: unknown pixel format %d\n", fmt); abort();      // (the entry points refuse it first)
   }
 }
 

@@ -14,6 +14,7 @@
 namespace {
 
 using namespace rd;
+using namespace rdpix;
 
 struct P3 { float *p[3]; };
 struct P3c { const float *p[3]; };
@@ -144,11 +145,11 @@ __device__ __forceinline__ uint32_t ld_bytes(const uint8_t *p, int n) {
   return w;
 }
 template <int FMT> __device__ __forceinline__ void pix_load4(uint32_t (&w)[4], const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, const int (&pitch)[3], int x, int y, int m, bool wide) {
-  if (FMT == RD_PIX_RGB) {
+  if (rdpix::bpp(FMT) == 3) {
     const uint8_t *q = p0 + (size_t)y * pitch[0] + 3 * x;
     if (wide && m == 4) { const uint32_t *q4 = (const uint32_t *)q; w[0] = q4[0]; w[1] = q4[1]; w[2] = q4[2]; }
     else for (int k = 0; k < 3; k++) w[k] = ld_bytes(q + 4 * k, 3 * m - 4 * k);
-  } else if (FMT == RD_PIX_BGRA || FMT == RD_PIX_RGBA) {
+  } else if (rdpix::bpp(FMT) == 4) {
     const uint8_t *q = p0 + (size_t)y * pitch[0] + 4 * x;
     if (wide && m == 4) { const uint4 v = *(const uint4 *)q; w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
     else for (int k = 0; k < 4; k++) w[k] = ld_bytes(q + 4 * k, k < m ? 4 : 0);
@@ -167,21 +168,13 @@ template <int FMT> __device__ __forceinline__ void pix_load4(uint32_t (&w)[4], c
   }
 }
 
-// BT.601 limited range, OpenCV's fixed point (the contract in rectdetect_hip.h)
-__device__ __forceinline__ void yuv_bgr(int Y, int U, int V, int &b, int &g, int &r) {
-  const int u = U - 128, v = V - 128, yy = max(Y - 16, 0) * 1220542;
-  r = min(max((yy + 1673527 * v + (1 << 19)) >> 20, 0), 255);
-  g = min(max((yy - 852492 * v - 409993 * u + (1 << 19)) >> 20, 0), 255);
-  b = min(max((yy + 2116026 * u + (1 << 19)) >> 20, 0), 255);
-}
-
 // pixel j (0..3) of a group's raw words -> b, g, r
 template <int FMT> __device__ __forceinline__ void pix_bgr(const uint32_t (&w)[4], int j, int &b, int &g, int &r) {
   const auto byte = [&](int i) { return (int)((w[i >> 2] >> (8 * (i & 3))) & 255u); };
-  if (FMT == RD_PIX_RGB) { r = byte(3 * j); g = byte(3 * j + 1); b = byte(3 * j + 2); }
-  else if (FMT == RD_PIX_BGRA) { b = byte(4 * j); g = byte(4 * j + 1); r = byte(4 * j + 2); }
-  else if (FMT == RD_PIX_RGBA) { r = byte(4 * j); g = byte(4 * j + 1); b = byte(4 * j + 2); }
-  else if (FMT == RD_PIX_NV12) yuv_bgr(byte(j), byte(4 + 2 * (j >> 1)), byte(5 + 2 * (j >> 1)), b, g, r);
+  if (!is_yuv(FMT)) {
+    const int i = rdpix::bpp(FMT) * j, c[3] = { byte(i), byte(i + 1), byte(i + 2) };
+    b = c[rb_swapped(FMT) ? 2 : 0]; g = c[1]; r = c[rb_swapped(FMT) ? 0 : 2];
+  } else if (FMT == RD_PIX_NV12) yuv_bgr(byte(j), byte(4 + 2 * (j >> 1)), byte(5 + 2 * (j >> 1)), b, g, r);
   else yuv_bgr(byte(j), byte(4 + (j >> 1)), byte(6 + (j >> 1)), b, g, r);
 }
 
@@ -237,15 +230,15 @@ __global__ __launch_bounds__(256) void k_pix2plab_t(uint32_t *__restrict__ out, 
 // pixels of 2 rows per output row: HW<FMT> words per source row, or Y of both rows plus the one chroma row they share.  Wide loads under the same `wide` flag
 // (every address and pitch a multiple of 4), bytes otherwise and for groups that run past the row end; a group of m detector pixels has all of its 2m source
 // pixels inside the source row, and both source rows of a detector row exist, because the source is exactly twice the detector's size.
-template <int FMT> struct HalfW { static constexpr int row = (FMT == RD_PIX_BGR || FMT == RD_PIX_RGB) ? 6 : ((FMT == RD_PIX_BGRA || FMT == RD_PIX_RGBA) ? 8 : 2), n = FMT >= RD_PIX_NV12 ? 6 : 2 * row; };
+template <int FMT> struct HalfW { static constexpr int row = 2 * rdpix::bpp(FMT), n = is_yuv(FMT) ? 6 : 2 * row; };      // (row: the words of 8 pixels of plane 0)
 
 // the raw words of detector pixels x..x+3 of detector row y (m of them inside the row): packed formats: source row 2y, then source row 2y+1; NV12: Y of 2y (2 words),
 // Y of 2y+1, then U0 V0 .. U3 V3; I420: Y, Y, then U0..U3, V0..V3
 template <int FMT> __device__ __forceinline__ void pix_load_half(uint32_t (&w)[HalfW<FMT>::n], const uint8_t *p0, const uint8_t *p1, const uint8_t *p2, const int (&pitch)[3], int x, int y, int m, bool wide) {
   constexpr int RW = HalfW<FMT>::row;
   const bool full = wide && m == 4;
-  if (FMT <= RD_PIX_RGBA) {
-    constexpr int bpp = (FMT == RD_PIX_BGR || FMT == RD_PIX_RGB) ? 3 : 4;
+  if (!is_yuv(FMT)) {
+    constexpr int bpp = rdpix::bpp(FMT);
     const uint8_t *q = p0 + (size_t)(2 * y) * pitch[0] + (size_t)(2 * x) * bpp;
 #pragma unroll
     for (int r = 0; r < 2; r++, q += pitch[0]) {
@@ -285,11 +278,9 @@ template <int FMT> __device__ __forceinline__ void pix_bgr_half(const uint32_t (
   for (int t = 0; t < 4; t++) {      // source pixel 2j + (t & 1) of source row t >> 1
     const int sx = 2 * j + (t & 1), sr = t >> 1;
     int pb, pg, pr;
-    if (FMT <= RD_PIX_RGBA) {
-      constexpr int bpp = (FMT == RD_PIX_BGR || FMT == RD_PIX_RGB) ? 3 : 4;
-      const int i = 4 * RW * sr + bpp * sx;
-      if (FMT == RD_PIX_BGR || FMT == RD_PIX_BGRA) { pb = byte(i); pg = byte(i + 1); pr = byte(i + 2); }
-      else { pr = byte(i); pg = byte(i + 1); pb = byte(i + 2); }
+    if (!is_yuv(FMT)) {
+      const int i = 4 * RW * sr + rdpix::bpp(FMT) * sx, c[3] = { byte(i), byte(i + 1), byte(i + 2) };
+      pb = c[rb_swapped(FMT) ? 2 : 0]; pg = c[1]; pr = c[rb_swapped(FMT) ? 0 : 2];
     } else if (FMT == RD_PIX_NV12) yuv_bgr(byte(8 * sr + sx), byte(16 + 2 * j), byte(17 + 2 * j), pb, pg, pr);
     else yuv_bgr(byte(8 * sr + sx), byte(16 + j), byte(20 + j), pb, pg, pr);
     b += pb; g += pg; r += pr;
@@ -1092,8 +1083,8 @@ void bgr2plab_transposed(hipStream_t s, uint32_t *out, float *const dst[3], cons
 void bgr2plab_transposed(hipStream_t s, uint32_t *out, float *const dst[3], const uint8_t *bgr, int iw, int ih, int ws) {
   bgr2plab_transposed(s, out, dst, &bgr, iw, ih, ws, 1, 0);
 }
-void pix2plab_transposed(hipStream_t s, int fmt, uint32_t *out, float *const dst[3], const uint8_t *const (*planes)[3], const int pitch[3], int iw, int ih, int nz, size_t zs) {
-  P3 d = { { dst[0], dst[1], dst[2] } };
+// the nz frames of a group launch as the kernels take them; wide: every address and pitch a multiple of 4
+static PixZ pixz_of(const uint8_t *const (*planes)[3], const int pitch[3], int nz) {
   PixZ z;
   z.wide = 1;
   for (int k = 0; k < 3; k++) {
@@ -1101,35 +1092,23 @@ void pix2plab_transposed(hipStream_t s, int fmt, uint32_t *out, float *const dst
     if (pitch[k] & 3) z.wide = 0;
     for (int i = 0; i < RD_ZB_MAX; i++) { z.p[k][i] = planes[i < nz ? i : 0][k]; if ((uintptr_t)z.p[k][i] & 3) z.wide = 0; }
   }
+  return z;
+}
+void pix2plab_transposed(hipStream_t s, int fmt, uint32_t *out, float *const dst[3], const uint8_t *const (*planes)[3], const int pitch[3], int iw, int ih, int nz, size_t zs) {
+  const P3 d = { { dst[0], dst[1], dst[2] } };
+  const PixZ z = pixz_of(planes, pitch, nz);
   const dim3 grid(cdiv(iw, 64), cdiv(ih, 64), nz);
-  switch (fmt) {
-    case RD_PIX_RGB: hipLaunchKernelGGL(k_pix2plab_t<RD_PIX_RGB>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
-    case RD_PIX_BGRA: hipLaunchKernelGGL(k_pix2plab_t<RD_PIX_BGRA>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
-    case RD_PIX_RGBA: hipLaunchKernelGGL(k_pix2plab_t<RD_PIX_RGBA>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
-    case RD_PIX_NV12: hipLaunchKernelGGL(k_pix2plab_t<RD_PIX_NV12>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
-    case RD_PIX_I420: hipLaunchKernelGGL(k_pix2plab_t<RD_PIX_I420>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
-    default: abort();
-  }
+  // (a BGR frame has k_bgr2plab_t: no instantiation for it here)
+  const bool known = fmt != RD_PIX_BGR && dispatch(fmt, [&](auto f) {
+    if constexpr (f.value != RD_PIX_BGR) hipLaunchKernelGGL(k_pix2plab_t<f.value>, grid, block2, 0, s, out, d, z, iw, ih, zs);
+  });
+  if (!known) abort();
 }
 void pix2plab_half_transposed(hipStream_t s, int fmt, uint32_t *out, float *const dst[3], const uint8_t *const (*planes)[3], const int pitch[3], int iw, int ih, int nz, size_t zs) {
-  P3 d = { { dst[0], dst[1], dst[2] } };
-  PixZ z;
-  z.wide = 1;
-  for (int k = 0; k < 3; k++) {
-    z.pitch[k] = pitch[k];
-    if (pitch[k] & 3) z.wide = 0;
-    for (int i = 0; i < RD_ZB_MAX; i++) { z.p[k][i] = planes[i < nz ? i : 0][k]; if ((uintptr_t)z.p[k][i] & 3) z.wide = 0; }
-  }
+  const P3 d = { { dst[0], dst[1], dst[2] } };
+  const PixZ z = pixz_of(planes, pitch, nz);
   const dim3 grid(cdiv(iw, 64), cdiv(ih, 64), nz);
-  switch (fmt) {
-    case RD_PIX_BGR: hipLaunchKernelGGL(k_pix2plab_half_t<RD_PIX_BGR>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
-    case RD_PIX_RGB: hipLaunchKernelGGL(k_pix2plab_half_t<RD_PIX_RGB>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
-    case RD_PIX_BGRA: hipLaunchKernelGGL(k_pix2plab_half_t<RD_PIX_BGRA>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
-    case RD_PIX_RGBA: hipLaunchKernelGGL(k_pix2plab_half_t<RD_PIX_RGBA>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
-    case RD_PIX_NV12: hipLaunchKernelGGL(k_pix2plab_half_t<RD_PIX_NV12>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
-    case RD_PIX_I420: hipLaunchKernelGGL(k_pix2plab_half_t<RD_PIX_I420>, grid, block2, 0, s, out, d, z, iw, ih, zs); break;
-    default: abort();
-  }
+  if (!dispatch(fmt, [&](auto f) { hipLaunchKernelGGL(k_pix2plab_half_t<f.value>, grid, block2, 0, s, out, d, z, iw, ih, zs); })) abort();
 }
 void unpack_plab(hipStream_t s, float *L, float *a, float *b, const uint32_t *in, int n) {
   hipLaunchKernelGGL(k_unpack_plab, dim3(ew_grid(n)), dim3(256), 0, s, L, a, b, in, n);

@@ -17,7 +17,7 @@
 
 namespace {
 
-template <int FMT> __global__ __launch_bounds__(64) void k_signature(int8_t *sig, int *sums, RectifySrc S, const rdk::RectifyQuad *quads, int G, int m) {
+template <int FMT> __global__ __launch_bounds__(64) void k_signature(int8_t *sig, int *sums, PixFrame S, const rdk::RectifyQuad *quads, int G, int m) {
   const int i = blockIdx.x * 8 + threadIdx.x, j = blockIdx.y * 8 + threadIdx.y;      // (G is a multiple of 8: every thread has a cell)
   const rdk::RectifyQuad Q = quads[blockIdx.z];
   int8_t *dst = sig + (size_t)blockIdx.z * G * G + (size_t)j * G + i;
@@ -116,20 +116,11 @@ __global__ void k_match_rotations(int8_t *lib, const int8_t *S, int G) {
 
 namespace rdk {
 
-void match_signatures(hipStream_t s, int8_t *sig, int *sums, int fmt, const uint8_t *const planes[3], const int pitch[3], int iw, int ih, const RectifyQuad *quads, int n, int G, int m) {
+void match_signatures(hipStream_t s, int8_t *sig, int *sums, int fmt, const PixFrame &S, const RectifyQuad *quads, int n, int G, int m) {
   if (n <= 0) return;
-  RectifySrc S;
-  for (int k = 0; k < 3; k++) { S.pl[k] = planes[k]; S.pitch[k] = pitch[k]; }
-  S.iw = iw; S.ih = ih;
   const dim3 block(8, 8), grid(G / 8, G / 8, n);
-  switch (fmt) {
-    case RD_PIX_BGR: hipLaunchKernelGGL(k_signature<RD_PIX_BGR>, grid, block, 0, s, sig, sums, S, quads, G, m); break;
-    case RD_PIX_RGB: hipLaunchKernelGGL(k_signature<RD_PIX_RGB>, grid, block, 0, s, sig, sums, S, quads, G, m); break;
-    case RD_PIX_BGRA: hipLaunchKernelGGL(k_signature<RD_PIX_BGRA>, grid, block, 0, s, sig, sums, S, quads, G, m); break;
-    case RD_PIX_RGBA: hipLaunchKernelGGL(k_signature<RD_PIX_RGBA>, grid, block, 0, s, sig, sums, S, quads, G, m); break;
-    case RD_PIX_NV12: hipLaunchKernelGGL(k_signature<RD_PIX_NV12>, grid, block, 0, s, sig, sums, S, quads, G, m); break;
-    case RD_PIX_I420: hipLaunchKernelGGL(k_signature<RD_PIX_I420>, grid, block, 0, s, sig, sums, S, quads, G, m); break;
-    default: fprintf(stderr, "rdk::match_signatures: unknown pixel format %d\n", fmt); abort();      // (the entry points refuse it first)
+  if (!dispatch(fmt, [&](auto f) { hipLaunchKernelGGL(k_signature<f.value>, grid, block, 0, s, sig, sums, S, quads, G, m); })) {
+    fprintf(stderr, "rdk::match_signatures: unknown pixel format %d\n", fmt); abort();      // (the entry points refuse it first)
   }
 }
 

@@ -16,7 +16,7 @@
 
 namespace {
 
-template <int FMT> __global__ __launch_bounds__(64) void k_rectify(uint8_t *out, RectifySrc S, const rdk::RectifyQuad *quads, int pw, int ph) {
+template <int FMT> __global__ __launch_bounds__(64) void k_rectify(uint8_t *out, PixFrame S, const rdk::RectifyQuad *quads, int pw, int ph) {
   const int i0 = (blockIdx.x * 8 + threadIdx.x) * 4, j = blockIdx.y * 8 + threadIdx.y;
   if (i0 >= pw || j >= ph) return;
   const rdk::RectifyQuad Q = quads[blockIdx.z];
@@ -43,20 +43,11 @@ template <int FMT> __global__ __launch_bounds__(64) void k_rectify(uint8_t *out,
 
 namespace rdk {
 
-void rectify(hipStream_t s, uint8_t *out, int fmt, const uint8_t *const planes[3], const int pitch[3], int iw, int ih, const RectifyQuad *quads, int n, int pw, int ph) {
+void rectify(hipStream_t s, uint8_t *out, int fmt, const PixFrame &S, const RectifyQuad *quads, int n, int pw, int ph) {
   if (n <= 0) return;
-  RectifySrc S;
-  for (int k = 0; k < 3; k++) { S.pl[k] = planes[k]; S.pitch[k] = pitch[k]; }
-  S.iw = iw; S.ih = ih;
   const dim3 block(8, 8), grid((pw + 31) / 32, (ph + 7) / 8, n);
-  switch (fmt) {
-    case RD_PIX_BGR: hipLaunchKernelGGL(k_rectify<RD_PIX_BGR>, grid, block, 0, s, out, S, quads, pw, ph); break;
-    case RD_PIX_RGB: hipLaunchKernelGGL(k_rectify<RD_PIX_RGB>, grid, block, 0, s, out, S, quads, pw, ph); break;
-    case RD_PIX_BGRA: hipLaunchKernelGGL(k_rectify<RD_PIX_BGRA>, grid, block, 0, s, out, S, quads, pw, ph); break;
-    case RD_PIX_RGBA: hipLaunchKernelGGL(k_rectify<RD_PIX_RGBA>, grid, block, 0, s, out, S, quads, pw, ph); break;
-    case RD_PIX_NV12: hipLaunchKernelGGL(k_rectify<RD_PIX_NV12>, grid, block, 0, s, out, S, quads, pw, ph); break;
-    case RD_PIX_I420: hipLaunchKernelGGL(k_rectify<RD_PIX_I420>, grid, block, 0, s, out, S, quads, pw, ph); break;
-    default: fprintf(stderr, "rdk::rectify: unknown pixel format %d\n", fmt); abort();      // (the entry points refuse it first)
+  if (!dispatch(fmt, [&](auto f) { hipLaunchKernelGGL(k_rectify<f.value>, grid, block, 0, s, out, S, quads, pw, ph); })) {
+    fprintf(stderr, "rdk::rectify: unknown pixel format %d\n", fmt); abort();      // (the entry points refuse it first)
   }
 }
 

@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <atomic>
 #include "rd_annot_cover.h"
+#include "rd_pix.h"
 #include "rectdetect_hip.h"
 
 // Group launches (small frames, rd_api.hip): launchers of the frame path take `nz` frames per launch and `zs`, the byte pitch between the planes
@@ -160,13 +161,13 @@ void polyline_ids(hipStream_t s, const PolyFrame *frames, int nb, int n);
 // ---- rd_k_rectify.hip: rectified patches (the contract: rectdetect_hip.h, "rectified patches")
 // what a job uploads per quad: the coefficients a, b, c, d, e, f, g, h of rd_rectify_coefficients and the quad's status (0: an all-zero patch)
 struct RectifyQuad { double c[8]; int status; int pad; };
-// n patches of pw x ph BGR pixels, patch k at out + k * pw * ph * 3, from one iw x ih frame in format fmt (RD_PIX_*; planes / pitch as the caller's), one launch (quad = blockIdx.z)
-void rectify(hipStream_t s, uint8_t *out, int fmt, const uint8_t *const planes[3], const int pitch[3], int iw, int ih, const RectifyQuad *quads, int n, int pw, int ph);
+// n patches of pw x ph BGR pixels, patch k at out + k * pw * ph * 3, from one frame in format fmt (RD_PIX_*), one launch (quad = blockIdx.z)
+void rectify(hipStream_t s, uint8_t *out, int fmt, const rdpix::PixFrame &src, const RectifyQuad *quads, int n, int pw, int ph);
 
 // ---- rd_k_match.hip: matched quads (the contract: rectdetect_hip.h, "matched quads")
 // the signatures of n quads of one frame: quad k's G * G int8 values at sig + k * G * G (zeros for an invalid quad), its sa, saa ADDED to sums[2k], sums[2k+1]
 // (cleared by the caller); G in {8, 16, 32, 64}, m in {1, 2, 4}
-void match_signatures(hipStream_t s, int8_t *sig, int *sums, int fmt, const uint8_t *const planes[3], const int pitch[3], int iw, int ih, const RectifyQuad *quads, int n, int G, int m);
+void match_signatures(hipStream_t s, int8_t *sig, int *sums, int fmt, const rdpix::PixFrame &src, const RectifyQuad *quads, int n, int G, int m);
 // dots[q * ld + c] = signature q . column c for q < n rounded up to 16, c < ncols rounded up to 16: sig, lib and dots hold the padding rows and columns
 void match_dots(hipStream_t s, int *dots, int ld, const int8_t *sig, int n, const int8_t *lib, int ncols, int D);
 // the records of n quads, without their scores; colsums: sb, sbb per column
@@ -179,8 +180,8 @@ void match_rotations(hipStream_t s, int8_t *lib4, const int8_t *sig, int G);
 // stores them (BGR / BGRA: b, g, r; RGB / RGBA: r, g, b; NV12 / I420: y, u, v of rd_annot_yuv) - as col = c0 | c1 << 8 | c2 << 16
 struct AnnotRec { rd_annot_line L; uint32_t col; uint32_t pad; };
 enum { ANNOT_TILE_W = 64, ANNOT_TILE_H = 32, ANNOT_CHUNK = 256 };      // a block's tile of pixels; primitives tested per pass = records of the tile's list in LDS at a time
-// n primitives drawn into one iw x ih frame in format fmt, one launch, one block per tile.  dst == src plane by plane: in place (only covered pixels are written,
+// n primitives drawn into one frame in format fmt (dst and src: the same size), one launch, one block per tile.  dst == src plane by plane: in place (only covered pixels are written,
 // with clear every pixel); otherwise every pixel of dst is written once: the source's, black, or a primitive's colour.  clear: RD_ANNOT_CLEAR.
-void annotate(hipStream_t s, int fmt, uint8_t *const dst[3], const int dpitch[3], const uint8_t *const src[3], const int spitch[3], int iw, int ih, const AnnotRec *recs, int n, int clear);
+void annotate(hipStream_t s, int fmt, const rdpix::PixFrame &dst, const rdpix::PixFrame &src, const AnnotRec *recs, int n, int clear);
 
 }  // namespace rdk

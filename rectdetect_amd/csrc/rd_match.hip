@@ -80,10 +80,10 @@ int rd_matcher_templates(rd_matcher *m) {
 }
 
 // the frame where the kernels read it: a device frame in place, any other through the matcher's own buffer
-static Planes frame_on_device(rd_matcher *m, const char *who, const PixLayout &L, const void *const planes[3], const int pitches[3], int on_device) {
+static PixFrame frame_on_device(rd_matcher *m, const char *who, const PixLayout &L, const void *const planes[3], const int pitches[3], int on_device) {
   if (on_device == RD_FRAME_DEVICE) return planes_at(planes, pitches, L);
   m->frame.grow(m->ring.st, L.bytes);
-  const Planes src = m->frame.packed(L);
+  const PixFrame src = m->frame.packed(L);
   bring(m->ring.st, who, L, src, planes, pitches, on_device);
   return src;
 }
@@ -101,10 +101,10 @@ int rd_matcher_add(rd_matcher *m, int format, const void *const planes[3], const
   if (!q->status) return -2;
   RD_HIP(hipSetDevice(g->device));
   RD_HIP(hipStreamSynchronize(g->st));      // jobs in flight were scored against the library as it was
-  const Planes src = frame_on_device(m, who, L, planes, pitches, on_device);
+  const PixFrame src = frame_on_device(m, who, L, planes, pitches, on_device);
   RD_HIP(hipMemcpyAsync(&m->d_quads[at], q, sizeof(*q), hipMemcpyHostToDevice, g->st));
   RD_HIP(hipMemsetAsync(m->d_tsums, 0, 2 * sizeof(int), g->st));
-  rdk::match_signatures(g->st, m->d_tsig, m->d_tsums, format, src.p, src.pitch, iw, ih, &m->d_quads[at], 1, m->G, m->m);
+  rdk::match_signatures(g->st, m->d_tsig, m->d_tsums, format, src, &m->d_quads[at], 1, m->G, m->m);
   rdrt::check_launch("matched quads: a template's signature");
   RD_HIP(hipMemcpyAsync(m->h_tsums, m->d_tsums, 2 * sizeof(int), hipMemcpyDeviceToHost, g->st));
   RD_HIP(hipStreamSynchronize(g->st));
@@ -151,10 +151,10 @@ long rd_matcher_enqueue(rd_matcher *m, int format, const void *const planes[3], 
     rd_rectify_coefficients(quads + 8 * (size_t)k, q->c, &q->status);
   }
   if (n > 0) {      // (an empty job touches no frame)
-    const Planes src = frame_on_device(m, who, L, planes, pitches, on_device);
+    const PixFrame src = frame_on_device(m, who, L, planes, pitches, on_device);
     RD_HIP(hipMemcpyAsync(d_quads, h_quads, (size_t)n * sizeof(rdk::RectifyQuad), hipMemcpyHostToDevice, g->st));
     RD_HIP(hipMemsetAsync(m->d_sums, 0, (size_t)n * 2 * sizeof(int), g->st));
-    rdk::match_signatures(g->st, m->d_sig, m->d_sums, format, src.p, src.pitch, iw, ih, d_quads, n, m->G, m->m);
+    rdk::match_signatures(g->st, m->d_sig, m->d_sums, format, src, d_quads, n, m->G, m->m);
     rdrt::check_launch("matched quads: signatures");
     rdk::match_dots(g->st, m->d_dots, m->cols, m->d_sig, n, m->d_lib, ncols, m->D);
     rdrt::check_launch("matched quads: dots");

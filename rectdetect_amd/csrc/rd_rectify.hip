@@ -103,7 +103,7 @@ long rd_rectifier_enqueue(rd_rectifier *r, int format, const void *const planes[
     rd_rectify_coefficients(quads + 8 * (size_t)k, q->c, &q->status);
   }
   if (n > 0) {      // (an empty job touches no frame)
-    Planes src = planes_at(planes, pitches, L);      // a device frame: read where it lies
+    PixFrame src = planes_at(planes, pitches, L);      // a device frame: read where it lies
     if (on_device != RD_FRAME_DEVICE) {              // through the rectifier's own buffer, one plane after the other
       r->frame.grow(g->st, L.bytes);
       src = r->frame.packed(L);
@@ -115,7 +115,7 @@ long rd_rectifier_enqueue(rd_rectifier *r, int format, const void *const planes[
       if (!r->d_out[slot]) RD_HIP(hipMalloc((void **)&r->d_out[slot], (size_t)g->per_job * r->patch_bytes));      // (on first use: a rectifier that writes to device memory only has none)
       dst = r->d_out[slot];
     }
-    rdk::rectify(g->st, dst, format, src.p, src.pitch, iw, ih, d_quads, n, r->pw, r->ph);
+    rdk::rectify(g->st, dst, format, src, d_quads, n, r->pw, r->ph);
     rdrt::check_launch("rectified patches");
     if (out_kind == RD_FRAME_HOST_PINNED) RD_HIP(hipMemcpyAsync(out, dst, (size_t)n * r->patch_bytes, hipMemcpyDeviceToHost, g->st));
   }

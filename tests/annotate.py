@@ -1,11 +1,12 @@
 """Annotated frames for the tests: the contract of include/rectdetect_hip.h ("annotated frames") restated from its DEFINITION - the loop over the major coordinate
 with V(u) by floor division, not the per-pixel e test the kernel evaluates - in Python integers (covers) and numpy int64 (draw: every product stays below 2^45).
-Painter's order, the chroma rule, RD_ANNOT_CLEAR and the host helpers (rd_annot_rects, rd_annot_segments, rd_annot_yuv) are restated here too."""
+Painter's order, the chroma rule, RD_ANNOT_CLEAR and the host helpers (rd_annot_rects, rd_annot_segments) are restated here too; rd_annot_yuv is tests/pixfmt.py's bgr2yuv."""
 import math
 
 import numpy as np
 
 import rectdetect_amd as ra
+from tests.pixfmt import bgr2yuv as yuv      # rd_annot_yuv: (Y, U, V)
 
 COORD_MIN, COORD_MAX = -1048576, 1048575
 VIDRECT_STYLE = ((0, 255, 0, 1), (0, 200, 255, 2), (255, 0, 0, 1), (0, 0, 255, 2))      # b, g, r, thickness by status
@@ -62,12 +63,6 @@ def owners(prim_array, iw, ih, origin=(0, 0)):
             else:
                 own[u[ok] - oy, v[ok] - ox] = k
     return own
-
-
-def yuv(b, g, r):
-    """rd_annot_yuv in numpy int32 (arrays or scalars): (Y, U, V)"""
-    b, g, r = (np.asarray(v).astype(np.int32) for v in (b, g, r))
-    return ((66 * r + 129 * g + 25 * b + 128) >> 8) + 16, ((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128, ((112 * r - 94 * g - 18 * b + 128) >> 8) + 128
 
 
 def draw(fmt, planes, iw, ih, prim_array, clear=False):

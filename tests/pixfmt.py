@@ -30,12 +30,15 @@ def nv12_to_bgr(Y, UV):
     return i420_to_bgr(Y, UV[:, 0::2], UV[:, 1::2])
 
 
+def bgr2yuv(b, g, r):
+    """BGR -> YUV of the contract (rd_annot_yuv: BT.601 limited range) in numpy int32, arrays or scalars: (Y, U, V)"""
+    b, g, r = (np.asarray(v).astype(np.int32) for v in (b, g, r))
+    return ((66 * r + 129 * g + 25 * b + 128) >> 8) + 16, ((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128, ((112 * r - 94 * g - 18 * b + 128) >> 8) + 128
+
+
 def bgr_to_i420(bgr):
-    """BT.601 limited range, chroma averaged over 2x2 (even sizes): Y, U, V uint8 planes"""
-    b, g, r = (bgr[..., k].astype(np.int32) for k in range(3))
-    Y = ((66 * r + 129 * g + 25 * b + 128) >> 8) + 16
-    U = ((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128
-    V = ((112 * r - 94 * g - 18 * b + 128) >> 8) + 128
+    """chroma averaged over 2x2 (even sizes): Y, U, V uint8 planes"""
+    Y, U, V = bgr2yuv(bgr[..., 0], bgr[..., 1], bgr[..., 2])
     sub = lambda c: (c[0::2, 0::2] + c[1::2, 0::2] + c[0::2, 1::2] + c[1::2, 1::2] + 2) >> 2
     return tuple(np.clip(a, 0, 255).astype(np.uint8) for a in (Y, sub(U), sub(V)))
 
