@@ -26,6 +26,8 @@ inline dim3 grid2(int iw, int ih) { return dim3(cdiv(iw, 64), cdiv(ih, 4)); }
 #define RD_XY const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y
 #define SPARSE_GRID 512
 #define SPARSE_LOOP(i, cnt) for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < (cnt); i += gridDim.x * blockDim.x)
+// the same over the survivor list (k_compact1<0>): i = compact index of a chain pixel whose component can pass the size filter
+#define SURV_LOOP(i) for (int j_ = blockIdx.x * blockDim.x + threadIdx.x, ns_ = s.ctr[26]; j_ < ns_; j_ += gridDim.x * blockDim.x) if (const int i = s.surv[j_]; true)
 
 struct ls_rec { float x0, y0, x1, y1; int startIndex, endIndex, leftPtr, rightPtr, startCount, endCount, maxDist, polyid, npix, level; };
 struct lsx_rec { long long mx00, mx01, mx11, my0, my1; short dx, dy, vx, vy; int d2, pad; };
@@ -187,7 +189,7 @@ __device__ __forceinline__ int px_rank(const PolyScratch &s, int wpr, int qx, in
   return s.rowbase[qy] + s.pw[wi] + __popcll(w & ((1ull << b) - 1ull));
 }
 
-// pos[rank] = pixel for every chain pixel (raster order), lab[rank] = rank, ends[rank] = 0; rowbase[y] = chain pixels in rows above y; ctr[0] = their number
+// pos[rank] = pixel for every chain pixel (raster order), lab[rank] = rank, ends[rank] = 0, size[rank] = 0 (the component sizes of k_flatten); rowbase[y] = chain pixels in rows above y; ctr[0] = their number
 #define CS_ROWS_PER_BLOCK 8
 __global__ __launch_bounds__(256) void k_chain_scatter(const rdk::PolyFrames FRS, int iw, int ih, int wpr) {
   RD_FRAME;
@@ -218,7 +220,7 @@ __global__ __launch_bounds__(256) void k_chain_scatter(const rdk::PolyFrames FRS
     while (w) {
       const int b = __ffsll((long long)w) - 1;
       w &= w - 1;
-      s.pos[rank] = p + b; s.lab[rank] = rank; s.ends[rank] = 0;
+      s.pos[rank] = p + b; s.lab[rank] = rank; s.ends[rank] = 0; s.size[rank] = 0;
       rank++;
     }
   }
@@ -236,7 +238,8 @@ __global__ __launch_bounds__(256) void k_chain_scatter(const rdk::PolyFrames FRS
 // optional): pos[rank] = index, rank1[index] = rank + 1 for non-zero elements; *cnt = their number.
 #define CP_K (CP_PER_BLOCK / 256)
 __device__ __forceinline__ unsigned long long cp_word(unsigned gen, unsigned status, unsigned value) { return ((unsigned long long)(gen & 0xffffffu) << 40) | ((unsigned long long)status << 38) | value; }
-// (MODE 0 - the chain pixels themselves out of a dense plane - is gone: k_chain_scatter.)  MODE 1: element i is "chain pixel i is the root of a sub-chain of more than size_thre pixels"
+// MODE 0: element i is "chain pixel i lies in an 8-connected component of more than size_thre pixels" - the survivor list surv[], count in ctr[26] (k_flatten(0) has left
+// the root in lab[] and the component's size at the root in size[]); the other pixels get lab2 = -1 on the way, which is all the launches behind the chain graph read of them.  MODE 1: element i is "chain pixel i is the root of a sub-chain of more than size_thre pixels"
 // (pl:380-420: surviving roots are numbered 1..K in raster order = compact order).  MODE 2: element i is the id of chain pixel i's
 // sub-chain (0 = dropped), computed and stored on the way; block 0 also resets what the single-launch stage expects cleared
 // (header record, counters ctr[2..23], ctr[25]) when ls != nullptr.
@@ -244,11 +247,11 @@ template <int MODE>
 __global__ __launch_bounds__(256) void k_compact1(const rdk::PolyFrames FRS, int n, int nblk, int size_thre, int init_ls) {
   RD_FRAME;
   // what the three call sites compact, and where the results go (each has its own state words)
-  static_assert(MODE == 1 || MODE == 2, "two call sites");
-  int *__restrict__ pos = MODE == 2 ? s.live : nullptr;
+  static_assert(MODE == 0 || MODE == 1 || MODE == 2, "three call sites");
+  int *__restrict__ pos = MODE == 2 ? s.live : MODE == 0 ? s.surv : nullptr;
   int *__restrict__ rank1 = MODE == 1 ? s.rootid : nullptr;
   const int *nptr = s.ctr;
-  int *cnt = MODE == 1 ? s.ctr + 1 : s.ctr + 24;
+  int *cnt = MODE == 1 ? s.ctr + 1 : MODE == 2 ? s.ctr + 24 : s.ctr + 26;
   unsigned long long *state = s.cstate + (size_t)MODE * nblk;
   const int *genp = s.csync;
   ls_rec *ls = (MODE == 2 && init_ls) ? (ls_rec *)FRM.lslist : nullptr;
@@ -268,7 +271,15 @@ __global__ __launch_bounds__(256) void k_compact1(const rdk::PolyFrames FRS, int
   const unsigned gen = (unsigned)*genp;
   // flags of this thread's CP_K elements (all loads in flight together), wave counts per row of 256 elements
   unsigned on = 0;
-  if (MODE == 1) {
+  if (MODE == 0) {
+    int l[CP_K];
+#pragma unroll
+    for (int k = 0; k < CP_K; k++) { const int i = b * CP_PER_BLOCK + k * 256 + tid; l[k] = s.lab[i < n ? i : 0]; }
+#pragma unroll
+    for (int k = 0; k < CP_K; k++) l[k] = s.size[l[k]];      // pixels of the component (lab[] holds roots: k_flatten(0))
+#pragma unroll
+    for (int k = 0; k < CP_K; k++) { const int i = b * CP_PER_BLOCK + k * 256 + tid; if (i < n) { if (l[k] > size_thre) on |= 1u << k; else s.lab2[i] = -1; } }
+  } else if (MODE == 1) {
     int l[CP_K], sz[CP_K];
 #pragma unroll
     for (int k = 0; k < CP_K; k++) { const int i = b * CP_PER_BLOCK + k * 256 + tid; const int q = i < n ? i : 0; l[k] = s.lab2[q]; sz[k] = s.size[q]; }
@@ -340,6 +351,21 @@ __global__ __launch_bounds__(256) void k_compact1(const rdk::PolyFrames FRS, int
 }
 
 // ------------------------------------------------------------------------------------------------ chain graph
+// The launches, in order (polyline()):
+//   k_chain_union, k_flatten(0)    all chain pixels: neighbours, 8-connected components, per component its ends and its PIXELS (size[] at the root)
+//   k_compact1<0>                  the survivor list surv[] (count ctr[26]): the pixels of components of more than size_thre pixels, ascending.  The size filter
+//                                  further down counts the pixels of SUB-chains, a sub-chain lies within one component, so every other pixel ends with id 0 whatever
+//                                  the launches in between compute for it: it gets lab2 = -1 here and is not looked at again until k_compact1<1> / <2> read that -1.
+//                                  The test is `size > size_thre` on the component, the filter's own: it is not sharpened by the pixel a chain loses to number 0,
+//                                  because a chain beyond the 4 x 8-hop reach of the end search need not have one (tests/polycases.py: arch_mask)
+//   k_find_ends0, _flags, k_find_ends1 x 4, k_number x 3, k_flatten(1)
+//                                  over the survivor list (SURV_LOOP).  Arrays stay indexed by the compact index, and a survivor's neighbours are survivors -
+//                                  components are closed under the 8-neighbourhood - so nbr[] needs no remapping and no launch reads a record that was not written
+//   k_sub_union                    all chain pixels again, the dropped ones leaving at lab2 < 0 (see there)
+//   k_compact1<1>, <2>             all chain pixels: ids of the sub-chains that pass the size filter, the list live[] of their pixels
+// On the bench stream 12 % of the chain pixels are survivors (tools/chain_survivors.py).  What the hop launches read per hop is one 8-byte record (ne[], nl[]).
+// Nothing relies on an array's content from one frame to the next (rd_k_rect.hip reuses nbr, lab, alive behind the stage).
+//
 // The 8 neighbour compact indices of every chain pixel (E,NE,N,NW,W,SW,S,SE; -1 = none), its degree, and - in the same launch -
 // the 8-connected components of the chain mask (pl:811-854 to convergence): union with every neighbour of smaller index.
 // (lab[i] = i and ends[i] = 0 were set for all chain pixels by k_chain_scatter)
@@ -362,27 +388,29 @@ __global__ void k_chain_union(const rdk::PolyFrames FRS, int iw, int wpr) {
 
 // Optional work on the way, with the root each pixel has just found (saves a launch each):
 //   ends / deg: pl:149-155 - a pixel with junction count 2 (itself + one neighbour, deg == 1) is a chain end; count the ends per chain;
-//   size: pl:357-378 - pixels per sub-chain.  The lanes of a wave are consecutive chain pixels in raster order: a run of equal roots
-//         (a horizontal stretch of one chain) is counted by its first lane - same-address atomics are served one after the other,
-//         a long chain was thousands of them.
-// which 0: chain labels (+ ends per chain); 1: sub-chain labels (+ sizes)
+//   size: pl:357-378 - pixels per sub-chain (which 1); pixels per 8-connected component (which 0: what the survivor list is made from).
+//         The lanes of a wave are consecutive chain pixels in raster order: a run of equal roots (a horizontal stretch of one chain) is
+//         counted by its first lane - same-address atomics are served one after the other, a long chain was thousands of them.
+// which 0: chain labels (+ ends and pixels per chain), over all chain pixels; 1: sub-chain labels (+ sizes), over the survivor list (list order is raster order:
+// the runs stay runs, and integer atomics commute)
 __global__ void k_flatten(const rdk::PolyFrames FRS, int which) {
   RD_FRAME;
   int *lab = which == 0 ? s.lab : s.lab2;
   int *ends = which == 0 ? s.ends : nullptr;
   const int *deg = s.flag2;
-  int *size = which == 0 ? nullptr : s.size;
-  const int cnt = s.ctr[0];
-  for (int i0 = (blockIdx.x * blockDim.x + threadIdx.x) & ~63; i0 < cnt; i0 += gridDim.x * blockDim.x) {     // whole waves together
-    const int lane = threadIdx.x & 63, i = i0 + lane;
+  int *size = s.size;
+  const int cnt = which == 0 ? s.ctr[0] : s.ctr[26];
+  for (int j0 = (blockIdx.x * blockDim.x + threadIdx.x) & ~63; j0 < cnt; j0 += gridDim.x * blockDim.x) {     // whole waves together
+    const int lane = threadIdx.x & 63, j = j0 + lane;
     int r = -1;
-    if (i < cnt) {
+    if (j < cnt) {
+      const int i = which == 0 ? j : s.surv[j];
       const int l = lab[i];
       r = l;
       if (l >= 0) { r = uf_find(lab, l); if (r != l) lab[i] = r; }
       if (ends != nullptr && deg[i] == 1) atomicAdd(&ends[r], 1);
     }
-    if (size != nullptr) {
+    {
       const int prev = __shfl_up(r, 1);
       const bool start = lane == 0 || prev != r;
       const unsigned long long after = __ballot(start) & ~((2ull << lane) - 1ull);
@@ -397,8 +425,7 @@ __global__ void k_flatten(const rdk::PolyFrames FRS, int which) {
 //  in alive[] for the launches that follow)
 __global__ void k_find_ends0(const rdk::PolyFrames FRS) {
   RD_FRAME;
-  const int cnt = s.ctr[0];
-  SPARSE_LOOP(i, cnt) {
+  SURV_LOOP(i) {
     // (the eight neighbours, then their labels and end counts: two levels of loads, each issued together)
     int nb[8], lb[8], eb[8];
 #pragma unroll
@@ -418,106 +445,105 @@ __global__ void k_find_ends0(const rdk::PolyFrames FRS) {
         else if (living && found == 1) { b = nb[k]; found = 2; }
       }
     }
-    s.nx[0][i] = a; s.pv[0][i] = b;
+    s.ne[1][i] = make_int2(a, b);      // (plain: k_find_ends0_flags makes page 0 of it)
   }
 }
 
+// A record of the end search: .x = next, .y = prev, each with the orientation bit of its side in bit 30 (compact indices stay below 2^30: polyline()).
+// A hop reads ONE record of the pixel it stands on - both pointers and both bits - where it read two pointers and a flag word from three arrays.
+#define NE_IDX 0x3fffffff
+#define NE_BIT(v) (((v) >> 30) & 1)
 __global__ void k_find_ends0_flags(const rdk::PolyFrames FRS) {
   RD_FRAME;
-  const int cnt = s.ctr[0];
-  SPARSE_LOOP(i, cnt) {
-    int f = 0;
+  const int2 *__restrict__ raw = s.ne[1];
+  SURV_LOOP(i) {
+    int2 r = raw[i];
     if (s.alive[i]) {
-      const int a = s.nx[0][i], b = s.pv[0][i];
-      if (a != i && s.nx[0][a] == i) f |= 1;
-      if (b != i && s.pv[0][b] == i) f |= 2;
+      const int a = r.x, b = r.y;
+      if (a != i && raw[a].x == i) r.x |= 1 << 30;
+      if (b != i && raw[b].y == i) r.y |= 1 << 30;
     }
-    s.flag[i] = f;
+    s.ne[0][i] = r;
   }
 }
 
-// pl:222-267: eight hops towards both chain ends with orientation-reversal tracking; page selects the flag bit pair
+// pl:222-267: eight hops towards both chain ends with orientation-reversal tracking; a launch reads one page of records and writes the other
 // (final: the last of the four launches also does pl:269-285 for its pixel - link towards the end with the smaller index, the
-//  end itself gets number 0 - with the two ends it has just found)
+//  end itself gets number 0 - with the two ends it has just found; nothing reads its records).  No early exit at an end: the orientation bits
+// keep evolving there and the later launches read them.
 __global__ void k_find_ends1(const rdk::PolyFrames FRS, int page, int final) {
   RD_FRAME;
-  const int cnt = s.ctr[0];
-  const int *ni = s.nx[page], *pi = s.pv[page];
-  int *no = s.nx[page ^ 1], *po = s.pv[page ^ 1];
-  const int *fin = page == 0 ? s.flag : s.flag2;
-  int *fout = page == 0 ? s.flag2 : s.flag;
-  SPARSE_LOOP(i, cnt) {
-    if (!s.alive[i]) { no[i] = i; po[i] = i; fout[i] = fin[i]; if (final) { s.num[0][i] = 0; s.link[0][i] = -1; } continue; }
-    const int f0 = fin[i];
-    bool revn = page == 0 ? (f0 & 1) != 0 : (f0 & 4) != 0;
-    bool revp = page == 0 ? (f0 & 2) != 0 : (f0 & 8) != 0;
-    int nn = ni[i], pp = pi[i];
+  const int2 *__restrict__ rin = s.ne[page];
+  int2 *__restrict__ rout = s.ne[page ^ 1];
+  SURV_LOOP(i) {
+    const int2 me = rin[i];
+    if (!s.alive[i]) { rout[i] = me; if (final) s.nl[0][i] = make_int2(0, -1); continue; }      // (a deleted loop root: next = prev = itself, no bits)
+    bool revn = NE_BIT(me.x) != 0, revp = NE_BIT(me.y) != 0;
+    int nn = me.x & NE_IDX, pp = me.y & NE_IDX;
     for (int h = 0; h < 8; h++) {
-      const int nn2 = revn ? pi[nn] : ni[nn];
-      const int pp2 = revp ? ni[pp] : pi[pp];
-      int nf = fin[nn], pf = fin[pp];
-      if (page != 0) { nf >>= 2; pf >>= 2; }
-      revn = revn ? ((nf & 2) == 0) : ((nf & 1) != 0);
-      revp = revp ? ((pf & 1) == 0) : ((pf & 2) != 0);
-      nn = nn2; pp = pp2;
+      const int2 rn = rin[nn], rp = rin[pp];
+      nn = (revn ? rn.y : rn.x) & NE_IDX;
+      pp = (revp ? rp.x : rp.y) & NE_IDX;
+      revn = revn ? NE_BIT(rn.y) == 0 : NE_BIT(rn.x) != 0;
+      revp = revp ? NE_BIT(rp.x) == 0 : NE_BIT(rp.y) != 0;
     }
-    no[i] = nn; po[i] = pp;
-    int f = f0;
-    if (page == 0) { f &= 3; f |= revn ? 4 : 0; f |= revp ? 8 : 0; }
-    else { f &= (3 << 2); f |= revn ? 1 : 0; f |= revp ? 2 : 0; }
-    fout[i] = f;
-    if (final) {
-      int nb[8], al[8];
+    if (!final) { rout[i] = make_int2(nn | (revn ? 1 << 30 : 0), pp | (revp ? 1 << 30 : 0)); continue; }
+    int nb[8], al[8];
 #pragma unroll
-      for (int k = 0; k < 8; k++) nb[k] = s.nbr[i * 8 + k];
+    for (int k = 0; k < 8; k++) nb[k] = s.nbr[i * 8 + k];
 #pragma unroll
-      for (int k = 0; k < 8; k++) al[k] = s.alive[nb[k] >= 0 ? nb[k] : i];
-      int a = i, b = i, found = 0;
+    for (int k = 0; k < 8; k++) al[k] = s.alive[nb[k] >= 0 ? nb[k] : i];
+    int a = i, b = i, found = 0;
 #pragma unroll
-      for (int k = 0; k < 8; k++) {
-        const bool living = nb[k] >= 0 && al[k] != 0;
-        if (living && found == 0) { a = nb[k]; found = 1; }
-        else if (living && found == 1) { b = nb[k]; found = 2; }
-      }
-      const int lk = nn < pp ? a : b;
-      s.num[0][i] = lk == i ? 0 : 1; s.link[0][i] = lk;
+    for (int k = 0; k < 8; k++) {
+      const bool living = nb[k] >= 0 && al[k] != 0;
+      if (living && found == 0) { a = nb[k]; found = 1; }
+      else if (living && found == 1) { b = nb[k]; found = 2; }
     }
+    const int lk = nn < pp ? a : b;
+    s.nl[0][i] = make_int2(lk == i ? 0 : 1, lk);
   }
 }
 
-// pl:287-310: 32-hop pointer-jumping prefix sum of the hop counts
-// (init_sub: the last round also sets up the sub-chain labelling that follows - pl:312-355 - from the final numbers)
-__global__ void k_number(const rdk::PolyFrames FRS, int src, int init_sub) {
+// pl:287-310: 32-hop pointer-jumping prefix sum of the hop counts.  (number, link) of a pixel is one 8-byte record: a hop is one gather.  A chain end links to
+// itself with number 0 (k_find_ends1, final): once the record just read is such a fixed point every further hop adds 0 and stays, so the loop leaves - both
+// conditions are tested: a link cycle that carries numbers keeps hopping, and the hop counts (3 x 32) stay the reference's where they bite.
+// (last: the third round leaves the plain numbers num[] and sets up the sub-chain labelling that follows - pl:312-355 - from them)
+__global__ void k_number(const rdk::PolyFrames FRS, int src, int last) {
   RD_FRAME;
-  const int cnt = s.ctr[0];
-  const int *ni = s.num[src], *li = s.link[src];
-  int *no = s.num[src ^ 1], *lo_ = s.link[src ^ 1];
-  SPARSE_LOOP(i, cnt) {
-    int n = ni[i], l = li[i];
+  const int2 *__restrict__ in = s.nl[src];
+  int2 *__restrict__ out = s.nl[src ^ 1];
+  SURV_LOOP(i) {
+    const int2 me = in[i];
+    int n = me.x, l = me.y;
     if (l != -1) {
       bool ok = true;
       for (int h = 0; h < 32; h++) {
         if (l < 0) { ok = false; break; }
-        n += ni[l];
-        l = li[l];
+        const int2 r = in[l];
+        n += r.x;
+        if (r.y == l && r.x == 0) break;
+        l = r.y;
       }
       n = ok ? n : 0;
       l = ok ? l : -1;
     }
-    no[i] = n;
-    lo_[i] = l;
-    if (init_sub) { s.lab2[i] = n == 0 ? -1 : i; s.size[i] = 0; s.rootid[i] = 0; }
+    if (!last) { out[i] = make_int2(n, l); continue; }
+    s.num[i] = n;
+    s.lab2[i] = n == 0 ? -1 : i; s.size[i] = 0; s.rootid[i] = 0;
   }
 }
 
-// pl:312-355 to convergence: split chains where the numbering jumps by more than one (set up by the last k_number launch)
+// pl:312-355 to convergence: split chains where the numbering jumps by more than one (set up by the last k_number launch).
+// Over ALL chain pixels, the dropped ones leaving at their label: on the survivor list the launch was slower than before (92 against 67 us per launch of 8 frames;
+// 61 in this form) - there a wave holds 64 pixels of the same few chains, whose unions walk and lower the same words, lane after lane.
 __global__ void k_sub_union(const rdk::PolyFrames FRS) {
   RD_FRAME;
-  const int *__restrict__ number = s.num[1];
+  const int *__restrict__ number = s.num;
   const int cnt = s.ctr[0];
   SPARSE_LOOP(i, cnt) {
+    if (s.lab2[i] < 0) continue;      // dropped before the graph (k_compact1<0>), or number 0
     const int a = number[i];
-    if (a == 0) continue;
 #pragma unroll
     for (int k = 0; k < 8; k++) {
       const int j = s.nbr[i * 8 + k];
@@ -552,7 +578,7 @@ __global__ void k_seg_clear(const rdk::PolyFrames FRS, int lsbytes) { d_seg_clea
 __device__ __forceinline__ void d_seg_pass0a(const rdk::PolyFrames &FRS, int lsbytes) {
   RD_FRAME;
   ls_rec *ls = (ls_rec *)FRM.lslist;
-  const int *__restrict__ number = s.num[1];
+  const int *__restrict__ number = s.num;
   const int nlive = s.ctr[24];
   SPARSE_LOOP(j, nlive) {
     const int i = s.live[j];
@@ -569,7 +595,7 @@ __global__ void k_seg_pass0a(const rdk::PolyFrames FRS, int lsbytes) { d_seg_pas
 __device__ __forceinline__ void d_seg_pass0b(const rdk::PolyFrames &FRS, int lsbytes) {
   RD_FRAME;
   ls_rec *ls = (ls_rec *)FRM.lslist;
-  const int *__restrict__ number = s.num[1];
+  const int *__restrict__ number = s.num;
   const int nlive = s.ctr[24];
   SPARSE_LOOP(j, nlive) {
     const int i = s.live[j];
@@ -609,7 +635,7 @@ __device__ __forceinline__ float dist2f(float vx, float vy, float wx, float wy) 
 __device__ __forceinline__ void d_split_move_dist(const rdk::PolyFrames &FRS, int lsbytes, int iw, int do_dist) {
   RD_FRAME;
   ls_rec *ls = (ls_rec *)FRM.lslist;
-  const int *__restrict__ number = s.num[1];
+  const int *__restrict__ number = s.num;
   const int nlive = s.ctr[24];
   SPARSE_LOOP(j, nlive) {
     const int i = s.live[j];
@@ -644,7 +670,7 @@ __global__ void k_split_move_dist(const rdk::PolyFrames FRS, int lsbytes, int iw
 __device__ __forceinline__ void d_split_detect(const rdk::PolyFrames &FRS, int lsbytes, float minerror, int iw, int round) {
   RD_FRAME;
   const ls_rec *ls = (const ls_rec *)FRM.lslist;
-  const int *__restrict__ number = s.num[1];
+  const int *__restrict__ number = s.num;
   const int nlive = s.ctr[24];
   SPARSE_LOOP(j, nlive) {
     const int i = s.live[j];
@@ -927,7 +953,7 @@ __device__ __noinline__ void pp_moments(pp_lds &L, int pk, int xyv, int n) {
 __global__ __launch_bounds__(PP_T) void k_poly_persistent(const rdk::PolyFrames FRS, int lsbytes, float minerror, int iw) {
   RD_FRAME;
   ls_rec *ls = (ls_rec *)FRM.lslist;
-  const int *__restrict__ number = s.num[1];
+  const int *__restrict__ number = s.num;
   extern __shared__ __attribute__((aligned(16))) char pp_raw[];
   pp_lds &L = *(pp_lds *)pp_raw;
   const int tid = threadIdx.x;
@@ -1178,7 +1204,8 @@ PolyScratch *poly_scratch_create(int iw, int ih) {
   ps->cstate = dalloc<unsigned long long>(3 * (N / CP_PER_BLOCK + 2)); ps->csync = dalloc<int>(4);
   ps->pos = dalloc<int>(N); ps->nbr = dalloc<int>(N * 8);
   ps->lab = dalloc<int>(N); ps->alive = dalloc<int>(N); ps->ends = dalloc<int>(N);
-  for (int k = 0; k < 2; k++) { ps->nx[k] = dalloc<int>(N); ps->pv[k] = dalloc<int>(N); ps->num[k] = dalloc<int>(N); ps->link[k] = dalloc<int>(N); }
+  for (int k = 0; k < 2; k++) { ps->ne[k] = dalloc<int2>(N); ps->nl[k] = dalloc<int2>(N); }
+  ps->num = dalloc<int>(N); ps->surv = dalloc<int>(N);
   ps->flag = dalloc<int>(N); ps->flag2 = dalloc<int>(N);
   ps->lab2 = dalloc<int>(N); ps->size = dalloc<int>(N); ps->rootid = dalloc<int>(N); ps->id = dalloc<int>(N); ps->dist = dalloc<int>(N + 2);
   ps->cand = dalloc<int>(N * 8 / 4 + 64);
@@ -1201,8 +1228,8 @@ void poly_limits(int out[4]) { out[0] = PP_T * PP_PX; out[1] = PP_MAXSEG; out[2]
 
 void poly_scratch_destroy(PolyScratch *ps) {
   if (!ps) return;
-  void *all[] = { ps->sb, ps->rb, ps->tb, ps->pw, ps->rowsum, ps->rowbase, ps->cstate, ps->csync, ps->pos, ps->nbr, ps->lab, ps->alive, ps->ends, ps->nx[0], ps->nx[1], ps->pv[0], ps->pv[1],
-                  ps->num[0], ps->num[1], ps->link[0], ps->link[1], ps->flag, ps->flag2, ps->lab2, ps->size, ps->rootid, ps->id, ps->dist, ps->cand, ps->ctr, ps->lsx, ps->segaux, ps->live };
+  void *all[] = { ps->sb, ps->rb, ps->tb, ps->pw, ps->rowsum, ps->rowbase, ps->cstate, ps->csync, ps->pos, ps->nbr, ps->lab, ps->alive, ps->ends, ps->ne[0], ps->ne[1], ps->nl[0], ps->nl[1],
+                  ps->num, ps->surv, ps->flag, ps->flag2, ps->lab2, ps->size, ps->rootid, ps->id, ps->dist, ps->cand, ps->ctr, ps->lsx, ps->segaux, ps->live };
   for (void *p : all) if (p) (void)hipFree(p);
   delete ps;
 }
@@ -1211,8 +1238,15 @@ void poly_scratch_destroy(PolyScratch *ps) {
 void polyline(hipStream_t st, const PolyFrame *frames_host, int nb, int lslist_bytes, int ring_const, float minerror, int sizeThre, int iw, int ih, int mode) {
   const PolyFrames frames = pack_frames(frames_host, nb);
   const int N = iw * ih;
+  if (N > NE_IDX) { fprintf(stderr, "polyline: %dx%d: compact indices must stay below 2^30 (the records of the end search keep a bit beside them)\n", iw, ih); abort(); }
   const int maxrec = lslist_bytes / 56;
   const dim3 sg(SPARSE_GRID, 1, nb), sb(256);
+  // The launches over the survivor list - about half a per cent of the frame's pixels on the bench stream - get a thread per 128 pixels of the frame (more survivors:
+  // the kernels loop): at 1920x1080 that is 64 blocks a frame instead of 512, and the seven hop launches, which are dependent latency and little else, no longer wait for
+  // thousands of empty blocks to be dispatched (k_find_ends1 18.9 -> 11.5, k_number 29.0 -> 21.3 us per launch of 8 frames: profiles/NOTES_chain_prune.md).
+  int svb = cdiv(N, 128 * 256);
+  svb = svb < 32 ? 32 : svb > SPARSE_GRID ? SPARSE_GRID : svb;
+  const dim3 sv(svb, 1, nb);
 
   // tidy (oclpolyline.c:222-235) and compaction of the chain pixels in raster order, on bit planes
   const int wpr = cdiv(iw, 64);
@@ -1231,16 +1265,20 @@ void polyline(hipStream_t st, const PolyFrame *frames_host, int nb, int lslist_b
 
   // chains, loops, ends (oclpolyline.c:237-266)
   hipLaunchKernelGGL(k_chain_union, sg, sb, 0, st, frames, iw, wpr);
-  hipLaunchKernelGGL(k_flatten, sg, sb, 0, st, frames, 0);      // + ends per chain
-  hipLaunchKernelGGL(k_find_ends0, sg, sb, 0, st, frames);
-  hipLaunchKernelGGL(k_find_ends0_flags, sg, sb, 0, st, frames);
-  for (int r = 0; r < 4; r++) hipLaunchKernelGGL(k_find_ends1, sg, sb, 0, st, frames, r & 1, r == 3 ? 1 : 0);      // (the last one also links and numbers: pl:269-285)
-  // numbering (oclpolyline.c:268-275): three rounds 0->1->0->1 (the result is num[1])
-  for (int r = 0; r < 3; r++) hipLaunchKernelGGL(k_number, sg, sb, 0, st, frames, r & 1, r == 2 ? 1 : 0);
+  hipLaunchKernelGGL(k_flatten, sg, sb, 0, st, frames, 0);      // + ends and pixels per chain
+  // A sub-chain is part of one 8-connected component, so a component of at most sizeThre pixels cannot pass the size filter below whatever the launches in
+  // between compute for it: they run on the list of the other pixels - the survivors, neighbours of survivors are survivors - and the rest get lab2 = -1 here
+  // (no sub-chain: k_compact1<1> sees no root in them, k_compact1<2> gives them id 0; nothing else of them is read behind this point).  sizeThre 0 drops nothing.
+  hipLaunchKernelGGL(k_compact1<0>, cg, dim3(256), 0, st, frames, N, nblk, sizeThre, 0);
+  hipLaunchKernelGGL(k_find_ends0, sv, sb, 0, st, frames);
+  hipLaunchKernelGGL(k_find_ends0_flags, sv, sb, 0, st, frames);
+  for (int r = 0; r < 4; r++) hipLaunchKernelGGL(k_find_ends1, sv, sb, 0, st, frames, r & 1, r == 3 ? 1 : 0);      // (the last one also links and numbers: pl:269-285)
+  // numbering (oclpolyline.c:268-275): three rounds over the record pages 0->1->0, the third leaves the plain numbers num[]
+  for (int r = 0; r < 3; r++) hipLaunchKernelGGL(k_number, sv, sb, 0, st, frames, r & 1, r == 2 ? 1 : 0);
 
   // split at numbering jumps, size filter, compact ids (oclpolyline.c:277-295)
   hipLaunchKernelGGL(k_sub_union, sg, sb, 0, st, frames);
-  hipLaunchKernelGGL(k_flatten, sg, sb, 0, st, frames, 1);     // + sub-chain sizes
+  hipLaunchKernelGGL(k_flatten, sv, sb, 0, st, frames, 1);     // + sub-chain sizes
   // (the chain-pixel count lives on the device: launch for the worst case, blocks beyond it exit at once)
   hipLaunchKernelGGL(k_compact1<1>, cg, dim3(256), 0, st, frames, N, nblk, sizeThre, 0);
   hipLaunchKernelGGL(k_compact1<2>, cg, dim3(256), 0, st, frames, N, nblk, 0, mode == 1 ? 1 : 0);

@@ -13,9 +13,12 @@ struct PolyScratch {
   int *pos;           // compact: pixel index, ascending
   int *nbr;           // compact: 8 neighbour compact indices (E,NE,N,NW,W,SW,S,SE), -1 = none
   int *lab, *alive, *ends;
-  int *nx[2], *pv[2], *flag, *flag2;
-  int *num[2], *link[2];
-  int *lab2, *size, *rootid, *id, *dist;
+  int2 *ne[2];        // end search: two pages of (next, prev) records, an orientation bit in bit 30 of each (k_find_ends1)
+  int *flag, *flag2;  // scratch of the refinement; degree of a chain pixel
+  int2 *nl[2];        // numbering: two pages of (number, link) records - a hop of k_number is one 8-byte gather
+  int *num;           // the final numbers (written by the last k_number round)
+  int *lab2, *size, *rootid, *id, *dist;      // (size: pixels per 8-connected component - k_flatten(0) - until the last k_number round clears it for the sub-chain sizes)
+  int *surv;          // compact indices of the chain pixels whose component has more than size_thre pixels (ascending); count in ctr[26].  The chain graph runs on these
   int *cand;          // candidate records of one split round (8 ints each)
   int *ctr;           // counters: [0]=cnt, [1]=nchains, [2..18]=candidates per round, [20]=refine done count ...
   void *lsx;          // per-segment moment sums
@@ -48,6 +51,7 @@ struct PolyFrame {
 
 #define RD_MAXB 8        // frames per launch of the sparse stages (8 descriptors = 2.8 KB of kernel arguments; the limit is 4 KB)
 struct PolyFrames { PolyFrame f[RD_MAXB]; };
+static_assert(sizeof(PolyFrames) + 64 + 256 <= 4096, "the descriptors travel by value: with a launch's other arguments (64 bytes at the most) and the 256 bytes the compiler appends they must fit 4 KB of kernel arguments");
 inline PolyFrames pack_frames(const PolyFrame *frames, int nb) {
   PolyFrames r;
   for (int z = 0; z < RD_MAXB; z++) r.f[z] = frames[z < nb ? z : 0];
