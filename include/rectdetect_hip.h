@@ -313,6 +313,55 @@ int rd_rectifier_wait(rd_rectifier *r, uint8_t *status_out);
  * the full-size source, see there.  Returns as rd_rectifier_enqueue; -1 also when nothing has been polled yet or d and r are on different devices. */
 long rd_detector_rectify_polled(rd_detector *d, rd_rectifier *r, const double *quads, int n, void *out, int out_kind);
 
+/* -- model-ready tensors: the same patches in the element type, layout and channel order the next model takes, normalised and - for a quad much larger than its
+ * patch - box-filtered, from the one launch (rd_k_tensor.hip, rd_rectify.hip, rd_tensor_host.c).  Exact like everything above: tests/tensor.py restates it in numpy.
+ *
+ * C = 1 for RD_TENSOR_GRAY, otherwise 3.  oversample m is 1, 2 or 4.  scale and bias are indexed by OUTPUT channel - under RD_TENSOR_RGB channel 0 is R -, GRAY uses
+ * index 0, and RD_TENSOR_U8 ignores them.  A spec is LEGAL for pw x ph when every enum is one of the values below, pw >= 1, ph >= 1, pw*m <= 16384, ph*m <= 16384
+ * and, for the float dtypes, scale[c] and bias[c] of the C channels in use are finite.
+ *
+ * Element (k, c, j, i) of a job - quad k, channel c, row j, column i:
+ *   1. P is the patch of quad k at (pw*m) x (ph*m) pixels, byte for byte the contract above: the coefficients, s = (i+0.5)/(pw*m), t = (j+0.5)/(ph*m), the clamps,
+ *      the 8.8 blend, each tap of a YUV frame converted first.
+ *   2. the channel value of a patch pixel, in int32: BGR: byte c of P;  RGB: byte 2-c of P;  GRAY: (29*B + 150*G + 77*R + 128) >> 8 ("matched quads", step 2).
+ *   3. S = the sum of the channel values over the m x m patch pixels (i*m .. i*m+m-1, j*m .. j*m+m-1): an integer, 0 .. 255*m*m.
+ *   4. U8:  (S + m*m/2) >> log2(m*m), one byte.
+ *      the float dtypes, in binary32, uncontracted, in this order:  v = (float)S * (1.0f/(m*m))  (exact: m*m is a power of two and S < 2^12);
+ *        v = v * scale[c], rounded to nearest even;  v = v + bias[c], rounded to nearest even.
+ *      F32 stores v.  F16 stores v converted to binary16, round to nearest even, overflow to infinity, subnormals kept.
+ *      BF16 stores the upper 16 bits of u + 0x7FFF + ((u >> 16) & 1), u the 32 bits of v: round to nearest even, overflow to infinity.  The formula would turn some
+ *      NaNs into infinities, but a NaN cannot arise from a legal spec: v >= 0 is finite, so the product is finite or infinite, and the sum of that and a finite
+ *      bias is never NaN.
+ * The element's offset from the job's `out`, in ELEMENTS:  NHWC: ((k*ph + j)*pw + i)*C + c;   NCHW: ((k*C + c)*ph + j)*pw + i.   `out` is aligned to the element's
+ * size; the job's n * rd_rectifier_patch_bytes(r) bytes are written and nothing else.  An invalid quad (status 0) gives all-zero BYTES in every dtype - not bias -
+ * from the same launch.  The spec { RD_TENSOR_U8, RD_TENSOR_NHWC, RD_TENSOR_BGR, 1 } is, by this definition, exactly the patch of rd_rectifier_create;
+ * { U8, either layout, GRAY, m } at pw = ph = G is the matcher's signature + 128. */
+#define RD_TENSOR_U8 0    /* dtype */
+#define RD_TENSOR_F16 1
+#define RD_TENSOR_BF16 2
+#define RD_TENSOR_F32 3
+#define RD_TENSOR_NHWC 0  /* layout */
+#define RD_TENSOR_NCHW 1
+#define RD_TENSOR_BGR 0   /* channels */
+#define RD_TENSOR_RGB 1
+#define RD_TENSOR_GRAY 2
+typedef struct { int32_t dtype, layout, channels, oversample; float scale[3], bias[3]; } rd_tensor_spec;   /* 40 bytes */
+/* host only, no GPU needed (rd_tensor_host.c).  1 when the spec is legal for pw x ph, else 0 (a NULL spec too) */
+int rd_tensor_spec_ok(const rd_tensor_spec *spec, int pw, int ph);
+/* the bytes of one quad's tensor: pw * ph * C * the element's size; 0 for a spec that is not legal for pw x ph */
+size_t rd_tensor_bytes(const rd_tensor_spec *spec, int pw, int ph);
+/* step 4 for one element of channel c from its box sum S: writes the element's 1, 2 or 4 bytes to out and returns that count; 0, and nothing written, for a NULL
+ * argument, an unknown dtype, channel kind or oversample, or c outside 0 .. C-1 */
+int rd_tensor_element(const rd_tensor_spec *spec, int c, int32_t S, void *out);
+/* out[0..3] <- the legal dtypes, layouts and channel kinds as bit sets (bit v: value v is legal), and the legal oversamplings ORed together (1 | 2 | 4) */
+void rd_tensor_limits(int32_t out[4]);
+/* A rectifier whose jobs write tensors.  NULL for the bad arguments of rd_rectifier_create, a NULL spec or a spec that is not legal for pw x ph.  The handle is an
+ * ordinary rd_rectifier: rd_rectifier_enqueue, rd_rectifier_wait, rd_rectifier_destroy and rd_detector_rectify_polled work on it with every pixel format, frame
+ * kind and output kind, and `out` holds n * rd_rectifier_patch_bytes(r) bytes. */
+rd_rectifier *rd_rectifier_create_tensor(int device, int pw, int ph, int max_quads, int njobs, const rd_tensor_spec *spec);
+/* the bytes of one quad's output: pw * ph * 3 for a rectifier made by rd_rectifier_create; 0 for NULL */
+size_t rd_rectifier_patch_bytes(const rd_rectifier *r);
+
 /* ---- annotated frames: rectangles' outlines and line segments drawn INTO a frame on the device (rd_k_annotate.hip, rd_annotate.hip) - the picture vidrect.cpp /
  * rect.cpp (showRect) and vidpoly.cpp / poly.cpp make with OpenCV's line() on the host, for frames that never leave HBM.  OpenCV's round brush is not restated; the
  * arithmetic is defined here, in integers, exactly, so that an independent restatement (tests/annotate.py) reproduces every byte.

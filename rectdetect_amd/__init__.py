@@ -10,7 +10,8 @@ Mirrors of the reference programs' call sequences:
   * :class:`RectDetector` - rect.cpp / vidrect.cpp (``oclrect_executeOnce`` / ``enqueueTask`` / ``pollTask``)
   * :class:`Detector` - the ``rd_detector`` extension (device-resident frames, several frames in flight)
   * :class:`PolylineDetector` - its polyline kind: poly.cpp / vidpoly.cpp per frame, several frames in flight
-  * :class:`Rectifier` - the ``rd_rectifier`` extension: what is inside detected quads as upright patches of fixed size
+  * :class:`Rectifier` - the ``rd_rectifier`` extension: what is inside detected quads as upright patches of fixed size, or - with a
+    :func:`tensor_spec` - as model-ready tensors (float, planar, normalised, box-filtered)
   * :class:`Annotator` - the ``rd_annotator`` extension: rectangles' outlines and line segments drawn into frames on the device
   * :class:`Compositor` - the ``rd_compositor`` extension: a colour or an image written into the quads of a frame on the device
   * :class:`Matcher` - the ``rd_matcher`` extension: which template of a library is inside each quad, decided on the device
@@ -38,6 +39,13 @@ MATCH_DTYPE = np.dtype([("status", "<i4"), ("tmpl", "<i4"), ("rot", "<i4"), ("do
                         ("saa", "<i8"), ("score", "<f8"), ("score2", "<f8")])
 assert MATCH_DTYPE.itemsize == 56
 MATCH_DOTS = 1
+# a rectifier's tensor spec (rd_tensor_spec; the contract is in include/rectdetect_hip.h, "model-ready tensors")
+TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = range(4)
+TENSOR_NHWC, TENSOR_NCHW = 0, 1
+TENSOR_BGR, TENSOR_RGB, TENSOR_GRAY = range(3)
+TENSOR_SPEC_DTYPE = np.dtype([("dtype", "<i4"), ("layout", "<i4"), ("channels", "<i4"), ("oversample", "<i4"), ("scale", "<f4", (3,)), ("bias", "<f4", (3,))])
+assert TENSOR_SPEC_DTYPE.itemsize == 40
+TENSOR_NUMPY = {TENSOR_U8: np.dtype(np.uint8), TENSOR_F16: np.dtype(np.float16), TENSOR_BF16: np.dtype(np.uint16), TENSOR_F32: np.dtype(np.float32)}      # (bf16: its bits)
 ANNOT_SEG_ALL, ANNOT_SEG_CHAINS = 0, 1
 
 # pixel formats of enqueue_planes (rd_detector_enqueue_planes; the conversion contract is in include/rectdetect_hip.h)
@@ -111,6 +119,13 @@ def _declare(L):
         "rd_rectifier_enqueue": (ctypes.c_long, [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ci, ci, vp, ci, vp, ci]),
         "rd_rectifier_wait": (ci, [vp, vp]),
         "rd_detector_rectify_polled": (ctypes.c_long, [vp, vp, vp, ci, vp, ci]),
+        # model-ready tensors (rd_rectify.hip, rd_tensor_host.c)
+        "rd_tensor_spec_ok": (ci, [vp, ci, ci]),
+        "rd_tensor_bytes": (cz, [vp, ci, ci]),
+        "rd_tensor_element": (ci, [vp, ci, ctypes.c_int32, vp]),
+        "rd_tensor_limits": (None, [vp]),
+        "rd_rectifier_create_tensor": (vp, [ci, ci, ci, ci, ci, vp]),
+        "rd_rectifier_patch_bytes": (cz, [vp]),
         # annotated frames (rd_annotate.hip)
         "rd_annot_covers": (ci, [vp, ci, ci]),
         "rd_annot_touches": (ci, [vp, ci, ci, ci, ci]),
@@ -638,14 +653,14 @@ class _Service:
     """what Rectifier, Annotator and Compositor share: a handle made by rd_<name>_create whose jobs are waited for oldest first"""
     _name = None
 
-    def _create(self, *args):
+    def _create(self, *args, ctor="create"):
         L = lib()
         if L.rd_device_count() <= 0:
             raise RuntimeError("rectdetect_amd: no HIP device visible - there is no CPU fallback")
         self._wait_fn, self._destroy_fn = getattr(L, "rd_%s_wait" % self._name), getattr(L, "rd_%s_destroy" % self._name)
-        self.h = getattr(L, "rd_%s_create" % self._name)(*args)
+        self.h = getattr(L, "rd_%s_%s" % (self._name, ctor))(*args)
         if not self.h:
-            raise ValueError("rd_%s_create: invalid arguments (%r)" % (self._name, args))
+            raise ValueError("rd_%s_%s: invalid arguments (%r)" % (self._name, ctor, args))
 
     def _wait(self, nstatus=None):
         """blocks until the oldest job is done: its number of items, or with nstatus - the most a job takes - their status bytes"""
@@ -681,13 +696,75 @@ class _Service:
             self.h = None
 
 
+def tensor_spec(dtype, layout, channels, oversample=1, scale=(1, 1, 1), bias=(0, 0, 0)):
+    """an rd_tensor_spec as a TENSOR_SPEC_DTYPE record: dtype TENSOR_U8 / F16 / BF16 / F32, layout TENSOR_NHWC / NCHW, channels TENSOR_BGR / RGB / GRAY, oversample 1, 2
+    or 4, scale and bias per OUTPUT channel (a number: the same for all).  Whether it is legal is decided where it is used (tensor_spec_ok, Rectifier)."""
+    s = np.zeros((), TENSOR_SPEC_DTYPE)
+    s["dtype"], s["layout"], s["channels"], s["oversample"] = dtype, layout, channels, oversample
+    s["scale"], s["bias"] = np.broadcast_to(np.asarray(scale, np.float32), (3,)), np.broadcast_to(np.asarray(bias, np.float32), (3,))
+    return s
+
+
+def _spec_arg(spec):
+    return np.ascontiguousarray(spec, dtype=TENSOR_SPEC_DTYPE).reshape(())
+
+
+def tensor_spec_ok(spec, pw, ph):
+    """whether a spec is legal for pw x ph outputs (rd_tensor_spec_ok); runs without a GPU"""
+    return bool(lib().rd_tensor_spec_ok(_spec_arg(spec).ctypes.data, int(pw), int(ph)))
+
+
+def tensor_bytes(spec, pw, ph):
+    """the bytes of one quad's tensor, 0 for a spec that is not legal (rd_tensor_bytes); runs without a GPU"""
+    return int(lib().rd_tensor_bytes(_spec_arg(spec).ctypes.data, int(pw), int(ph)))
+
+
+def tensor_element(spec, c, S):
+    """the bytes of one element of channel c from its box sum S (rd_tensor_element: step 4 of the contract); runs without a GPU"""
+    out = np.zeros(4, np.uint8)
+    n = lib().rd_tensor_element(_spec_arg(spec).ctypes.data, int(c), int(S), out.ctypes.data)
+    if n <= 0:
+        raise ValueError("rd_tensor_element: invalid arguments (spec %r, channel %r)" % (spec, c))
+    return out[:n].tobytes()
+
+
+def tensor_limits():
+    """{"dtypes", "layouts", "channels", "oversamplings"}: the legal values of a spec's fields (rd_tensor_limits); runs without a GPU"""
+    a = np.zeros(4, np.int32)
+    lib().rd_tensor_limits(a.ctypes.data)
+    bits = lambda v: tuple(k for k in range(31) if v >> k & 1)
+    return {"dtypes": bits(int(a[0])), "layouts": bits(int(a[1])), "channels": bits(int(a[2])), "oversamplings": tuple(1 << k for k in bits(int(a[3])))}
+
+
 class Rectifier(_Service):
-    """The rd_rectifier extension: pw x ph BGR patches of up to max_quads quads per job, njobs jobs in flight (the contract: include/rectdetect_hip.h)."""
+    """The rd_rectifier extension: pw x ph BGR patches of up to max_quads quads per job, njobs jobs in flight (the contract: include/rectdetect_hip.h).  With
+    tensor=tensor_spec(...) a job writes model-ready tensors instead ("model-ready tensors" there): `out` then holds n * patch_bytes bytes of shape(n) and dtype."""
     _name = "rectifier"
 
-    def __init__(self, pw, ph, max_quads=64, njobs=2, device=0):
+    def __init__(self, pw, ph, max_quads=64, njobs=2, device=0, tensor=None):
         self.pw, self.ph, self.max_quads, self.njobs = pw, ph, max_quads, njobs
-        self._create(device, pw, ph, max_quads, njobs)
+        self.tensor = None if tensor is None else _spec_arg(tensor).copy()
+        if self.tensor is None:
+            self._create(device, pw, ph, max_quads, njobs)
+        else:
+            self._create(device, pw, ph, max_quads, njobs, self.tensor.ctypes.data, ctor="create_tensor")
+
+    @property
+    def patch_bytes(self):
+        """the bytes of one quad's output (rd_rectifier_patch_bytes)"""
+        return int(lib().rd_rectifier_patch_bytes(self.h))
+
+    @property
+    def dtype(self):
+        """the numpy dtype of an element; bfloat16 is reported as its bits, uint16"""
+        return TENSOR_NUMPY[int(self.tensor["dtype"])] if self.tensor is not None else np.dtype(np.uint8)
+
+    def shape(self, n):
+        """the shape of a job of n quads: (n, ph, pw, C) or, under TENSOR_NCHW, (n, C, ph, pw)"""
+        if self.tensor is None:
+            return (n, self.ph, self.pw, 3)
+        C = 1 if int(self.tensor["channels"]) == TENSOR_GRAY else 3
+        return (n, C, self.ph, self.pw) if int(self.tensor["layout"]) == TENSOR_NCHW else (n, self.ph, self.pw, C)
 
     def enqueue(self, fmt, planes, pitches, iw, ih, quads, out, on_device=False, pinned=False, out_pinned=False):
         """one job: patches of `quads` (n x 8 or n x 4 x 2 doubles, patch order) from an iw x ih frame in format fmt (PIX_*) into `out`, the ADDRESS of device memory or,
@@ -705,11 +782,13 @@ class Rectifier(_Service):
         return self._wait(self.max_quads)
 
     def rectify(self, frame_bgr, quads):
-        """convenience: the (n, ph, pw, 3) patches of `quads` from a numpy BGR image, through pinned memory (one job, waited for)"""
+        """convenience: the (n, ph, pw, 3) patches - with a tensor spec: the array of shape(n) and dtype - of `quads` from a numpy BGR image, through pinned memory
+        (one job, waited for)"""
         a = np.asarray(frame_bgr, dtype=np.uint8)
         q, n = _quads_arg(quads)
-        got = self._through_pinned(max(n, 1) * self.ph * self.pw * 3, lambda p: self.enqueue(PIX_BGR, a, None, a.shape[1], a.shape[0], q, p, out_pinned=True))
-        return got[:n * self.ph * self.pw * 3].reshape(n, self.ph, self.pw, 3)
+        pb = self.patch_bytes
+        got = self._through_pinned(max(n, 1) * pb, lambda p: self.enqueue(PIX_BGR, a, None, a.shape[1], a.shape[0], q, p, out_pinned=True))
+        return got[:n * pb].view(self.dtype).reshape(self.shape(n))
 
 
 def annot_limits():

@@ -164,6 +164,11 @@ struct RectifyQuad { double c[8]; int status; int pad; };
 // n patches of pw x ph BGR pixels, patch k at out + k * pw * ph * 3, from one frame in format fmt (RD_PIX_*), one launch (quad = blockIdx.z)
 void rectify(hipStream_t s, uint8_t *out, int fmt, const rdpix::PixFrame &src, const RectifyQuad *quads, int n, int pw, int ph);
 
+// ---- rd_k_tensor.hip: model-ready tensors (the contract: rectdetect_hip.h, "model-ready tensors")
+// n tensors of pw x ph elements in the dtype, layout and channels of spec (legal for pw x ph: rd_tensor_spec_ok), quad k's at out + k * rd_tensor_bytes(spec, pw, ph),
+// from one frame in format fmt (RD_PIX_*), one launch (quad = blockIdx.z)
+void rectify_tensor(hipStream_t s, void *out, int fmt, const rdpix::PixFrame &src, const RectifyQuad *quads, int n, int pw, int ph, const rd_tensor_spec &spec);
+
 // ---- rd_k_match.hip: matched quads (the contract: rectdetect_hip.h, "matched quads")
 // the signatures of n quads of one frame: quad k's G * G int8 values at sig + k * G * G (zeros for an invalid quad), its sa, saa ADDED to sums[2k], sums[2k+1]
 // (cleared by the caller); G in {8, 16, 32, 64}, m in {1, 2, 4}

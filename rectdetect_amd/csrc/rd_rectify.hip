@@ -1,5 +1,5 @@
 // rectdetect-mi355x: the rectifier - rectified patches of quads behind the detector's poll (the contract: include/rectdetect_hip.h, "rectified patches";
-// the kernel: rd_k_rectify.hip; the jobs in flight, the frame's checks and its way to the device: rd_jobs.h).
+// the kernels: rd_k_rectify.hip and, for a rectifier made with a tensor spec, rd_k_tensor.hip ("model-ready tensors"); the jobs in flight, the frame's checks and its way to the device: rd_jobs.h).
 #include "rd_jobs.h"
 #include "rd_kernels.h"
 #include <math.h>
@@ -10,7 +10,9 @@ using namespace rdjob;
 struct rd_rectifier {
   Ring ring;                                // (first: rd_jobs.h)
   int pw, ph;
-  size_t patch_bytes;
+  size_t patch_bytes;                       // of one quad's output: pw * ph * 3, or rd_tensor_bytes of the spec
+  int tensor;                               // made by rd_rectifier_create_tensor: jobs launch rdk::rectify_tensor with `spec`
+  rd_tensor_spec spec;
   rdk::RectifyQuad *d_quads, *h_quads;      // njobs blocks of max_quads each, a job's at slot * max_quads: pinned staging and their place in the device array
   uint8_t **d_out;                          // per slot: max_quads patches on their way to pinned host memory (allocated on first use)
   DevBuf frame;                             // host and pinned frames travel through here
@@ -58,18 +60,29 @@ void rd_rectify_coefficients(const double quad[8], double coef[8], int *status) 
   if (status) *status = 1;
 }
 
-rd_rectifier *rd_rectifier_create(int device, int pw, int ph, int max_quads, int njobs) {
+// spec == NULL: the classic rectifier
+static rd_rectifier *rectifier_create(int device, int pw, int ph, int max_quads, int njobs, const rd_tensor_spec *spec) {
   if (pw < 1 || ph < 1 || pw > 16384 || ph > 16384 || max_quads < 1 || max_quads > 65535 || !ring_args_ok(device, njobs)) return NULL;
+  if (spec && !rd_tensor_spec_ok(spec, pw, ph)) return NULL;
   rd_rectifier *r = (rd_rectifier *)calloc(1, sizeof(*r));
   ring_create(&r->ring, RD_MAGIC_RECTIFIER, device, max_quads, njobs);
   r->pw = pw; r->ph = ph;
-  r->patch_bytes = (size_t)pw * ph * 3;
+  r->patch_bytes = spec ? rd_tensor_bytes(spec, pw, ph) : (size_t)pw * ph * 3;
+  if (spec) { r->tensor = 1; r->spec = *spec; }
   const size_t nq = (size_t)njobs * max_quads;
   RD_HIP(hipMalloc((void **)&r->d_quads, nq * sizeof(rdk::RectifyQuad)));
   RD_HIP(hipHostMalloc((void **)&r->h_quads, nq * sizeof(rdk::RectifyQuad), hipHostMallocDefault));
   r->d_out = (uint8_t **)calloc(njobs, sizeof(uint8_t *));
   return r;
 }
+
+rd_rectifier *rd_rectifier_create(int device, int pw, int ph, int max_quads, int njobs) { return rectifier_create(device, pw, ph, max_quads, njobs, NULL); }
+
+rd_rectifier *rd_rectifier_create_tensor(int device, int pw, int ph, int max_quads, int njobs, const rd_tensor_spec *spec) {
+  return spec ? rectifier_create(device, pw, ph, max_quads, njobs, spec) : NULL;
+}
+
+size_t rd_rectifier_patch_bytes(const rd_rectifier *r) { return r ? r->patch_bytes : 0; }
 
 void rd_rectifier_destroy(rd_rectifier *r) {
   if (!r) return;
@@ -115,7 +128,8 @@ long rd_rectifier_enqueue(rd_rectifier *r, int format, const void *const planes[
       if (!r->d_out[slot]) RD_HIP(hipMalloc((void **)&r->d_out[slot], (size_t)g->per_job * r->patch_bytes));      // (on first use: a rectifier that writes to device memory only has none)
       dst = r->d_out[slot];
     }
-    rdk::rectify(g->st, dst, format, src, d_quads, n, r->pw, r->ph);
+    if (r->tensor) rdk::rectify_tensor(g->st, dst, format, src, d_quads, n, r->pw, r->ph, r->spec);
+    else rdk::rectify(g->st, dst, format, src, d_quads, n, r->pw, r->ph);
     rdrt::check_launch("rectified patches");
     if (out_kind == RD_FRAME_HOST_PINNED) RD_HIP(hipMemcpyAsync(out, dst, (size_t)n * r->patch_bytes, hipMemcpyDeviceToHost, g->st));
   }
