@@ -128,23 +128,36 @@ void rd_detector_drain(rd_detector *d);
 /* copy of the line-segment list of the most recently POLLED frame: returns n (records 1..n), writes up to max records */
 int rd_detector_last_segments(rd_detector *d, void *dst, int max_records);
 
-/* counters since creation: which 0 = frames whose polyline stage did not fit the single-launch kernel's on-chip tables and
- * was repeated with the multi-launch path (same results, slower); 1 = device microseconds summed over the polled frames
- * (HIP events on the frame's stream: first kernel start to last copy end, so concurrent frames overlap); 2 = frames in that sum; 3 = host microseconds spent inside rd_detector_enqueue;
- * 4 = frames whose region merge had not settled within their launch budget and were repeated with more launches (32, then 64, then 128); 6 = frames still changing after 128 (none so far);
- * 5 = the current launch budget of the region merge (8, 10, .. 20); 20..26 = frames launched with a budget of 8 / 10 / .. / 20; 40 + k = frames whose merge needed k launches;
- * 10 = frames with more line segments than a slot's probe buffer holds (65535), whose probes were taken again into a larger buffer (the list keeps the
- * reference's capacity of 16N / 56 records; nothing is dropped); 11 / 12 = frames whose rectangles came from the device post-process (RD_DEVICE_POST=1:
- * candidate funnel + pose estimation in rd_k_post.hip) / from the host post-process; 13 = microseconds the worker threads spent in the
- * host post-process (sum over frames); 14 = frames whose small-region absorption (oclrect.cl:348-371) was finished by the slow path -
- * rounds over work lists until nothing changes - because they left more undecided pixels than the single-block tail holds (frames made of small regions);
- * 15 = frames per group launch; 16 / 17 = groups whose strong masks took one launch / one launch per frame; 18 = frames that travelled straight from the caller's pinned
- * memory (RD_FRAME_HOST_PINNED), 19 = host frames copied into the detector's own pinned staging first (RD_FRAME_HOST);
- * 30 = polyline kind: frames whose segment list was longer than the block handed to pinned host memory at the end of the frame and was fetched by the poll;
- * 31 = device bytes of one slot's planes (both kinds; the polyline stage's compact scratch, the same for both, not included); 32 = records of that block (header included);
- * 33 = device bytes of the scaled-source staging a slot owns once it has taken a host or pinned frame at scale 2 (rd_detector_enqueue_scaled; as many bytes again of
- * pinned host memory go with it), 0 until a slot has - counter 31 does not include them.
- * The polyline kind keeps 0, 1, 2, 3, 15, 18, 19 as above (0: frames repeated in multi-launch form); the region, post-process and strong-mask counters stay 0 there. */
+/* Counters since creation (`which`; the numbers are part of the ABI); -1 for a number that is none of them.
+ * The polyline kind keeps 0, 1, 2, 3, 15, 18, 19 and 30..33; the region, post-process and strong-mask counters stay 0 there. */
+enum rd_counter {
+  RD_CTR_POLY_REDONE = 0,            /* frames whose polyline stage did not fit the single-launch kernel's on-chip tables and was repeated with the multi-launch path (same results, slower) */
+  RD_CTR_DEVICE_US = 1,              /* device microseconds summed over the polled frames (HIP events on the frame's stream: first kernel start to last copy end, so concurrent frames overlap) */
+  RD_CTR_DEVICE_FRAMES = 2,          /* frames in that sum */
+  RD_CTR_ENQUEUE_US = 3,             /* host microseconds spent inside rd_detector_enqueue */
+  RD_CTR_REGION_REDONE = 4,          /* frames whose region merge had not settled within their launch budget and were repeated with more launches (32, then 64, then 128) */
+  RD_CTR_REGION_BUDGET = 5,          /* the current launch budget of the region merge (8, 10, .. 20) */
+  RD_CTR_REGION_UNSETTLED = 6,       /* frames still changing after 128 launches (none so far) */
+  RD_CTR_PROBES_REGROWN = 10,        /* frames with more line segments than a slot's probe buffer holds (65535), whose probes were taken again into a larger buffer (the list keeps
+                                        the reference's capacity of 16N / 56 records; nothing is dropped) */
+  RD_CTR_POST_DEVICE = 11,           /* frames whose rectangles came from the device post-process (RD_DEVICE_POST=1: candidate funnel + pose estimation in rd_k_post.hip) */
+  RD_CTR_POST_HOST = 12,             /* frames whose rectangles came from the host post-process */
+  RD_CTR_POST_HOST_US = 13,          /* microseconds the worker threads spent in the host post-process (sum over frames) */
+  RD_CTR_ABSORB_SLOW = 14,           /* frames whose small-region absorption (oclrect.cl:348-371) was finished by the slow path - rounds over work lists until nothing changes -
+                                        because they left more undecided pixels than the single-block tail holds (frames made of small regions) */
+  RD_CTR_FRAMES_PER_LAUNCH = 15,     /* frames per group launch (1: every frame its own launches) */
+  RD_CTR_STRONG_ONE_LAUNCH = 16,     /* groups whose strong masks took one launch */
+  RD_CTR_STRONG_BY_FRAME = 17,       /* groups whose strong masks took one launch per frame */
+  RD_CTR_FRAMES_PINNED = 18,         /* frames that travelled straight from the caller's pinned memory (RD_FRAME_HOST_PINNED) */
+  RD_CTR_FRAMES_COPIED = 19,         /* host frames copied into the detector's own pinned staging first (RD_FRAME_HOST) */
+  RD_CTR_BUDGET_FRAMES = 20,         /* 20..26: frames launched with a budget of 8 / 10 / .. / 20 launches of the region merge */
+  RD_CTR_LONG_LISTS = 30,            /* polyline kind: frames whose segment list was longer than the block handed to pinned host memory at the end of the frame and was fetched by the poll */
+  RD_CTR_SLOT_BYTES = 31,            /* device bytes of one slot's planes (both kinds; the polyline stage's compact scratch, the same for both, not included) */
+  RD_CTR_HANDOFF_RECORDS = 32,       /* records of the block handed to pinned host memory at the end of a frame (header included) */
+  RD_CTR_SCALED_STAGING_BYTES = 33,  /* device bytes of the scaled-source staging a slot owns once it has taken a host or pinned frame at scale 2 (rd_detector_enqueue_scaled; as many
+                                        bytes again of pinned host memory go with it), 0 until a slot has - RD_CTR_SLOT_BYTES does not include them */
+  RD_CTR_NEED_FRAMES = 40            /* 40 + k, k = 0..20: frames whose region merge needed k launches (the one that changes nothing included; 20: or more) */
+};
 long rd_detector_counter(rd_detector *d, int which);
 
 /* ---- Environment.  Everything is read when a detector is created (rd_detector_create / init_oclrect) and never again; an empty value counts as unset.
@@ -165,7 +178,7 @@ long rd_detector_counter(rd_detector *d, int which);
  * Switches of experiments that were measured and not kept exist only in tuning builds (-DRD_TUNING, tools/variants.sh). */
 
 /* Test hook: copy an internal plane of the most recently completed frame to host memory.  Returns bytes written,
- * 0 for an unknown name or a name of the other kind.  Both kinds are served from one table (rd_api.hip).
+ * 0 for an unknown name or a name of the other kind.  Both kinds are served from one table (rd_detector.hip).
  * Rectangle kind: plab0 plab1 lblur vxy strength nms mask0 tidy label1 strsum edge500 smooth quant strong junction mergemask
  * region0 (merged regions) rsize region (after absorbing small ones) boundarysrc boundary lsid table lslist (the segment list, 16 bytes per pixel)
  * polyctr (64 counters of the polyline stage) iirflags (16 ints) d2work (16 ints) absorb (8 status words of the absorption);

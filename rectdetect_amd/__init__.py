@@ -52,6 +52,9 @@ ANNOT_SEG_ALL, ANNOT_SEG_CHAINS = 0, 1
 PIX_BGR, PIX_RGB, PIX_BGRA, PIX_RGBA, PIX_NV12, PIX_I420 = range(6)
 PIX_NAMES = {PIX_BGR: "BGR", PIX_RGB: "RGB", PIX_BGRA: "BGRA", PIX_RGBA: "RGBA", PIX_NV12: "NV12", PIX_I420: "I420"}
 
+# counters of rd_detector_counter this module reads (enum rd_counter of include/rectdetect_hip.h says what each counts)
+CTR_POLY_REDONE, CTR_DEVICE_US, CTR_DEVICE_FRAMES, CTR_REGION_REDONE, CTR_REGION_BUDGET, CTR_ABSORB_SLOW, CTR_FRAMES_PER_LAUNCH = 0, 1, 2, 4, 5, 14, 15
+
 CL_MEM_READ_WRITE = 1 << 0
 CL_MEM_COPY_HOST_PTR = 1 << 5
 CL_TRUE = 1
@@ -529,26 +532,26 @@ class Detector(_PolledJobs):
 
     def redone_frames(self):
         """frames whose polyline stage overflowed the single-launch kernel and was repeated the long way"""
-        return lib().rd_detector_counter(self.h, 0)
+        return lib().rd_detector_counter(self.h, CTR_POLY_REDONE)
 
     def frames_per_launch(self):
-        """frames that share one set of launches (group launches, rd_detector_counter 15)"""
-        return lib().rd_detector_counter(self.h, 15)
+        """frames that share one set of launches (group launches, RD_CTR_FRAMES_PER_LAUNCH)"""
+        return lib().rd_detector_counter(self.h, CTR_FRAMES_PER_LAUNCH)
 
     def region_round_budget(self):
         """(current region-merge round budget, frames repeated with the full budget because theirs was too small)"""
-        return lib().rd_detector_counter(self.h, 5), lib().rd_detector_counter(self.h, 4)
+        return lib().rd_detector_counter(self.h, CTR_REGION_BUDGET), lib().rd_detector_counter(self.h, CTR_REGION_REDONE)
 
     def absorption(self):
         """(undecided pixels the tile kernel of the small-region absorption left to the single-block tail, sweeps the tail took) for the last
-        polled frame, and how many frames so far were finished by the slow path (rd_detector_counter 14)"""
+        polled frame, and how many frames so far were finished by the slow path (RD_CTR_ABSORB_SLOW)"""
         w = self.plane("absorb", np.int32, 8)
         self.absorb_trace = {"steps": int(w[3]), "us_gather": w[4] / 100.0, "us_sweeps": w[5] / 100.0, "us_choose": w[6] / 100.0, "us_pointers": w[7] / 100.0}
-        return int(w[1]), int(w[2]), lib().rd_detector_counter(self.h, 14)
+        return int(w[1]), int(w[2]), lib().rd_detector_counter(self.h, CTR_ABSORB_SLOW)
 
     def device_time(self):
         """(summed device microseconds of the polled frames measured with HIP events, number of frames)"""
-        return lib().rd_detector_counter(self.h, 1), lib().rd_detector_counter(self.h, 2)
+        return lib().rd_detector_counter(self.h, CTR_DEVICE_US), lib().rd_detector_counter(self.h, CTR_DEVICE_FRAMES)
 
     def last_segments(self):
         n = lib().rd_detector_last_segments(self.h, None, 0)

@@ -1,4 +1,4 @@
-// rectdetect-mi355x: composited quads - what the kernel (rd_k_composite.hip), the runtime (rd_composite.hip) and the entry point behind the poll (rd_api.hip) share.
+// rectdetect-mi355x: composited quads - what the kernel (rd_k_composite.hip), the runtime (rd_composite.hip) and the entry point behind the poll (rd_frames.hip) share.
 // The records and the host's arithmetic: rd_comp_host.h.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -113,7 +113,7 @@ template <typename T>
 __device__ __forceinline__ const T &atu(const T *base, unsigned idx) { return *(const T *)((const char *)base + idx * (unsigned)sizeof(T)); }
 
 // Frames batched per launch (small frames): frame z of a group launch works on planes that lie z * zs bytes behind the ones the launch
-// was given (all planes of a frame slot are carved out of one allocation at the same offsets, rd_api.hip: slot_planes).  A kernel of the
+// was given (all planes of a frame slot are carved out of one allocation at the same offsets, rd_detector.hip: slot_planes).  A kernel of the
 // frame path starts with  RD_ZSHIFT(zs, out, in, ...)  on its plane pointers (null pointers - optional planes - stay null); with
 // gridDim.z == 1 or zs == 0 nothing moves.  Scalar arithmetic: the offset is the same for all lanes.
 template <typename T> __device__ __forceinline__ T *rd_zs_ptr(T *p, size_t off) { return p ? (T *)((char *)p + off) : p; }

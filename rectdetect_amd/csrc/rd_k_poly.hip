@@ -1174,18 +1174,18 @@ __global__ void k_scatter_ids(const rdk::PolyFrames FRS) {
   SPARSE_LOOP(j, nlive) { const int i = s.live[j]; ids[s.pos[i]] = s.id[i]; }
 }
 
-// Result hand-off of the poly kind: the frame's counters ([0, 32): ctr[25] = the single-block kernel gave up) and the first `records` records of its list -
-// header included - written straight into the slot's pinned host block (FRM.pack, device address of pinned host memory) at [64, 64 + 14 * records): the
+// Result hand-off of the poly kind: the frame's counters (RD_PACK_POLYCTR_INTS of them: ctr[RD_PACK_GAVE_UP] = the single-block kernel gave up) and the first `records`
+// records of its list - header included - written straight into the slot's pinned host block (FRM.pack, device address of pinned host memory) from RD_PACK_RECORDS on: the
 // poll finds them there without a copy launch.  Longer lists are fetched by the poll from FRM.lslist.
 __global__ __launch_bounds__(256) void k_poly_handoff(const rdk::PolyFrames FRS, int records) {
   RD_FRAME;
   const int *__restrict__ ls = (const int *)FRM.lslist;
   int *__restrict__ pack = FRM.pack;
   const int n = ls[0];
-  const int m = (n + 1 < records ? n + 1 : records) * 14;
+  const int m = (n + 1 < records ? n + 1 : records) * RD_REC_INTS;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < 32) pack[t] = s.ctr[t];
-  for (int i = t; i < m; i += gridDim.x * blockDim.x) pack[64 + i] = ls[i];
+  if (t < RD_PACK_POLYCTR_INTS) pack[t] = s.ctr[t];
+  for (int i = t; i < m; i += gridDim.x * blockDim.x) pack[RD_PACK_RECORDS + i] = ls[i];
 }
 
 template <typename T> T *dalloc(size_t n) { void *p = nullptr; if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) return nullptr; return (T *)p; }

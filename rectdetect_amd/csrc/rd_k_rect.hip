@@ -1960,8 +1960,8 @@ __global__ __launch_bounds__(256) void k_reduce_box(const rdk::PolyFrames FRS, i
 // host instead of the 4N-byte plane and the 16N-byte table.  Double precision, same operation order as the host code.
 struct ls_rec { float x0, y0, x1, y1; int startIndex, endIndex, leftPtr, rightPtr, startCount, endCount, maxDist, polyid, npix, level; };
 
-// The kernel also assembles the block that travels to the host in ONE copy (pack): [0,32) polyline counters, [32,52) region
-// round flags, [52,60) absorption status, [64, 64 + 14 * pack_records) segment records 0.., then 90 ints of probes per record.
+// The kernel also assembles the block that travels to the host in ONE copy (pack; its layout: rd_kernels.h, RD_PACK_*): polyline counters, region
+// round flags, absorption status, segment records 0 .. pack_records - 1, then RD_PROBE_INTS ints of probes per record.
 __global__ void k_sample_segments(const rdk::PolyFrames FRS, int max_records, int iw, int ih, int nentry, int pack_records) {
   RD_VFRAME;
   int *__restrict__ out = FRM.probes;
@@ -1974,16 +1974,16 @@ __global__ void k_sample_segments(const rdk::PolyFrames FRS, int max_records, in
   const int n = *(const int *)ls;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (pack) {
-    if (t < 32) pack[t] = polyctr[t];
-    else if (t < 52) pack[t] = rflags[t - 32];        // (the flags of the first 20 launches of the region merge)
-    else if (t < 60) pack[t] = rflags[RD_REGION_STATUS_AT + t - 52];   // (the status words of the absorption)
-    if (t < 14) pack[64 + t] = ((const int *)ls)[t];        // header record
+    if (t < RD_PACK_FLAGS) pack[t] = polyctr[t];
+    else if (t < RD_PACK_STATUS) pack[t] = rflags[t - RD_PACK_FLAGS];        // (the flags of the first 20 launches of the region merge)
+    else if (t < RD_PACK_STATUS + RD_PACK_STATUS_INTS) pack[t] = rflags[RD_REGION_STATUS_AT + t - RD_PACK_STATUS];   // (the status words of the absorption)
+    if (t < RD_REC_INTS) pack[RD_PACK_RECORDS + t] = ((const int *)ls)[t];        // header record
   }
   const int i = t / 15 + 1, k = t % 15;
   if (i > n || i >= max_records) return;
   int *o = out + (size_t)(i * 15 + k) * 6;
   const bool packed = pack && i < pack_records;
-  if (packed && k < 14) pack[64 + i * 14 + k] = ((const int *)ls)[i * 14 + k];   // the record itself (14 ints), one int per probe thread
+  if (packed && k < RD_REC_INTS) pack[RD_PACK_RECORDS + i * RD_REC_INTS + k] = ((const int *)ls)[i * RD_REC_INTS + k];   // the record itself, one int per probe thread
   int segid = 0;
   if (ls[i].polyid != 0) {
     int sx, sy;
@@ -1998,7 +1998,7 @@ __global__ void k_sample_segments(const rdk::PolyFrames FRS, int max_records, in
 #pragma unroll
   for (int q = 0; q < 6; q++) o[q] = v[q];
   if (packed) {
-    int *po = pack + 64 + pack_records * 14 + (size_t)(i * 15 + k) * 6;
+    int *po = pack + RD_PACK_RECORDS + pack_records * RD_REC_INTS + (size_t)(i * 15 + k) * 6;
 #pragma unroll
     for (int q = 0; q < 6; q++) po[q] = v[q];
   }

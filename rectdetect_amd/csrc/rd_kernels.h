@@ -8,7 +8,7 @@
 #include "rd_pix.h"
 #include "rectdetect_hip.h"
 
-// Group launches (small frames, rd_api.hip): launchers of the frame path take `nz` frames per launch and `zs`, the byte pitch between the planes
+// Group launches (small frames, rd_frames.hip): launchers of the frame path take `nz` frames per launch and `zs`, the byte pitch between the planes
 // of consecutive frame slots (rd_device.h: RD_ZSHIFT); the defaults launch one frame.
 #define RD_ZB_MAX 8
 
@@ -125,7 +125,7 @@ int despeckle2_slow(hipStream_t s, int *out, const int *in, int *scratch, const 
 // launches of the rounds after which despeckle2_slow() calls a frame without a fixed point an internal error (a dependency chain moves at least one pixel right or
 // one row down per link: iw + 2 * ih bounds its length, and every launch settles two links)
 static inline int despeckle2_slow_bound(int iw, int ih) { return iw + 2 * ih + 16; }
-#define RD_REGION_FIRST_BUDGET 20      // the largest budget a frame is launched with (rd_api.hip: kRoundBudgets); a frame still changing in its last launch climbs the ladder (region_ladder)
+#define RD_REGION_FIRST_BUDGET 20      // the largest budget a frame is launched with (rd_frames.hip: kRoundBudgets); a frame still changing in its last launch climbs the ladder (region_ladder)
 // the budget after `budget` on that ladder: 32, then doubled up to the definition's limit; 0: there is none
 static inline int region_ladder_next(int budget) { const int b = budget < 32 ? 32 : budget * 2; return b <= RD_REGION_MAX_LAUNCHES ? b : 0; }
 #define RD_ABSORB_THRE 16              // regions of at most this many pixels (junction counts included: quirk H2) are absorbed (oclrect.c:337)
@@ -136,8 +136,21 @@ struct PolyFrame;      // rd_poly_scratch.h: per-frame descriptor of the sparse 
 void reduce_ls_init(hipStream_t s, int *table, int *claim, int *tlist, int nentry);   // once per allocation
 // votes of the chain pixels left in each frame's scratch by the last polyline() call (their final segment ids) into frames[z].table
 void reduce_ls(hipStream_t s, const PolyFrame *frames, int nb, int iw, int ih, int nentry, int tables_are_clean = 0);   // tables_are_clean: label8_boundary(vt_*) has undone the previous use already
+// The hand-over block: what the host needs from a frame, written by the frame's last kernel (k_sample_segments; the polyline kind's k_poly_handoff) straight into the
+// slot's pinned host memory (PolyFrame::pack) and read there by the poll.  Ints:
+#define RD_PACK_POLYCTR 0              // [0, 32): the polyline stage's counters 0..31 (poly_scratch_counters)
+#define RD_PACK_POLYCTR_INTS 32
+#define RD_PACK_GAVE_UP 25             //   of them: != 0, the single-block polyline kernel gave up on the frame (its on-chip tables are too small)
+#define RD_PACK_FLAGS 32               // [32, 52): the region merge's flags of its first RD_REGION_FIRST_BUDGET launches (!= 0: that launch changed something)
+#define RD_PACK_STATUS 52              // [52, 60): the absorption's status words ([0] != 0: the fast path gave up)
+#define RD_PACK_STATUS_INTS 8
+#define RD_PACK_RECORDS 64             // the segment list from its header record on, RD_REC_INTS ints per record (linesegment_t, 56 bytes)
+#define RD_REC_INTS 14
+#define RD_PROBE_INTS (15 * 6)         // behind the block's records: the probes, this many ints per record (15 probe points of 6 values)
+static_assert(RD_PACK_FLAGS == RD_PACK_POLYCTR + RD_PACK_POLYCTR_INTS && RD_PACK_STATUS == RD_PACK_FLAGS + RD_REGION_FIRST_BUDGET && RD_PACK_STATUS + RD_PACK_STATUS_INTS <= RD_PACK_RECORDS,
+              "the hand-over block's parts lie back to back in front of the records");
 // per segment, 15 probe points: {boundary id, table slot owner, 4 box values} -> out[(seg*15 + k)*6 ..]
-// pack (may be null): the block for the host in one piece - 64 ints of counters / flags, pack_records records of 14 ints, then their probes
+// pack (may be null): the hand-over block - counters / flags, pack_records records, then their probes
 void sample_segments(hipStream_t s, const PolyFrame *frames, int nb, int max_records, int iw, int ih, int nentry, int pack_records);
 
 // ---- rd_k_post.hip: segments + probes -> rectangles on the device (candidate funnel + pose estimation, one wave per candidate)

@@ -504,7 +504,7 @@ def test_reference_api_on_page_locked_buffers_keeps_the_copy_contract(ctx):
 
 
 def ctypes_cast_detector(rect_detector):
-    """the rd_detector behind an oclrect_t (struct oclrect_t { uint32_t magic; rd_detector *det; ... }, rd_api.hip): for its counters"""
+    """the rd_detector behind an oclrect_t (struct oclrect_t { uint32_t magic; rd_detector *det; ... }, rd_detector.hip): for its counters"""
     import ctypes
     return ctypes.cast(rect_detector.h + 8, ctypes.POINTER(ctypes.c_void_p))[0]
 
@@ -1784,7 +1784,7 @@ def test_builtin_sensitivity_report():
         assert "baseline" in same or order_dependent, f"frame {fi}: the HIP path shares the baseline's builtin definitions and must return its list"
 
 
-# ---- the slots' planes: one list (rd_api.hip: kSlotPlanes), one allocation per detector, one table of debug planes
+# ---- the slots' planes: one list (rd_detector.hip: kSlotPlanes), one allocation per detector, one table of debug planes
 # device bytes of one slot (counter 31) as commit 1a1e500 returns them (its library, run once on the GPU) - the commit before the plane list became one table, which must not
 # add, drop, resize or re-round a plane
 SLOT_BYTES = {("rect", 16, 16): 89856, ("rect", 65, 55): 1178112, ("rect", 64, 54): 1136384, ("rect", 333, 217): 23737856, ("rect", 1920, 1080): 489198592,
