@@ -465,19 +465,23 @@ template <int SRC16, typename T> __device__ __forceinline__ float iir_field(T v,
   if (SRC16) return (float)(int)v * sc + hf;
   return (float)v;
 }
+// k_iir_fused_edge: the blocks of a column that k_iir_fused (below) does not take, from block `nf` on - the last block of a column whose height is no multiple of
+// IF_ROWS (8 .. IF_ROWS + 7 rows), and the only block of a plane shorter than IF_ROWS.  The general form: any row count, mirrored rows, a run-in that starts at the
+// line's true beginning.  Its rows are run-time values, so what a wave parks is indexed at run time and lives in LDS: the whole block's tile, which is what keeps
+// this form at two waves per SIMD with 128-row blocks.  A launch of its own, after k_iir_fused.
 template <int TOUT, int IF_ROWS, int SRC16>
-__global__ __launch_bounds__(128) void k_iir_fused(P3 dst, P3c src, float *__restrict__ tails, int W, int H, int nchunks, int *bad, int np, size_t zs) {
+__global__ __launch_bounds__(128) void k_iir_fused_edge(P3 dst, P3c src, float *__restrict__ tails, int W, int H, int nchunks, int nf, int *bad, int np, size_t zs) {
   __shared__ float fwt[(IF_ROWS + 8) * IF_PITCH];
   const int lane = threadIdx.x & 63, anti = threadIdx.x >> 6;
-  // (grid: x = 64-column strips, y = plane + np * frame of a group launch, z = blocks of rows)
-  const int k = blockIdx.y % np, c = blockIdx.z;
+  // (grid: x = 64-column strips, y = plane + np * frame of a group launch, z = block of rows - nf)
+  const int k = blockIdx.y % np, c = nf + (int)blockIdx.z;
   // The plane's pointers picked by comparisons, not by indexing the structs: an index that is not a constant sends the struct through memory, the pointers come
   // back without their address space and every access becomes a flat instruction with a 64-bit address per lane.  Rows are then addressed as a UNIFORM row pointer
   // (scalar registers, advanced by scalar additions) plus the lane's 32-bit byte offset - no vector instruction per access.
   float *dk = k == 0 ? dst.p[0] : (k == 1 ? dst.p[1] : dst.p[2]);
   const float *sk = k == 0 ? src.p[0] : (k == 1 ? src.p[1] : src.p[2]);
   { const size_t rd_zoff_ = (size_t)(blockIdx.y / np) * zs; RD_ZS1(dk); RD_ZS1(sk); RD_ZS1(tails); RD_ZS1(bad); }
-  if (blockIdx.x == 0 && k == 0 && blockIdx.z == 0 && threadIdx.x == 0) *bad = 0;      // diagnostics flag of the check that follows this launch
+  if (blockIdx.x == 0 && k == 0 && c == 0 && threadIdx.x == 0) *bad = 0;      // diagnostics flag of the check that follows this launch
   const int x = blockIdx.x * 64 + lane;
   const bool xin = x < W;
   typedef typename iir_src<SRC16>::T TS;
@@ -493,59 +497,7 @@ __global__ __launch_bounds__(128) void k_iir_fused(P3 dst, P3c src, float *__res
   float *__restrict__ tl = tails + ((size_t)(k * nchunks + c) * 4 * 7) * W;      // (uniform)
   const int ylo = -IIR_WARM, yhi = H + IIR_WARM;
   float cur[IIR_CH], nxt[IIR_CH];
-  static_assert(IIR_CH >= 8 && IF_WU % IIR_CH == 0 && (IF_ROWS / 2) % IIR_CH == 0, "the interior path walks whole chunks, half a block per phase");
-  if (s0 - IF_WU >= 0 && s1 + IF_WU <= H && s1 - s0 == IF_ROWS) {
-    // Interior block (all but the first and last of a column): no mirrored rows, no clamping, a full block - the same steps
-    // as below with every row test resolved at compile time (the scalar address and branch work of the general form costs
-    // as many issue slots as the recurrence itself).  A chunk = IIR_CH rows; while one is evaluated the next one's rows are
-    // fetched (MORE = 0: there is no next one).
-    // IIR_CHUNK(row pointer of the chunk's first row, row step, STORE: what to do with an output row, TAIL: tails set or -1)
-#define IIR_CHUNK(PTR, STEP, STORE, TAIL, TIDX) IIR_CHUNK_(PTR, STEP, STORE, TAIL, TIDX, 1)
-#define IIR_CHUNK_(PTR, STEP, STORE, TAIL, TIDX, MORE)                                                                  \
-    {                                                                                                                    \
-      if (MORE) { _Pragma("unroll") for (int j = 0; j < IIR_CH; j++) nxt[j] = IIR_LD(IIR_ROW((PTR) + ((long)(IIR_CH + j) * (STEP)) * W)); } \
-      _Pragma("unroll") for (int j = 0; j < IIR_CH; j++) {                                                               \
-        IIR_STEP(cur[j]);                                                                                                \
-        STORE;                                                                                                           \
-        if ((TAIL) >= 0 && j >= IIR_CH - 7 && xin) IIR_OUT(tl + (size_t)((TAIL) * 7 + (TIDX)) * W) = d;                            \
-        IIR_SHIFT(cur[j]);                                                                                               \
-      }                                                                                                                  \
-      _Pragma("unroll") for (int j = 0; j < IIR_CH; j++) cur[j] = nxt[j];                                                \
-    }
-    constexpr int HALF = IF_ROWS / 2 / IIR_CH;     // chunks per phase
-    IIR_STATE;
-    if (!anti) {   // causal: rows s0 - IF_WU .. s1 - 1
-      const TS *p = in + (size_t)(s0 - IF_WU) * W;
-#pragma unroll
-      for (int j = 0; j < IIR_CH; j++) cur[j] = IIR_LD(IIR_ROW(p + (size_t)j * W));
-      for (int q = 0; q < IF_WU / IIR_CH - 1; q++) { IIR_CHUNK(p, 1, (void)0, -1, 0); p += (size_t)IIR_CH * W; }
-      IIR_CHUNK(p, 1, (void)0, 0, j - (IIR_CH - 7)); p += (size_t)IIR_CH * W;                    // rows s0-16 .. s0-1: "warm" tails
-      float *f = fwt + lane;
-      for (int q = 0; q < HALF; q++) { IIR_CHUNK(p, 1, f[j * IF_PITCH] = d, -1, 0); p += (size_t)IIR_CH * W; f += IIR_CH * IF_PITCH; }
-      __syncthreads();
-      float *o = TOUT ? nullptr : dk + (size_t)mid * W;
-#define IIR_FINISH_F { const float r = (f[j * IF_PITCH] + d) - cur[j] * IIR_C0; if (TOUT) f[j * IF_PITCH] = r; else if (xin) IIR_OUT(o + (long)j * W) = r; }
-      for (int q = 0; q < HALF - 1; q++) { IIR_CHUNK(p, 1, IIR_FINISH_F, -1, 0); p += (size_t)IIR_CH * W; f += IIR_CH * IF_PITCH; if (!TOUT) o += (size_t)IIR_CH * W; }
-      IIR_CHUNK_(p, 1, IIR_FINISH_F, 1, j - (IIR_CH - 7), 0);                                     // rows s1-16 .. s1-1: "true" tails
-#undef IIR_FINISH_F
-    } else {       // anti-causal: rows s1 - 1 + IF_WU .. s0
-      const TS *p = in + (size_t)(s1 - 1 + IF_WU) * W;
-#pragma unroll
-      for (int j = 0; j < IIR_CH; j++) cur[j] = IIR_LD(IIR_ROW(p - (long)j * W));
-      for (int q = 0; q < IF_WU / IIR_CH - 1; q++) { IIR_CHUNK(p, -1, (void)0, -1, 0); p -= (size_t)IIR_CH * W; }
-      IIR_CHUNK(p, -1, (void)0, 2, (IIR_CH - 1) - j); p -= (size_t)IIR_CH * W;                   // rows s1+15 .. s1: "warm" tails (index = row - s1)
-      float *f = fwt + (IF_ROWS - 1) * IF_PITCH + lane;
-      for (int q = 0; q < HALF; q++) { IIR_CHUNK(p, -1, f[-j * IF_PITCH] = d, -1, 0); p -= (size_t)IIR_CH * W; f -= IIR_CH * IF_PITCH; }
-      __syncthreads();
-      float *o = TOUT ? nullptr : dk + (size_t)(mid - 1) * W;
-#define IIR_FINISH_B { const float r = d + f[-j * IF_PITCH] - cur[j] * IIR_C0; if (TOUT) f[-j * IF_PITCH] = r; else if (xin) IIR_OUT(o - (long)j * W) = r; }
-      for (int q = 0; q < HALF - 1; q++) { IIR_CHUNK(p, -1, IIR_FINISH_B, -1, 0); p -= (size_t)IIR_CH * W; f -= IIR_CH * IF_PITCH; if (!TOUT) o -= (size_t)IIR_CH * W; }
-      IIR_CHUNK_(p, -1, IIR_FINISH_B, 3, (IIR_CH - 1) - j, 0);                                     // rows s0+15 .. s0: "true" tails (index = row - s0)
-#undef IIR_FINISH_B
-    }
-#undef IIR_CHUNK
-#undef IIR_CHUNK_
-  } else {
+  {
     IIR_STATE;
     if (!anti) {   // ---------------- causal sweep: rows fb .. s1-1 (one barrier, before row `mid`)
       const int fb = (s0 - IF_WU <= ylo) ? ylo : s0 - IF_WU;
@@ -611,6 +563,164 @@ __global__ __launch_bounds__(128) void k_iir_fused(P3 dst, P3c src, float *__res
       for (int r = lane; r < rows; r += 64) at32(o, (unsigned)r) = fwt[r * IF_PITCH + col];
     }
   }
+}
+
+// k_iir_fused: the blocks of IF_ROWS rows exactly (block 0 .. nf - 1: all but a shorter or longer last one).  Every row of the block is a compile-time distance
+// from the block's start, so the wave that parks a value is made the wave that consumes it and the parked half stays in REGISTERS:
+//   first half   wave 0 sweeps causally s0 - IF_WU .. mid - 1, wave 1 anti-causally s1 - 1 + IF_WU .. mid; each keeps the IF_ROWS / 2 raw outputs of its half
+//   swap         each writes its recurrence state (q1 .. q7, 14 floats a lane) to LDS; one barrier; each reads the other's
+//   second half  wave 0 continues the ANTI-causal sweep mid - 1 .. s0, wave 1 the CAUSAL one mid .. s1 - 1, over the rows whose other sweep they parked themselves,
+//                and finish them: (anti + causal) - c0 * in
+// Every sweep visits the rows it visited before, in the same order, from the same state; who adds does not matter (the sum commutes).  The wave that ends a sweep
+// writes its "true" tails: wave 1 the causal set, wave 0 the anti-causal one.  The two roles differ by the sign of the row step alone, which is a wave-uniform
+// value (`rs`): ONE instruction stream serves both, and both halves are unrolled (a parked value needs a register with a name).
+// LDS: the swap area (7168 bytes) and, with TOUT, a batch of IF_TB finished rows per wave that leaves transposed before the next one is written (row pitch 64 + 64 / IF_TB
+// floats: the rows of one batch as columns of 64 / IF_TB lanes each, conflict-free both ways).
+// (a row pointer handed over as the wave-uniform value it is, opaque to the optimiser: the row step's sign is a run-time value here, and otherwise the lane's offset is
+// folded into the pointer and every access walks a 64-bit address per lane - two registers and a vector addition)
+__device__ __forceinline__ unsigned iir_off(unsigned o) { asm("" : "+v"(o)); return o; }
+template <typename T> __device__ __forceinline__ __attribute__((address_space(1))) T *iir_uni(T *p) {
+  __attribute__((address_space(1))) T *g = (__attribute__((address_space(1))) T *)p;
+  asm("" : "+s"(g));
+  return g;
+}
+#ifndef IIR_PCH
+#define IIR_PCH 16              // rows per chunk here (see IIR_CH; 8 measured 1 us per frame and pass slower at 128-row blocks, at the same three waves per SIMD)
+#endif
+#ifndef IF_TB
+#define IF_TB 32               // rows per transposition batch: 32 -> 128-byte column segments; 16 -> 64-byte ones wrote 21 % more bytes (WRITE_SIZE) and ran 1.7 us per frame slower
+#endif
+#define IF_TP (64 + 64 / IF_TB)
+#ifdef IF_WPE                  // tuning builds: the waves per SIMD the register allocation is to aim at
+#define IF_WPE_ATTR __attribute__((amdgpu_waves_per_eu(IF_WPE)))
+#else
+#define IF_WPE_ATTR
+#endif
+template <int TOUT, int IF_ROWS, int SRC16>
+__global__ __launch_bounds__(128) IF_WPE_ATTR void k_iir_fused(P3 dst, P3c src, float *__restrict__ tails, int W, int H, int nchunks, int *bad, int np, size_t zs) {
+  constexpr int HALF = IF_ROWS / 2, CH = IIR_PCH, CPI = 64 / IF_TB;
+  static_assert(CH >= 8 && IF_WU % CH == 0 && HALF % CH == 0 && HALF % IF_TB == 0 && 64 % IF_TB == 0, "whole chunks and whole batches, half a block per phase");
+  __shared__ float swp[2 * 14 * 64];
+  __shared__ float stg[TOUT ? 2 * IF_TB * IF_TP : 1];
+  const int lane = threadIdx.x & 63, anti = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  // (grid: x = 64-column strips, y = plane + np * frame of a group launch, z = block of rows)
+  // (the division runs on the vector unit: its result is handed back as the wave-uniform value it is, or every pointer below lives in vector registers)
+  const int fz = __builtin_amdgcn_readfirstlane((int)(blockIdx.y / np)), k = blockIdx.y - fz * np, c = blockIdx.z;
+  // (pointers by comparisons, rows as a uniform pointer plus the lane's 32-bit byte offset: k_iir_fused_edge)
+  float *dk = k == 0 ? dst.p[0] : (k == 1 ? dst.p[1] : dst.p[2]);
+  const float *sk = k == 0 ? src.p[0] : (k == 1 ? src.p[1] : src.p[2]);
+  { const size_t rd_zoff_ = (size_t)fz * zs; RD_ZS1(dk); RD_ZS1(sk); RD_ZS1(tails); RD_ZS1(bad); }
+  if (blockIdx.x == 0 && k == 0 && blockIdx.z == 0 && threadIdx.x == 0) *bad = 0;      // diagnostics flag of the check that follows this launch
+  const int x = blockIdx.x * 64 + lane;
+  const bool xin = x < W;
+  typedef typename iir_src<SRC16>::T TS;
+  const TS *__restrict__ in = (const TS *)sk;
+  const unsigned xs = (unsigned)(xin ? x : W - 1) * (unsigned)sizeof(TS), x4 = (unsigned)(xin ? x : W - 1) * 4u;
+  // (this kernel's form of IIR_ROW / IIR_OUT: the offset opaque too, so that its extension to 64 bits stays with the access and the access takes the scalar base)
+#undef IIR_ROW
+#undef IIR_OUT
+#define IIR_ROW(ptr) (*(const TS *)((const char *)(ptr) + xo_))             /* xo_: the opaque offset, made once per chunk of loads */
+#define IIR_OUT(ptr) (*(float *)((char *)(ptr) + iir_off(x4)))
+  const float sc = k == 0 ? 1.0f / 4096 : 1.0f / 1024, hf = k == 0 ? 0.5f / 4096 : 0.5f / 1024;
+  const int s0 = c * IF_ROWS, s1 = s0 + IF_ROWS, mid = s0 + HALF;
+  float *__restrict__ tl = tails + ((size_t)(k * nchunks + c) * 4 * 7) * W;      // tails: k_iir_fused_edge
+  const long rs = anti ? -(long)W : (long)W;      // row step of the first half's sweep, in elements; the second half walks by -rs
+  float cur[CH], nxt[CH], park[HALF];
+  // IIR_PCHUNK(MORE: there is a chunk to fetch meanwhile, its first row, its row step, BODY: what to do with output d of row j of this chunk)
+#define IIR_PSTEPS(...)                                                                                                  \
+      _Pragma("unroll") for (int j = 0; j < CH; j++) {                                                                   \
+        IIR_STEP(cur[j]);                                                                                                \
+        __VA_ARGS__;                                                                                                     \
+        IIR_SHIFT(cur[j]);                                                                                               \
+      }                                                                                                                  \
+      _Pragma("unroll") for (int j = 0; j < CH; j++) cur[j] = nxt[j];
+#define IIR_PCHUNK(MORE, NEXT, NSTEP, ...)                                                                               \
+    {                                                                                                                    \
+      if (MORE) { const TS *n_ = (NEXT); const unsigned xo_ = iir_off(xs); _Pragma("unroll") for (int j = 0; j < CH; j++) { nxt[j] = IIR_LD(IIR_ROW(iir_uni(n_))); n_ += (NSTEP); } } \
+      IIR_PSTEPS(__VA_ARGS__)                                                                                            \
+    }
+  // (a copy of its own: the output also sits in one half of the state pair q1, and a 64-bit pair kept alive for its one half costs two registers a row)
+#define IIR_PARK(dst, v) asm("v_mov_b32 %0, %1" : "=v"(dst) : "v"(v))
+  IIR_STATE;
+  const TS *p = in + (size_t)(anti ? s1 - 1 : s0) * W;                           // the first half's first row
+  const TS *const pb = in + (size_t)(anti ? mid : mid - 1) * W;                  // where the second half starts
+  // the run-in, IF_WU rows; its last 7: "warm" tails - causal set 0, index row - (s0 - 7); anti-causal set 2, index row - s1
+  float *const tw = tl + (size_t)(anti ? 2 * 7 + 6 : 0) * W;
+#define IIR_WTAIL if (j >= CH - 7 && xin) IIR_OUT(iir_uni(tw + (long)(j - (CH - 7)) * rs)) = d
+  if (anti ? s1 + IF_WU <= H : s0 - IF_WU >= 0) {
+    const TS *w = p - IF_WU * rs;
+    { const unsigned xo_ = iir_off(xs);
+#pragma unroll
+      for (int j = 0; j < CH; j++) cur[j] = IIR_LD(IIR_ROW(iir_uni(w + (long)j * rs))); }
+    for (int q = 0; q < IF_WU / CH - 1; q++) { IIR_PCHUNK(1, w + CH * rs, rs, (void)0); w += CH * rs; }
+    IIR_PCHUNK(1, p, rs, IIR_WTAIL);
+  } else {
+    // The column's first block (wave 0) or one of its last (wave 1): the run-in leaves the plane.  The line's sweep starts IIR_WARM samples outside it, on mirrored
+    // samples, from a zero state; a step on a zero state and a zero input leaves the zero state (+0 in every bit: 0 * c0 is +0, and +0 plus a product of either
+    // sign of zero is +0), so the rows further out are fed as zeros and the same IF_WU steps arrive at the state of the line's own start.
+    const int dy = anti ? -1 : 1, y0 = anti ? s1 - 1 + IF_WU : s0 - IF_WU;
+    const unsigned xo_ = iir_off(xs);
+    auto eld = [&](int yy) -> float {
+      const int yc = clampi(yy, -IIR_WARM, H + IIR_WARM);
+      const float v = IIR_LD(IIR_ROW(iir_uni(in + (size_t)mirror1(yc, H) * W)));
+      return yy == yc ? v : 0.0f;
+    };
+#define IIR_PCHUNK_E(YN, ...) { _Pragma("unroll") for (int j = 0; j < CH; j++) nxt[j] = eld((YN) + j * dy); IIR_PSTEPS(__VA_ARGS__) }
+#pragma unroll
+    for (int j = 0; j < CH; j++) cur[j] = eld(y0 + j * dy);
+    for (int q = 0; q < IF_WU / CH - 1; q++) IIR_PCHUNK_E(y0 + (q + 1) * CH * dy, (void)0)
+    IIR_PCHUNK(1, p, rs, IIR_WTAIL);
+  }
+#undef IIR_WTAIL
+#pragma unroll
+  for (int q = 0; q < HALF / CH; q++) {
+    const bool last = q == HALF / CH - 1;
+    IIR_PCHUNK(1, last ? pb : p + CH * rs, last ? -rs : rs, IIR_PARK(park[q * CH + j], d)); p += CH * rs;
+  }
+  {   // the swap: my state out, the other sweep's state in
+    float *mine = swp + anti * (14 * 64) + lane, *theirs = swp + (anti ^ 1) * (14 * 64) + lane;
+#define IIR_SWAP(n, q) mine[(2 * n) * 64] = q.x; mine[(2 * n + 1) * 64] = q.y;
+    IIR_SWAP(0, q1) IIR_SWAP(1, q2) IIR_SWAP(2, q3) IIR_SWAP(3, q4) IIR_SWAP(4, q5) IIR_SWAP(5, q6) IIR_SWAP(6, q7)
+#undef IIR_SWAP
+    __syncthreads();
+#define IIR_SWAP(n, q) q.x = theirs[(2 * n) * 64]; q.y = theirs[(2 * n + 1) * 64];
+    IIR_SWAP(0, q1) IIR_SWAP(1, q2) IIR_SWAP(2, q3) IIR_SWAP(3, q4) IIR_SWAP(4, q5) IIR_SWAP(5, q6) IIR_SWAP(6, q7)
+#undef IIR_SWAP
+  }
+  // second half, step i: row mid - 1 - i (wave 0) or mid + i (wave 1), whose other sweep is park[HALF - 1 - i]; the last 7 rows: "true" tails - anti-causal set 3,
+  // index row - s0 (wave 0); causal set 1, index row - (s1 - 7) (wave 1)
+  p = pb;
+  float *const tt = tl + (size_t)(anti ? 1 * 7 : 3 * 7 + 6) * W;
+  float *o = dk + (size_t)(anti ? mid : mid - 1) * W;                            // (!TOUT) the row being finished
+  float *const st = stg + (TOUT ? anti * (IF_TB * IF_TP) : 0);
+  // (TOUT) a batch leaves as 64 / IF_TB columns of IF_TB rows per store: this lane takes row `br` of the batch in column `bc` + CPI * n; wave 0 walks down, so its
+  // slot of the batch's r-th row is IF_TB - 1 - r
+  const int br = lane % IF_TB, bc = lane / IF_TB;
+  const float *const sl = st + (anti ? br : IF_TB - 1 - br) * IF_TP + bc;
+  const unsigned bo = ((unsigned)bc * (unsigned)H + (unsigned)br) * 4u;
+#pragma unroll
+  for (int q = 0; q < HALF / CH; q++) {
+    const bool last = q == HALF / CH - 1;
+    IIR_PCHUNK(!last, p - CH * rs, -rs, {
+      const int i = q * CH + j;
+      const float r = (park[HALF - 1 - i] + d) - cur[j] * IIR_C0;
+      if (TOUT) st[(i % IF_TB) * IF_TP + lane] = r; else if (xin) IIR_OUT(iir_uni(o - (long)j * rs)) = r;
+      if (i >= HALF - 7 && xin) IIR_OUT(iir_uni(tt - (long)(i - (HALF - 7)) * rs)) = d;
+      if (TOUT && i % IF_TB == IF_TB - 1) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const int lowest = anti ? mid + (i / IF_TB) * IF_TB : mid - (i / IF_TB + 1) * IF_TB;      // the batch's first row
+        float *const ob = dk + (size_t)(blockIdx.x * 64) * H + lowest;
+        _Pragma("unroll") for (int n = 0; n < IF_TB; n++)
+          if ((int)blockIdx.x * 64 + n * CPI + bc < W) *(float *)((char *)iir_uni(ob + (size_t)(n * CPI) * H) + bo) = sl[n * CPI];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      }
+    });
+    p -= CH * rs; if (!TOUT) o -= CH * rs;
+  }
+#undef IIR_PCHUNK
+#undef IIR_PCHUNK_E
+#undef IIR_PSTEPS
+#undef IIR_PARK
 }
 
 #undef IIR_LD
@@ -1151,11 +1261,18 @@ void iir_blur_pass(hipStream_t s, float *const dst[3], const float *const src[3]
                    int transpose_out, float *tails, int *bad, int src16, int nz, size_t zs) {
   const int rows = if_pick_rows(np, W, H, transpose_out, nz);
   const int nchunks = if_nchunks(H, rows);
+  // blocks 0 .. nf - 1 have `rows` rows exactly (k_iir_fused); the last one does when H is a multiple of `rows`, and goes to k_iir_fused_edge when not
+  const int nf = (H - (nchunks - 1) * rows == rows) ? nchunks : nchunks - 1;
   const dim3 grid(cdiv(W, 64), np * nz, nchunks);
-#define IF_LAUNCH(T, R, S16) hipLaunchKernelGGL((k_iir_fused<T, R, S16>), grid, dim3(128), 0, s, mk3(dst, np), mk3c(src, np), tails, W, H, nchunks, bad, np, zs)
-#define IF_LAUNCH_R(R) { if (transpose_out && src16) IF_LAUNCH(1, R, 1); else if (transpose_out) IF_LAUNCH(1, R, 0); else IF_LAUNCH(0, R, 0); }
+  const dim3 fgrid(grid.x, grid.y, nf), egrid(grid.x, grid.y, nchunks - nf);
+#define IF_LAUNCH(T, R, S16) { if (nf > 0) hipLaunchKernelGGL((k_iir_fused<T, R, S16>), fgrid, dim3(128), 0, s, mk3(dst, np), mk3c(src, np), tails, W, H, nchunks, bad, np, zs); \
+    if (nf < nchunks) hipLaunchKernelGGL((k_iir_fused_edge<T, R, S16>), egrid, dim3(128), 0, s, mk3(dst, np), mk3c(src, np), tails, W, H, nchunks, nf, bad, np, zs); }
+#define IF_LAUNCH_R(R) { if (transpose_out && src16) IF_LAUNCH(1, R, 1) else if (transpose_out) IF_LAUNCH(1, R, 0) else IF_LAUNCH(0, R, 0) }
   switch (rows) {
     case 64: IF_LAUNCH_R(64); break;
+#if IF_GROUP_ROWS != 64 && IF_GROUP_ROWS != 128
+    case IF_GROUP_ROWS: IF_LAUNCH_R(IF_GROUP_ROWS); break;
+#endif
     default: IF_LAUNCH_R(128); break;
   }
 #undef IF_LAUNCH_R
