@@ -645,6 +645,84 @@ int rd_matcher_wait(rd_matcher *m, rd_match *out, int32_t *dots_out);
  * Returns as rd_matcher_enqueue; -1 also when nothing has been polled yet or d and m are on different devices. */
 long rd_detector_match_polled(rd_detector *d, rd_matcher *m, const double *quads, int n, int flags);
 
+/* ---- remapped frames: the frame an IDEAL pinhole camera would have seen, made on the device from the frame a real lens gave (rd_k_remap.hip, rd_remap.hip,
+ * rd_remap_host.c) - lens undistortion ahead of the detector, whose polyline stage, quad vote and pose fit all assume straight lines and a pinhole.  The reference
+ * leaves this to OpenCV on the host (cv::remap), so the arithmetic is defined here - exactly, so that an independent restatement (tests/remap.py, numpy float64)
+ * reproduces every byte.
+ *
+ * rd_lens is the SOURCE camera: focal lengths and principal point in pixels and the Brown-Conrady coefficients in OpenCV's order (k1, k2, p1, p2, k3).  rd_view is
+ * the ideal camera of the OUTPUT.  Pixel centres sit at integers.
+ *
+ * Source position (X, Y) of output pixel (u, v) - IEEE double, exactly these operations in this order, no contraction (rd_remap_points):
+ *   x = (u - view.cx) / view.fx;   y = (v - view.cy) / view.fy
+ *   xx = x*x;  yy = y*y;  xy = x*y;  r2 = xx + yy
+ *   rad = ((k3*r2 + k2)*r2 + k1)*r2 + 1.0
+ *   xd = (x*rad + (2.0*p1)*xy) + p2*(r2 + 2.0*xx)
+ *   yd = (y*rad + p1*(r2 + 2.0*yy)) + (2.0*p2)*xy
+ *   X = lens.fx*xd + lens.cx;   Y = lens.fy*yd + lens.cy
+ * (Believed to be the map of OpenCV's initUndistortRectifyMap with R = I, up to the order of roundings; not checked - there is no OpenCV to check against.)
+ *
+ * Table entry of (u, v): two int32.  The position is INSIDE when X >= 0 && X <= iw-1 && Y >= 0 && Y <= ih-1 for an iw x ih source - compared in double, so a NaN or
+ * an infinity is outside; X = -0.0 and X = iw-1 are inside.
+ *   inside:   xi = (int)floor(X * 256.0);   yi = (int)floor(Y * 256.0)
+ *   outside:  xi = yi = -1
+ * The table is ow * oh entries, rows back to back: entry (u, v) at table[2 * (v*ow + u)], xi first.
+ *
+ * A caller's own map: two planes of ow * oh float32, mapx and mapy, rows back to back - what cv::initUndistortRectifyMap(..., CV_32FC1), a fisheye calibration or
+ * a stereo rectification hands out.  With X = (double)mapx[v*ow + u] and Y = (double)mapy[v*ow + u] the same entry rule applies (rd_remap_table_map): both sources
+ * end in the one table, and one kernel applies it.
+ *
+ * Output pixel (u, v): 3 bytes B, G, R at out + v * out_pitch + 3 * u.  An outside entry gives the job's fill colour.  Otherwise
+ *   x0 = xi >> 8;  fx = xi & 255;  x1 = min(x0+1, iw-1)                                (y0, fy, y1 the same with yi and ih)
+ * and per channel, in int32, with p(x, y) the channel's byte of source pixel (x, y):
+ *   top = p(x0,y0)*(256-fx) + p(x1,y0)*fx;   bot = p(x0,y1)*(256-fx) + p(x1,y1)*fx
+ *   out = (top*(256-fy) + bot*fy + 32768) >> 16
+ * - the rectifier's blend.  p is the (B, G, R) of the source pixel under the conversion contract above: for NV12 and I420 each of the four taps is converted first and
+ * blended afterwards, so the output from a frame in any format equals, byte for byte, the output from the BGR frame the contract gives for it. */
+typedef struct { double fx, fy, cx, cy, k1, k2, p1, p2, k3; } rd_lens;   /* 72 bytes: the SOURCE camera; OpenCV's order of the Brown-Conrady coefficients */
+typedef struct { double fx, fy, cx, cy; } rd_view;                       /* 32 bytes: the ideal camera of the OUTPUT */
+
+/* host helpers; none needs a GPU */
+/* the map above for n arbitrary points: uv[2k], uv[2k+1] = (u, v) -> XY[2k], XY[2k+1] = (X, Y).  The definition the table is built from - and what draws something
+ * detected in the undistorted frame onto the ORIGINAL one.  No argument is checked. */
+void rd_remap_points(const rd_lens *lens, const rd_view *view, const double *uv, int n, double *XY);
+/* The table of an ow x oh output from an iw x ih source, from a lens and a view or from a caller's maps.  Both return the number of INSIDE entries, or -1 with
+ * nothing written for bad arguments: a NULL pointer, ow or oh < 1 or > 16384, iw or ih < 1 or > 65536, a lens or view field that is not finite, a view with fx or
+ * fy equal to 0. */
+int rd_remap_table_lens(const rd_lens *lens, const rd_view *view, int ow, int oh, int iw, int ih, int32_t *table);
+int rd_remap_table_map(const float *mapx, const float *mapy, int ow, int oh, int iw, int ih, int32_t *table);
+/* (double)(ow / 2) / view->fx, with the integer half width the pose fit uses: the tanAOV to pass to rd_detector_poll for frames made with this view */
+double rd_view_tan_aov(const rd_view *view, int ow);
+/* out[0], out[1]: the smallest and the largest ow and oh (1, 16384); out[2], out[3]: the smallest and the largest iw and ih (1, 65536) */
+void rd_remap_limits(int32_t out[4]);
+
+/* A remapper makes ow x oh BGR frames from iw x ih source frames, up to njobs jobs in flight, on one stream of its own.  Create builds the table on the host with the
+ * functions above and uploads it once (8 bytes per output pixel of device memory).  NULL on their argument errors, njobs < 1 or > 1024, no such device. */
+typedef struct rd_remapper rd_remapper;
+rd_remapper *rd_remapper_create_lens(int device, const rd_lens *lens, const rd_view *view, int ow, int oh, int iw, int ih, int njobs);
+rd_remapper *rd_remapper_create_map(int device, const float *mapx, const float *mapy, int ow, int oh, int iw, int ih, int njobs);
+void rd_remapper_destroy(rd_remapper *r);                 /* waits for the jobs in flight */
+int rd_remapper_inside(const rd_remapper *r);             /* entries of its table that are inside; -1 for a bad handle */
+/* One job: the ow x oh output of one source frame - iw x ih, the remapper's - in pixel format `format` (RD_PIX_*; planes / pitches as for rd_detector_enqueue_planes).
+ * on_device: where the source lies, as for rd_rectifier_enqueue - RD_FRAME_HOST (copied into the remapper's own device buffer, which grows on demand, before the call
+ *   returns), RD_FRAME_DEVICE (read in place) or RD_FRAME_HOST_PINNED (the copy engine reads it in place; memory that is not pinned is fatal); device and pinned frames
+ *   stay valid and unchanged until the job's rd_remapper_wait returned.
+ * fill_bgr: the colour of outside pixels, B | G << 8 | R << 16.
+ * out / out_pitch / out_kind: where the frame goes, its row stride in bytes (>= 3 * ow) and what memory it is - RD_FRAME_DEVICE (the kernel writes there) or
+ *   RD_FRAME_HOST_PINNED (the copy engine does).  Only the 3 * ow row bytes are written: the pitch padding of `out` is left alone.  Valid until the job's wait.
+ * Returns the job's sequence number, or -1 with nothing enqueued for an argument error: an unknown format, on_device or out_kind, a NULL plane the format uses, a pitch
+ * smaller than its plane's row, NV12 / I420 with an odd iw or ih, out NULL, out_pitch < 3 * ow, `out` not memory of the kind out_kind names (pageable memory; only the
+ * kind of the memory at `out` is asked about - that it holds (oh-1) * out_pitch + 3 * ow bytes is the caller's contract).  A call with njobs jobs already in flight is
+ * fatal, as it is for the detector.
+ *
+ * Hand-over to the detector: after rd_remapper_wait the caller passes a device `out` to rd_detector_enqueue(d, out, out_pitch, RD_FRAME_DEVICE) of a detector of
+ * ow x oh pixels, polls with rd_view_tan_aov(view, ow), and keeps `out` until that frame's poll returned; every rd_detector_*_polled service then reads the
+ * undistorted frame in place.  With njobs > 1 and as many `out` frames the remap of frame n+1 runs while frame n is detected.  Rectangles come back in the
+ * coordinates of the OUTPUT; rd_remap_points takes them to the original frame. */
+long rd_remapper_enqueue(rd_remapper *r, int format, const void *const planes[3], const int pitches[3], int on_device, uint32_t fill_bgr, void *out, int out_pitch,
+                         int out_kind);
+int rd_remapper_wait(rd_remapper *r);                     /* the oldest job: blocks until its frame is where it was told to go; 0, or -1: no job in flight */
+
 /* ---- synthetic frames (csrc/rd_synth.c) */
 int rd_synth_num_quads(int iw, int ih);
 void rd_synth_frame(uint8_t *bgr, int iw, int ih, int ws, uint64_t seed, int t, int noise);

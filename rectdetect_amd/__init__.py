@@ -43,6 +43,8 @@ MATCH_DOTS = 1
 TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = range(4)
 TENSOR_NHWC, TENSOR_NCHW = 0, 1
 TENSOR_BGR, TENSOR_RGB, TENSOR_GRAY = range(3)
+LENS_DTYPE = np.dtype([(n, "<f8") for n in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")])      # rd_lens, 72 bytes
+VIEW_DTYPE = np.dtype([(n, "<f8") for n in ("fx", "fy", "cx", "cy")])                                    # rd_view, 32 bytes
 TENSOR_SPEC_DTYPE = np.dtype([("dtype", "<i4"), ("layout", "<i4"), ("channels", "<i4"), ("oversample", "<i4"), ("scale", "<f4", (3,)), ("bias", "<f4", (3,))])
 assert TENSOR_SPEC_DTYPE.itemsize == 40
 TENSOR_NUMPY = {TENSOR_U8: np.dtype(np.uint8), TENSOR_F16: np.dtype(np.float16), TENSOR_BF16: np.dtype(np.uint16), TENSOR_F32: np.dtype(np.float32)}      # (bf16: its bits)
@@ -162,6 +164,18 @@ def _declare(L):
         "rd_matcher_enqueue": (ctypes.c_long, [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ci, ci, vp, ci, ci]),
         "rd_matcher_wait": (ci, [vp, vp, vp]),
         "rd_detector_match_polled": (ctypes.c_long, [vp, vp, vp, ci, ci]),
+        # remapped frames (rd_remap.hip, rd_remap_host.c)
+        "rd_remap_points": (None, [vp, vp, vp, ci, vp]),
+        "rd_remap_table_lens": (ci, [vp, vp, ci, ci, ci, ci, vp]),
+        "rd_remap_table_map": (ci, [vp, vp, ci, ci, ci, ci, vp]),
+        "rd_view_tan_aov": (cd, [vp, ci]),
+        "rd_remap_limits": (None, [vp]),
+        "rd_remapper_create_lens": (vp, [ci, vp, vp, ci, ci, ci, ci, ci]),
+        "rd_remapper_create_map": (vp, [ci, vp, vp, ci, ci, ci, ci, ci]),
+        "rd_remapper_destroy": (None, [vp]),
+        "rd_remapper_inside": (ci, [vp]),
+        "rd_remapper_enqueue": (ctypes.c_long, [vp, ci, ctypes.POINTER(vp), ctypes.POINTER(ci), ci, ctypes.c_uint32, vp, ci, ci]),
+        "rd_remapper_wait": (ci, [vp]),
         "rd_synth_frame": (None, [vp, ci, ci, ci, ctypes.c_uint64, ci, ci]),
         "rd_synth_num_quads": (ci, [ci, ci]),
         # reference API (oclhelper.h / raw cl*)
@@ -1034,6 +1048,121 @@ class Matcher(_Service):
         a = np.asarray(frame_bgr, dtype=np.uint8)
         self.enqueue(PIX_BGR, a, None, a.shape[1], a.shape[0], quads)
         return self.wait()
+
+
+def lens(fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
+    """an rd_lens as a LENS_DTYPE record: the SOURCE camera, with the Brown-Conrady coefficients in OpenCV's order"""
+    return np.array((fx, fy, cx, cy, k1, k2, p1, p2, k3), LENS_DTYPE)
+
+
+def view(fx, fy, cx, cy):
+    """an rd_view as a VIEW_DTYPE record: the ideal camera of the OUTPUT"""
+    return np.array((fx, fy, cx, cy), VIEW_DTYPE)
+
+
+def _lens_arg(l):
+    return np.ascontiguousarray(l, dtype=LENS_DTYPE).reshape(())
+
+
+def _view_arg(v):
+    """a view, or a lens whose fx, fy, cx, cy the view takes"""
+    if getattr(v, "dtype", None) == LENS_DTYPE:
+        return view(*(float(np.asarray(v)[n]) for n in ("fx", "fy", "cx", "cy")))
+    return np.ascontiguousarray(v, dtype=VIEW_DTYPE).reshape(())
+
+
+def _maps_arg(mapx, mapy, ow, oh):
+    mx, my = np.ascontiguousarray(mapx, dtype=np.float32), np.ascontiguousarray(mapy, dtype=np.float32)
+    if mx.size != ow * oh or my.size != ow * oh:
+        raise ValueError("remap: maps of %d and %d values for an output of %dx%d" % (mx.size, my.size, ow, oh))
+    return mx, my
+
+
+def remap_points(lens, view, uv):
+    """the source positions (n, 2) of output points uv (n, 2) under a lens and a view (rd_remap_points); runs without a GPU"""
+    l, v = _lens_arg(lens), _view_arg(view)
+    p = np.ascontiguousarray(uv, dtype=np.float64).reshape(-1, 2)
+    out = np.zeros_like(p)
+    lib().rd_remap_points(l.ctypes.data, v.ctypes.data, p.ctypes.data, len(p), out.ctypes.data)
+    return out
+
+
+def remap_table_lens(lens, view, ow, oh, iw, ih):
+    """(the (oh, ow, 2) int32 table xi, yi of an ow x oh output from an iw x ih source, its number of inside entries) (rd_remap_table_lens); runs without a GPU"""
+    l, v = _lens_arg(lens), _view_arg(view)
+    table = np.zeros((max(int(oh), 0), max(int(ow), 0), 2), np.int32)
+    n = lib().rd_remap_table_lens(l.ctypes.data, v.ctypes.data, int(ow), int(oh), int(iw), int(ih), table.ctypes.data)
+    if n < 0:
+        raise ValueError("rd_remap_table_lens: invalid arguments (lens %r, view %r, %dx%d from %dx%d)" % (l, v, ow, oh, iw, ih))
+    return table, n
+
+
+def remap_table_map(mapx, mapy, ow, oh, iw, ih):
+    """the same from a caller's float32 maps of ow * oh values each (rd_remap_table_map); runs without a GPU"""
+    mx, my = _maps_arg(mapx, mapy, ow, oh)
+    table = np.zeros((int(oh), int(ow), 2), np.int32)
+    n = lib().rd_remap_table_map(mx.ctypes.data, my.ctypes.data, int(ow), int(oh), int(iw), int(ih), table.ctypes.data)
+    if n < 0:
+        raise ValueError("rd_remap_table_map: invalid arguments (%dx%d from %dx%d)" % (ow, oh, iw, ih))
+    return table, n
+
+
+def view_tan_aov(view, ow):
+    """the tan_aov to poll with for ow-wide frames made with this view (rd_view_tan_aov); runs without a GPU"""
+    return float(lib().rd_view_tan_aov(_view_arg(view).ctypes.data, int(ow)))
+
+
+def remap_limits():
+    """{"min_out", "max_out", "min_src", "max_src"}: the smallest and largest side of an output and of a source (rd_remap_limits); runs without a GPU"""
+    a = np.zeros(4, np.int32)
+    lib().rd_remap_limits(a.ctypes.data)
+    return {"min_out": int(a[0]), "max_out": int(a[1]), "min_src": int(a[2]), "max_src": int(a[3])}
+
+
+class Remapper(_Service):
+    """The rd_remapper extension: ow x oh BGR frames as an ideal camera would have seen them, from iw x ih source frames in any pixel format, njobs jobs in flight
+    (the contract: include/rectdetect_hip.h, "remapped frames").  Either lens (and view: None takes the lens's fx, fy, cx, cy) or maps=(mapx, mapy), float32."""
+    _name = "remapper"
+
+    def __init__(self, ow, oh, iw, ih, lens=None, view=None, maps=None, njobs=2, device=0):
+        self.ow, self.oh, self.iw, self.ih, self.njobs = ow, oh, iw, ih, njobs
+        if (lens is None) == (maps is None):
+            raise ValueError("Remapper: either a lens or maps")
+        if maps is not None:
+            mx, my = _maps_arg(maps[0], maps[1], ow, oh)
+            self._create(device, mx.ctypes.data, my.ctypes.data, ow, oh, iw, ih, njobs, ctor="create_map")
+        else:
+            l = _lens_arg(lens)
+            v = _view_arg(l if view is None else view)
+            self._create(device, l.ctypes.data, v.ctypes.data, ow, oh, iw, ih, njobs, ctor="create_lens")
+
+    @property
+    def inside(self):
+        """the entries of the table that are inside the source (rd_remapper_inside)"""
+        return int(lib().rd_remapper_inside(self.h))
+
+    def enqueue(self, fmt, planes, pitches, on_device, out, out_pitch, fill=(0, 0, 0), pinned=False, out_pinned=False):
+        """one job: the ow x oh frame of an iw x ih source in format fmt (PIX_*) into `out` - the ADDRESS of device memory (the data_ptr() of a torch tensor will do)
+        or, with out_pinned, of pinned host memory - with rows out_pitch bytes apart; outside pixels get fill = (b, g, r).  planes / pitches as
+        Detector.enqueue_planes: numpy planes (copied before the call returns; pitches may be None), or with on_device / pinned their addresses, read in place until the
+        job's wait().  Returns the job's sequence number; ValueError on an argument error (nothing enqueued)."""
+        if on_device == 2:      # (RD_FRAME_HOST_PINNED by its number)
+            on_device, pinned = False, True
+        ptrs, pitch_c, kind, pitch, _ = _plane_args(planes, pitches, on_device, pinned)
+        b, g, r = (int(c) & 255 for c in fill)
+        seq = lib().rd_remapper_enqueue(self.h, int(fmt), ptrs, pitch_c, kind, b | g << 8 | r << 16, int(out) if out else None, int(out_pitch), 2 if out_pinned else 1)
+        if seq == -1:
+            raise ValueError("rd_remapper_enqueue: invalid arguments (format %r, pitches %r, out %r, out_pitch %r)" % (fmt, pitch, out, out_pitch))
+        return seq
+
+    def wait(self):
+        """blocks until the oldest job is done"""
+        self._wait()
+
+    def remap(self, frame_bgr, fill=(0, 0, 0)):
+        """convenience: the (oh, ow, 3) output of a numpy BGR image, as a new array, through pinned memory (one job, waited for)"""
+        a = np.asarray(frame_bgr, dtype=np.uint8)
+        return self._through_pinned(self.oh * self.ow * 3, lambda p: self.enqueue(PIX_BGR, a, None, False, p, self.ow * 3, fill, out_pinned=True)).reshape(self.oh, self.ow, 3)
 
 
 def postprocess_planes(segs, boundary, table, iw, ih, tan_aov):

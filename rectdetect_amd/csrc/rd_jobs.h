@@ -66,6 +66,7 @@ struct DevBuf {
 #define RD_MAGIC_ANNOTATOR 0x5244414eu
 #define RD_MAGIC_COMPOSITOR 0x5244434fu
 #define RD_MAGIC_MATCHER 0x52444d41u
+#define RD_MAGIC_REMAPPER 0x5244524du
 struct Ring {
   uint32_t magic;
   int device, per_job, njobs;

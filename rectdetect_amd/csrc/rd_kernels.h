@@ -202,4 +202,11 @@ enum { ANNOT_TILE_W = 64, ANNOT_TILE_H = 32, ANNOT_CHUNK = 256 };      // a bloc
 // with clear every pixel); otherwise every pixel of dst is written once: the source's, black, or a primitive's colour.  clear: RD_ANNOT_CLEAR.
 void annotate(hipStream_t s, int fmt, const rdpix::PixFrame &dst, const rdpix::PixFrame &src, const AnnotRec *recs, int n, int clear);
 
+// ---- rd_k_remap.hip: remapped frames (the contract: rectdetect_hip.h, "remapped frames")
+// the entries of a row of the table as the kernel reads it: ow rounded up to 4, so that a thread's 4 entries are 32 aligned bytes; the padding entries are (-1, -1)
+int remap_table_pitch(int ow);
+// an ow x oh BGR frame (rows out_pitch bytes apart, 3 * ow of them written) from one frame in format fmt (RD_PIX_*) through `table`: oh rows of
+// remap_table_pitch(ow) entries xi, yi, 256-byte aligned, every inside entry within src; outside entries get fill_bgr (B | G << 8 | R << 16)
+void remap(hipStream_t s, uint8_t *out, int out_pitch, int fmt, const rdpix::PixFrame &src, const int32_t *table, int ow, int oh, uint32_t fill_bgr);
+
 }  // namespace rdk
