@@ -372,8 +372,47 @@ void rd_tensor_limits(int32_t out[4]);
  * ordinary rd_rectifier: rd_rectifier_enqueue, rd_rectifier_wait, rd_rectifier_destroy and rd_detector_rectify_polled work on it with every pixel format, frame
  * kind and output kind, and `out` holds n * rd_rectifier_patch_bytes(r) bytes. */
 rd_rectifier *rd_rectifier_create_tensor(int device, int pw, int ph, int max_quads, int njobs, const rd_tensor_spec *spec);
-/* the bytes of one quad's output: pw * ph * 3 for a rectifier made by rd_rectifier_create; 0 for NULL */
+/* the bytes of one quad's output: pw * ph * 3 for a rectifier made by rd_rectifier_create, rd_tensor_bytes or rd_scan_bytes of the spec for the others; 0 for NULL */
 size_t rd_rectifier_patch_bytes(const rd_rectifier *r);
+
+/* -- scanned pages: the quad as a clean page - the patch's luma divided by its local mean (shading correction) or compared with it (adaptive threshold), as bytes
+ * or as one bit per pixel in packed rows, the raster of a PBM "P4" file (rd_k_scan.hip, rd_rectify.hip, rd_scan_host.c).  Two launches per job: the G plane by the
+ * tensor kernel, then the window sums and the decision.  Exact, in integers, like everything above: tests/scan.py restates it in numpy.
+ *
+ * A spec is LEGAL for pw x ph when mode is one of the three below, 1 <= radius <= 63, 0 <= k <= 255, 0 <= d <= 255, 1 <= white <= 255, oversample m is 1, 2 or 4,
+ * invert is 0 or 1, reserved is 0, pw >= 1, ph >= 1, pw*m <= 16384 and ph*m <= 16384.
+ *
+ * Pixel (i, j) of quad k:
+ *   1. G0(i, j) is, byte for byte, the element of the tensor spec { RD_TENSOR_U8, RD_TENSOR_NHWC, RD_TENSOR_GRAY, m } for the same quad, frame, pw and ph (steps 1-4
+ *      of "model-ready tensors").  G = invert ? 255 - G0 : G0.
+ *   2. The window of (i, j) is the intersection of the patch with the square of side 2*radius + 1 centred on (i, j):
+ *      [max(0, i-r), min(pw-1, i+r)] x [max(0, j-r), min(ph-1, j+r)].  N is its pixel count, T the sum of G over it.  T <= 255 * 127^2, and everything below fits
+ *      int32: the largest term is 256 * 127^2 * 510 = 2 105 802 240.
+ *   3. ink = 256*N*(G + d) < (256 - k)*T: the pixel is darker than (1 - k/256) of its neighbourhood's mean by more than d (Bradley's ratio with OpenCV's constant).
+ *      A constant patch has no ink for any k, d; an all-zero window has no ink.
+ *   4. F = (T == 0) ? white : min(255, (G*N*white + (T >> 1)) / T), an integer division: a pixel equal to its neighbourhood's mean comes out as `white`.
+ *   5. Output, quad k at out + k * rd_rectifier_patch_bytes(r):  RD_SCAN_FLAT: F at j*pw + i.  RD_SCAN_BILEVEL: ink ? 0 : 255 at the same place.
+ *      RD_SCAN_BITS: row j starts at byte j * ((pw + 7) >> 3), pixel i is bit 7 - (i & 7) of byte i >> 3, 1 = ink, and the pad bits of a row's last byte are 0.
+ *      An invalid quad (status 0) gives all-zero bytes in every mode.  The job's n * rd_rectifier_patch_bytes(r) bytes are written and nothing else. */
+#define RD_SCAN_FLAT 0          /* shading-corrected gray, one byte per pixel */
+#define RD_SCAN_BILEVEL 1       /* one byte per pixel: 0 = ink, 255 = paper */
+#define RD_SCAN_BITS 2          /* one BIT per pixel, 1 = ink, most significant bit first, rows padded to whole bytes with 0 bits: the raster of a PBM "P4" file */
+typedef struct { int32_t mode, radius, k, d, white, oversample, invert, reserved; } rd_scan_spec;   /* 32 bytes */
+/* host only, no GPU needed (rd_scan_host.c).  1 when the spec is legal for pw x ph, else 0 (a NULL spec too) */
+int rd_scan_spec_ok(const rd_scan_spec *spec, int pw, int ph);
+/* the bytes of one quad's page: pw * ph, or ((pw + 7) >> 3) * ph for RD_SCAN_BITS; 0 for a spec that is not legal for pw x ph */
+size_t rd_scan_bytes(const rd_scan_spec *spec, int pw, int ph);
+/* step 1's inversion and steps 3 and 4 for one pixel: G0 in 0 .. 255, N in 1 .. 127^2, T - the sum of the INVERTED G over the window - in 0 .. 255*N.  Writes 1 or 0
+ * to *ink and F to *flat (either may be NULL and is then skipped) and returns 1; returns 0 and writes nothing for a NULL spec, a spec whose k, d, white or invert
+ * is not legal, or G0, N or T outside these ranges */
+int rd_scan_pixel(const rd_scan_spec *spec, int G0, int N, int T, uint8_t *ink, uint8_t *flat);
+/* out[0] <- the legal modes as a bit set (bit v: value v is legal), out[1] <- the legal oversamplings ORed together (1 | 2 | 4), out[2] <- the largest radius,
+ * out[3], out[4] <- the width and the height, in output pixels, of the tile a block of the kernel makes, out[5..7] <- 0 */
+void rd_scan_limits(int32_t out[8]);
+/* A rectifier whose jobs write scanned pages.  NULL for the bad arguments of rd_rectifier_create, a NULL spec or a spec that is not legal for pw x ph.  The handle is
+ * an ordinary rd_rectifier: rd_rectifier_enqueue, rd_rectifier_wait, rd_rectifier_destroy and rd_detector_rectify_polled work on it with every pixel format, frame
+ * kind and output kind, and `out` holds n * rd_rectifier_patch_bytes(r) bytes. */
+rd_rectifier *rd_rectifier_create_scan(int device, int pw, int ph, int max_quads, int njobs, const rd_scan_spec *spec);
 
 /* ---- annotated frames: rectangles' outlines and line segments drawn INTO a frame on the device (rd_k_annotate.hip, rd_annotate.hip) - the picture vidrect.cpp /
  * rect.cpp (showRect) and vidpoly.cpp / poly.cpp make with OpenCV's line() on the host, for frames that never leave HBM.  OpenCV's round brush is not restated; the

@@ -11,7 +11,8 @@ Mirrors of the reference programs' call sequences:
   * :class:`Detector` - the ``rd_detector`` extension (device-resident frames, several frames in flight)
   * :class:`PolylineDetector` - its polyline kind: poly.cpp / vidpoly.cpp per frame, several frames in flight
   * :class:`Rectifier` - the ``rd_rectifier`` extension: what is inside detected quads as upright patches of fixed size, or - with a
-    :func:`tensor_spec` - as model-ready tensors (float, planar, normalised, box-filtered)
+    :func:`tensor_spec` - as model-ready tensors (float, planar, normalised, box-filtered), or - with a :func:`scan_spec` - as scanned pages (shading-corrected
+    gray, bilevel bytes or packed bit rows)
   * :class:`Annotator` - the ``rd_annotator`` extension: rectangles' outlines and line segments drawn into frames on the device
   * :class:`Compositor` - the ``rd_compositor`` extension: a colour or an image written into the quads of a frame on the device
   * :class:`Matcher` - the ``rd_matcher`` extension: which template of a library is inside each quad, decided on the device
@@ -48,6 +49,10 @@ VIEW_DTYPE = np.dtype([(n, "<f8") for n in ("fx", "fy", "cx", "cy")])           
 TENSOR_SPEC_DTYPE = np.dtype([("dtype", "<i4"), ("layout", "<i4"), ("channels", "<i4"), ("oversample", "<i4"), ("scale", "<f4", (3,)), ("bias", "<f4", (3,))])
 assert TENSOR_SPEC_DTYPE.itemsize == 40
 TENSOR_NUMPY = {TENSOR_U8: np.dtype(np.uint8), TENSOR_F16: np.dtype(np.float16), TENSOR_BF16: np.dtype(np.uint16), TENSOR_F32: np.dtype(np.float32)}      # (bf16: its bits)
+# a rectifier's scan spec (rd_scan_spec; the contract is in include/rectdetect_hip.h, "scanned pages")
+SCAN_FLAT, SCAN_BILEVEL, SCAN_BITS = range(3)
+SCAN_SPEC_DTYPE = np.dtype([(n, "<i4") for n in ("mode", "radius", "k", "d", "white", "oversample", "invert", "reserved")])
+assert SCAN_SPEC_DTYPE.itemsize == 32
 ANNOT_SEG_ALL, ANNOT_SEG_CHAINS = 0, 1
 
 # pixel formats of enqueue_planes (rd_detector_enqueue_planes; the conversion contract is in include/rectdetect_hip.h)
@@ -131,6 +136,12 @@ def _declare(L):
         "rd_tensor_limits": (None, [vp]),
         "rd_rectifier_create_tensor": (vp, [ci, ci, ci, ci, ci, vp]),
         "rd_rectifier_patch_bytes": (cz, [vp]),
+        # scanned pages (rd_rectify.hip, rd_scan_host.c)
+        "rd_scan_spec_ok": (ci, [vp, ci, ci]),
+        "rd_scan_bytes": (cz, [vp, ci, ci]),
+        "rd_scan_pixel": (ci, [vp, ci, ci, ci, vp, vp]),
+        "rd_scan_limits": (None, [vp]),
+        "rd_rectifier_create_scan": (vp, [ci, ci, ci, ci, ci, vp]),
         # annotated frames (rd_annotate.hip)
         "rd_annot_covers": (ci, [vp, ci, ci]),
         "rd_annot_touches": (ci, [vp, ci, ci, ci, ci]),
@@ -753,15 +764,61 @@ def tensor_limits():
     return {"dtypes": bits(int(a[0])), "layouts": bits(int(a[1])), "channels": bits(int(a[2])), "oversamplings": tuple(1 << k for k in bits(int(a[3])))}
 
 
+def scan_spec(mode, radius=15, k=26, d=0, white=230, oversample=1, invert=False):
+    """an rd_scan_spec as a SCAN_SPEC_DTYPE record: mode SCAN_FLAT / BILEVEL / BITS, the window's radius, ink where a pixel is darker than (1 - k/256) of its
+    neighbourhood's mean by more than d, the value FLAT gives a pixel equal to that mean, oversample 1, 2 or 4, invert for light ink on a dark page.  Whether it is
+    legal is decided where it is used (scan_spec_ok, Rectifier)."""
+    s = np.zeros((), SCAN_SPEC_DTYPE)
+    s["mode"], s["radius"], s["k"], s["d"], s["white"], s["oversample"], s["invert"] = mode, radius, k, d, white, oversample, int(invert)
+    return s
+
+
+def _scan_arg(spec):
+    return np.ascontiguousarray(spec, dtype=SCAN_SPEC_DTYPE).reshape(())
+
+
+def scan_spec_ok(spec, pw, ph):
+    """whether a scan spec is legal for pw x ph pages (rd_scan_spec_ok); runs without a GPU"""
+    return bool(lib().rd_scan_spec_ok(_scan_arg(spec).ctypes.data, int(pw), int(ph)))
+
+
+def scan_bytes(spec, pw, ph):
+    """the bytes of one quad's page, 0 for a spec that is not legal (rd_scan_bytes); runs without a GPU"""
+    return int(lib().rd_scan_bytes(_scan_arg(spec).ctypes.data, int(pw), int(ph)))
+
+
+def scan_pixel(spec, G0, N, T):
+    """(ink, flat) of one pixel from its gray value G0, its window's pixel count N and the window's sum T of the (inverted) values (rd_scan_pixel: steps 3 and 4 of
+    the contract); runs without a GPU"""
+    out = np.zeros(2, np.uint8)
+    if not lib().rd_scan_pixel(_scan_arg(spec).ctypes.data, int(G0), int(N), int(T), out.ctypes.data, out.ctypes.data + 1):
+        raise ValueError("rd_scan_pixel: invalid arguments (spec %r, G0 %r, N %r, T %r)" % (spec, G0, N, T))
+    return int(out[0]), int(out[1])
+
+
+def scan_limits():
+    """{"modes", "oversamplings", "max_radius", "tile_w", "tile_h"}: the legal values of a scan spec's fields and the kernel's tile (rd_scan_limits); runs without a GPU"""
+    a = np.zeros(8, np.int32)
+    lib().rd_scan_limits(a.ctypes.data)
+    bits = lambda v: tuple(k for k in range(31) if v >> k & 1)
+    return {"modes": bits(int(a[0])), "oversamplings": tuple(1 << k for k in bits(int(a[1]))), "max_radius": int(a[2]), "tile_w": int(a[3]), "tile_h": int(a[4])}
+
+
 class Rectifier(_Service):
     """The rd_rectifier extension: pw x ph BGR patches of up to max_quads quads per job, njobs jobs in flight (the contract: include/rectdetect_hip.h).  With
-    tensor=tensor_spec(...) a job writes model-ready tensors instead ("model-ready tensors" there): `out` then holds n * patch_bytes bytes of shape(n) and dtype."""
+    tensor=tensor_spec(...) a job writes model-ready tensors instead ("model-ready tensors" there), with scan=scan_spec(...) scanned pages ("scanned pages"):
+    `out` then holds n * patch_bytes bytes of shape(n) and dtype."""
     _name = "rectifier"
 
-    def __init__(self, pw, ph, max_quads=64, njobs=2, device=0, tensor=None):
+    def __init__(self, pw, ph, max_quads=64, njobs=2, device=0, tensor=None, scan=None):
+        if tensor is not None and scan is not None:
+            raise ValueError("Rectifier: tensor= and scan= exclude each other")
         self.pw, self.ph, self.max_quads, self.njobs = pw, ph, max_quads, njobs
         self.tensor = None if tensor is None else _spec_arg(tensor).copy()
-        if self.tensor is None:
+        self.scan = None if scan is None else _scan_arg(scan).copy()
+        if self.scan is not None:
+            self._create(device, pw, ph, max_quads, njobs, self.scan.ctypes.data, ctor="create_scan")
+        elif self.tensor is None:
             self._create(device, pw, ph, max_quads, njobs)
         else:
             self._create(device, pw, ph, max_quads, njobs, self.tensor.ctypes.data, ctor="create_tensor")
@@ -777,7 +834,9 @@ class Rectifier(_Service):
         return TENSOR_NUMPY[int(self.tensor["dtype"])] if self.tensor is not None else np.dtype(np.uint8)
 
     def shape(self, n):
-        """the shape of a job of n quads: (n, ph, pw, C) or, under TENSOR_NCHW, (n, C, ph, pw)"""
+        """the shape of a job of n quads: (n, ph, pw, C) or, under TENSOR_NCHW, (n, C, ph, pw); scanned pages: (n, ph, pw) or, under SCAN_BITS, (n, ph, (pw + 7) // 8)"""
+        if self.scan is not None:
+            return (n, self.ph, (self.pw + 7) // 8 if int(self.scan["mode"]) == SCAN_BITS else self.pw)
         if self.tensor is None:
             return (n, self.ph, self.pw, 3)
         C = 1 if int(self.tensor["channels"]) == TENSOR_GRAY else 3
@@ -799,7 +858,7 @@ class Rectifier(_Service):
         return self._wait(self.max_quads)
 
     def rectify(self, frame_bgr, quads):
-        """convenience: the (n, ph, pw, 3) patches - with a tensor spec: the array of shape(n) and dtype - of `quads` from a numpy BGR image, through pinned memory
+        """convenience: the (n, ph, pw, 3) patches - with a tensor or a scan spec: the array of shape(n) and dtype - of `quads` from a numpy BGR image, through pinned memory
         (one job, waited for)"""
         a = np.asarray(frame_bgr, dtype=np.uint8)
         q, n = _quads_arg(quads)

@@ -182,6 +182,11 @@ void rectify(hipStream_t s, uint8_t *out, int fmt, const rdpix::PixFrame &src, c
 // from one frame in format fmt (RD_PIX_*), one launch (quad = blockIdx.z)
 void rectify_tensor(hipStream_t s, void *out, int fmt, const rdpix::PixFrame &src, const RectifyQuad *quads, int n, int pw, int ph, const rd_tensor_spec &spec);
 
+// ---- rd_k_scan.hip: scanned pages (the contract: rectdetect_hip.h, "scanned pages")
+// n pages of pw x ph pixels in the mode of spec (legal for pw x ph: rd_scan_spec_ok), quad k's at out + k * rd_scan_bytes(spec, pw, ph), from the G plane
+// rectify_tensor made of the same quads with { U8, NHWC, GRAY, spec.oversample } (quad k's at plane + k * pw * ph), one launch (quad = blockIdx.z)
+void scan(hipStream_t s, uint8_t *out, const uint8_t *plane, const RectifyQuad *quads, int n, int pw, int ph, const rd_scan_spec &spec);
+
 // ---- rd_k_match.hip: matched quads (the contract: rectdetect_hip.h, "matched quads")
 // the signatures of n quads of one frame: quad k's G * G int8 values at sig + k * G * G (zeros for an invalid quad), its sa, saa ADDED to sums[2k], sums[2k+1]
 // (cleared by the caller); G in {8, 16, 32, 64}, m in {1, 2, 4}
