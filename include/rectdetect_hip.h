@@ -256,6 +256,34 @@ int rd_region_planes_device(int device, int stage, int iw, int ih, const int32_t
  * the tail's words, [27..31] 0.  Runs without a GPU. */
 void rd_region_limits(int iw, int ih, int32_t out[32]);
 
+/* test tap: the vote stage (oclrect.cl:427-464, reduceLS: rd_k_rect.hip's k_reduce_clean, k_reduce_claim, k_reduce_box) and the sampling kernel that reads its table and
+ * assembles a frame's hand-over block, on masks and boundary planes of the caller, through the frame path's own calls.  nsteps >= 1 steps of 1 <= nb <= 8 frames of iw x ih
+ * pixels; frame z keeps its scratch, list, table, claim and touched-slot list from step to step, as a detector's slot does from frame to frame (tables set up once).  Per step
+ * ONE set of launches for its nb frames: the polyline stage and its id plane (as rd_polyline_planes_device, lists of 16 bytes per pixel), the votes, the samples.
+ * In: masks, boundaries = nsteps * nb planes of iw * ih ints, step-major (mask: zero / non-zero; boundary: a component id per pixel, any int, <= 0 = none); ring_nonzero,
+ *   minerror, size_thre, form = nsteps values each (a launch shares them among its frames); clean = how a step undoes the tables' entries of the step before: 0 = the votes'
+ *   own first launch, 1 = the boundary labelling (run on a scratch region plane of the tap's), whose last kernel does it on the frame path, and votes that are told so;
+ *   max_records, pack_records = what the frame path passes the sampling kernel (records that get probes; records that travel in the block); rflags = nb * 256 ints, frame z's
+ *   region flags and status words as the block copies them; guard = the word every int of the probes buffer and the block holds before a step; probes_ints, pack_ints = ints
+ *   of a frame's probes buffer and block.
+ * Out, per step and frame (step-major): ids_out iw * ih ints, lslist_out 16 * iw * ih bytes, ctr_out 64 ints (rd_polyline_planes_device), table_out nentry * 5 ints (nentry =
+ *   iw * ih * 4 / 5), tlist_out nentry + 1 ints ([0] = count), claim_out nentry ints, probes_out probes_ints ints, pack_out pack_ints ints.
+ * Returns 0, or -1 without touching the device for a null pointer, a frame rd_detector_create refuses, nsteps < 1, nb outside 1..8, a form or clean other than 0 / 1, a negative
+ * size_thre, max_records < 5 (the block's leading 60 words are written by the first of max_records * 15 threads; one record of margin), pack_records < 1 (the header record travels always),
+ * probes_ints < max_records * 90 or pack_ints < 64 + pack_records * 104.  Fatal in a -DRD_BOUNDARY_FLATTEN=0 tuning build (the plane holds ids, not links).  Needs a GPU
+ * (fatal without one); not called by the frame path. */
+int rd_votes_planes_device(int device, int iw, int ih, int nsteps, int nb, const int32_t *masks, const int32_t *boundaries,
+                           const int32_t *ring_nonzero, const float *minerror, const int32_t *size_thre, const int32_t *form, int clean,
+                           int max_records, int pack_records, const int32_t *rflags, int32_t guard, int probes_ints, int pack_ints,
+                           int32_t *ids_out, void *lslist_out, int32_t *ctr_out, int32_t *table_out, int32_t *tlist_out, int32_t *claim_out, int32_t *probes_out, int32_t *pack_out);
+/* the constants the vote stage's crafted cases are placed by: out[0] distinct boundary ids of a 7 x 7 window one pass of the vote kernels holds, [1] slots of a block's claim
+ * hash and [2] the slots a claim tries before it goes straight to memory, [3] and [4] the same for a block's box hash, [5] threads per block and [6] blocks per frame of the
+ * claim and the box kernel, [7] frames per launch at most, [8] the word of an unclaimed `claim` entry, then the hand-over block's layout in ints: [9] where the region flags
+ * start and [10] how many there are, [11] where the absorption's status words start and [12] how many, [13] where those status words lie in rflags, [14] where the records
+ * start, [15] ints per record, [16] ints of probes per record; [17..23] 0.  Runs without a GPU. */
+#define RD_VOTES_LIMITS_INTS 24
+void rd_votes_limits(int32_t out[RD_VOTES_LIMITS_INTS]);
+
 /* ---- rectified patches: what is INSIDE a quad, as an upright image of fixed size (rd_k_rectify.hip, rd_rectify.hip).
  * The reference only draws outlines (rect.cpp, vidrect.cpp), so the arithmetic is defined here - exactly, so that an independent restatement (tests/rectify.py,
  * numpy float64) reproduces every byte.

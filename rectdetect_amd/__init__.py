@@ -115,6 +115,8 @@ def _declare(L):
         "rd_polyline_limits": (None, [vp]),
         "rd_region_planes_device": (ci, [ci, ci, ci, ci, vp, vp, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp]),
         "rd_region_limits": (None, [ci, ci, vp]),
+        "rd_votes_planes_device": (ci, [ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, ctypes.c_int32, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "rd_votes_limits": (None, [vp]),
         "rd_probe_pixels": (None, [cf, cf, cf, cf, ci, ci, vp]),
         "rd_post_run": (vp, [vp, ci, vp, ci, ci, cd]),
         "rd_post_helpers_configure": (None, [ci]),
@@ -1277,6 +1279,68 @@ def polyline_planes_device(mask, ring_nonzero, minerror, size_thre, lslist_bytes
         raise ValueError("rd_polyline_planes_device: invalid arguments")
     n = min(int(raw[0]), nbytes // 56 - 1)
     return raw[: 14 * (max(n, 0) + 1)].view(LS_DTYPE).copy(), ids, ctr
+
+
+VOTES_LIMIT_NAMES = ("RB_MAX", "CA_T", "CA_PROBES", "BA_T", "BA_PROBES", "block", "grid", "MAXB", "CLAIM_NONE", "PACK_FLAGS", "PACK_FLAGS_INTS", "PACK_STATUS", "PACK_STATUS_INTS",
+                     "RFLAGS_STATUS_AT", "PACK_RECORDS", "REC_INTS", "PROBE_INTS")
+VOTES_RFLAGS_INTS = 256
+
+
+def votes_limits():
+    """The constants the vote stage's crafted cases are placed by (rd_votes_limits) by name; runs without a GPU."""
+    out = np.zeros(24, np.int32)
+    lib().rd_votes_limits(out.ctypes.data)
+    return dict(zip(VOTES_LIMIT_NAMES, (int(v) for v in out)))
+
+
+class VotesFrame:
+    """What rd_votes_planes_device returns for one frame of one step: ids (2-D), segs (header + records, LS_DTYPE), list_ints (the whole list buffer), ctr (64), table
+    (nentry x 5), tlist (the entries, tlist[0] of them), claim (nentry), probes and pack (every int of the buffers, guard words included)."""
+
+    def __init__(self, shape, ids, raw, ctr, table, tlist, claim, probes, pack):
+        self.ids, self.list_ints, self.ctr, self.table, self.claim, self.probes, self.pack = ids.reshape(shape), raw, ctr, table.reshape(-1, 5), claim, probes, pack
+        n = min(max(int(raw[0]), 0), raw.size // 14 - 1)
+        self.segs = raw[: 14 * (n + 1)].view(LS_DTYPE).copy()
+        self.tlist_count = int(tlist[0])
+        self.tlist = tlist[1: 1 + min(max(self.tlist_count, 0), tlist.size - 1)].copy()
+
+
+def votes_planes_device(steps, clean=0, max_records=64, pack_records=64, rflags=None, guard=0x5a5a5a5a, probes_ints=None, pack_ints=None, device=0):
+    """The vote stage through the frame path's calls (rd_votes_planes_device).  steps = [dict(frames=[(mask, boundary), ...], ring=0/1, minerror=, size_thre=, form=0/1)], every
+    step with the same number of frames, every plane 2-D and of one size; frame z keeps its tables from step to step.  rflags: (frames, 256) ints.  probes_ints / pack_ints
+    default to what max_records / pack_records need plus 256 guard words.  Returns [[VotesFrame per frame] per step].  Needs a GPU."""
+    lim = votes_limits()
+    nsteps, nb = len(steps), len(steps[0]["frames"])
+    if any(len(s["frames"]) != nb for s in steps):
+        raise ValueError("votes_planes_device: every step takes the same number of frames")
+    masks = np.ascontiguousarray([[np.asarray(m, dtype=np.int32) for m, _ in s["frames"]] for s in steps], dtype=np.int32)
+    bounds = np.ascontiguousarray([[np.asarray(b, dtype=np.int32) for _, b in s["frames"]] for s in steps], dtype=np.int32)
+    if masks.ndim != 4 or masks.shape != bounds.shape:
+        raise ValueError("votes_planes_device: planes of different sizes")
+    ih, iw = masks.shape[2:]
+    n, k = iw * ih, nsteps * nb
+    nentry = n * 4 // 5
+    ring = np.array([int(s.get("ring", 0)) for s in steps], np.int32)
+    minerror = np.array([float(s.get("minerror", 1.0)) for s in steps], np.float32)
+    size_thre = np.array([int(s.get("size_thre", 10)) for s in steps], np.int32)
+    form = np.array([int(s.get("form", 0)) for s in steps], np.int32)
+    rf = np.zeros((nb, VOTES_RFLAGS_INTS), np.int32) if rflags is None else np.ascontiguousarray(rflags, dtype=np.int32)
+    if rf.shape != (nb, VOTES_RFLAGS_INTS):
+        raise ValueError("votes_planes_device: rflags is (frames, %d) ints" % VOTES_RFLAGS_INTS)
+    if probes_ints is None:
+        probes_ints = max(int(max_records), 0) * lim["PROBE_INTS"] + 256
+    if pack_ints is None:
+        pack_ints = lim["PACK_RECORDS"] + max(int(pack_records), 0) * (lim["REC_INTS"] + lim["PROBE_INTS"]) + 256
+    guard = int(np.array([guard & 0xFFFFFFFF], np.uint32).view(np.int32)[0])
+    ids, raw, ctr = np.zeros((k, n), np.int32), np.zeros((k, n * 4), np.int32), np.zeros((k, 64), np.int32)
+    table, tlist, claim = np.zeros((k, nentry * 5), np.int32), np.zeros((k, nentry + 1), np.int32), np.zeros((k, nentry), np.int32)
+    probes, pack = np.zeros((k, int(probes_ints)), np.int32), np.zeros((k, int(pack_ints)), np.int32)
+    if lib().rd_votes_planes_device(int(device), iw, ih, nsteps, nb, masks.ctypes.data, bounds.ctypes.data, ring.ctypes.data, minerror.ctypes.data, size_thre.ctypes.data,
+                                    form.ctypes.data, int(clean), int(max_records), int(pack_records), rf.ctypes.data, guard, int(probes_ints), int(pack_ints),
+                                    ids.ctypes.data, raw.ctypes.data, ctr.ctypes.data, table.ctypes.data, tlist.ctypes.data, claim.ctypes.data, probes.ctypes.data,
+                                    pack.ctypes.data) != 0:
+        raise ValueError("rd_votes_planes_device: invalid arguments")
+    return [[VotesFrame((ih, iw), *(a[s * nb + z] for a in (ids, raw, ctr, table, tlist, claim, probes, pack))) for z in range(nb)] for s in range(nsteps)]
 
 
 REGION_INFO_INTS = 144

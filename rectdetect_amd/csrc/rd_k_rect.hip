@@ -1678,30 +1678,34 @@ __device__ __forceinline__ unsigned ls_slot(int id, int bid, int nentry) { retur
 // sparse: one thread per chain pixel left by the polyline stage (raster-ordered compact list, so the compact index orders
 // pixels like the pixel index does)
 // The RB_MAX smallest distinct boundary ids greater than `floor` inside a 7x7 window, ascending, in registers (unused
-// entries 0x7fffffff); returns whether larger ids remain.  Callers loop: windows with more ids than fit (rare) simply take
+// entries RB_NONE); returns whether larger ids remain.  Callers loop: windows with more ids than fit (rare) simply take
 // another pass with floor = the largest id of the previous one, so every pass issues its dependent loads together.
 #define RB_MAX 8
-#define RB_NONE 0x7fffffff
+#define RV_NT 256          // threads of a block of k_reduce_claim and k_reduce_box (the kernels' strides and launch bounds name the number itself)
+#define RV_GRID 512        // their blocks per frame
+// (RB_NONE is no id: ids are 1 .. 0x7fffffff.  Cells are compared as unsigned words, where RB_NONE lies above every id and below every negative cell - with
+//  0x7fffffff in its place, as it once was, a cell holding that id was never collected and its votes were lost)
+#define RB_NONE ((int)0x80000000u)
 __device__ __forceinline__ bool rb_collect(const int (&win)[49], int floor, int (&bs)[RB_MAX]) {
   // repeated minimum extraction: pass q finds the smallest id above the one of pass q-1; windows hold one to three distinct ids
   // as a rule, and the passes stop as soon as no lane of the wave finds another one
 #pragma unroll
   for (int q = 0; q < RB_MAX; q++) bs[q] = RB_NONE;
-  int cur = floor;
+  unsigned cur = (unsigned)floor;
 #pragma unroll
   for (int q = 0; q < RB_MAX; q++) {
-    int m = RB_NONE;
+    unsigned m = (unsigned)RB_NONE;
 #pragma unroll
-    for (int k = 0; k < 49; k++) { const int b = win[k]; m = (b > cur && b < m) ? b : m; }
-    bs[q] = m;
-    cur = m;                              // (RB_NONE once exhausted: nothing is larger)
-    if (!__any(m != RB_NONE)) break;
+    for (int k = 0; k < 49; k++) { const unsigned b = (unsigned)win[k]; m = (b > cur && b < m) ? b : m; }      // (a cell <= 0 is 0 or above RB_NONE: never taken)
+    bs[q] = (int)m;
+    cur = m;                              // (RB_NONE once exhausted: no id is larger)
+    if (!__any(bs[q] != RB_NONE)) break;
   }
   bool more = false;
   if (__any(bs[RB_MAX - 1] != RB_NONE)) {
     const int last = bs[RB_MAX - 1];
 #pragma unroll
-    for (int k = 0; k < 49; k++) more = more || (last != RB_NONE && win[k] > last);
+    for (int k = 0; k < 49; k++) more = more || (last != RB_NONE && win[k] > last);      // (signed: negative cells are no ids; `last` is an id here)
   }
   return more;
 }
@@ -1761,6 +1765,7 @@ __global__ __launch_bounds__(1024) void k_reduce_clean(const rdk::PolyFrames FRS
 // (claims are aggregated per block like the box updates below: slot -> smallest claiming pixel in an LDS hash, one atomicMin per
 //  slot and block at the end; the one that finds the slot unclaimed appends it to tlist)
 #define CA_T 1024
+#define CA_PROBES 32      // slots of the hash a claim tries before it goes straight to memory
 __global__ __launch_bounds__(256) void k_reduce_claim(const rdk::PolyFrames FRS, int iw, int ih, int nentry) {
   RD_VFRAME;
   int *claim = FRM.claim, *tlist = FRM.tlist;
@@ -1800,7 +1805,12 @@ __global__ __launch_bounds__(256) void k_reduce_claim(const rdk::PolyFrames FRS,
     bool more = true;
     while (__any(more)) {               // one pass for all but a few pixels
       int bs[RB_MAX];
-      const bool again = more && rb_collect(win, floor, bs);
+      bool again = false;
+      if (more) again = rb_collect(win, floor, bs);
+      else {        // (a lane that is done while others take another pass: no ids, and a floor that is not the first pass's)
+#pragma unroll
+        for (int q = 0; q < RB_MAX; q++) bs[q] = RB_NONE;
+      }
       unsigned slot[RB_MAX];
 #pragma unroll
       for (int q = 0; q < RB_MAX; q++) slot[q] = ls_slot(id, bs[q] == RB_NONE ? 0 : bs[q], nentry);
@@ -1827,7 +1837,7 @@ __global__ __launch_bounds__(256) void k_reduce_claim(const rdk::PolyFrames FRS,
           const int kprev = atomicCAS(&keys[h], -1, (int)slot[q]);
           if (kprev == -1 || kprev == (int)slot[q]) { atomicMin(&vals[h], i); break; }
           h = (h + 1) & (CA_T - 1);
-          if (++probes == 32) {         // table full of other slots: straight to memory
+          if (++probes == CA_PROBES) {  // table full of other slots: straight to memory
             if (atomicMin(&claim[slot[q]], i) == 0x7f7f7f7f) tlist[1 + atomicAdd(&tlist[0], 1)] = (int)slot[q];
             break;
           }
@@ -1850,10 +1860,11 @@ __global__ __launch_bounds__(256) void k_reduce_claim(const rdk::PolyFrames FRS,
 // are served one after the other (measured: the longest segment of a frame set the duration of the kernel).  The block keeps a
 // small hash (slot -> the four maxima) in LDS and touches each of its slots once in global memory at the end.
 #define BA_T 512
+#define BA_PROBES 16      // slots of the hash a box update tries before it goes straight to memory
 struct BoxAgg { int keys[BA_T]; int vals[BA_T * 4]; };
 __device__ __forceinline__ void boxagg_add(BoxAgg &A, int *table, unsigned slot, int v1, int v2, int v3, int v4) {
   unsigned h = (slot * 2654435761u) >> 23;
-  for (int probes = 0; probes < 16; probes++) {
+  for (int probes = 0; probes < BA_PROBES; probes++) {
     const int kprev = atomicCAS(&A.keys[h], -1, (int)slot);
     if (kprev == -1 || kprev == (int)slot) {
       atomicMax(&A.vals[h * 4 + 0], v1); atomicMax(&A.vals[h * 4 + 1], v2); atomicMax(&A.vals[h * 4 + 2], v3); atomicMax(&A.vals[h * 4 + 3], v4);
@@ -2140,8 +2151,18 @@ void reduce_ls_init(hipStream_t s, int *table, int *claim, int *tlist, int nentr
 void reduce_ls(hipStream_t s, const PolyFrame *frames_host, int nb, int iw, int ih, int nentry, int tables_are_clean) {
   const PolyFrames frames = pack_frames(frames_host, nb);
   if (!tables_are_clean) hipLaunchKernelGGL(k_reduce_clean, dim3(1, 1, nb), dim3(1024), 0, s, frames);       // undo the previous use
-  hipLaunchKernelGGL(k_reduce_claim, dim3(512, 1, nb), dim3(256), 0, s, frames, iw, ih, nentry);
-  hipLaunchKernelGGL(k_reduce_box, dim3(512, 1, nb), dim3(256), 0, s, frames, iw, ih, nentry);
+  hipLaunchKernelGGL(k_reduce_claim, dim3(RV_GRID, 1, nb), dim3(RV_NT), 0, s, frames, iw, ih, nentry);
+  hipLaunchKernelGGL(k_reduce_box, dim3(RV_GRID, 1, nb), dim3(RV_NT), 0, s, frames, iw, ih, nentry);
+}
+
+// [0] RB_MAX, [1] CA_T, [2] CA_PROBES, [3] BA_T, [4] BA_PROBES, [5] threads and [6] blocks per frame of k_reduce_claim and k_reduce_box, [7] RD_MAXB, [8] the word of an
+// unclaimed entry of `claim`, [9] RD_PACK_FLAGS, [10] RD_REGION_FIRST_BUDGET, [11] RD_PACK_STATUS, [12] RD_PACK_STATUS_INTS, [13] RD_REGION_STATUS_AT, [14] RD_PACK_RECORDS,
+// [15] RD_REC_INTS, [16] RD_PROBE_INTS, [17..23] 0
+void votes_limits(int out[24]) {
+  for (int i = 0; i < 24; i++) out[i] = 0;
+  out[0] = RB_MAX; out[1] = CA_T; out[2] = CA_PROBES; out[3] = BA_T; out[4] = BA_PROBES; out[5] = RV_NT; out[6] = RV_GRID; out[7] = RD_MAXB; out[8] = 0x7f7f7f7f;
+  out[9] = RD_PACK_FLAGS; out[10] = RD_REGION_FIRST_BUDGET; out[11] = RD_PACK_STATUS; out[12] = RD_PACK_STATUS_INTS; out[13] = RD_REGION_STATUS_AT; out[14] = RD_PACK_RECORDS;
+  out[15] = RD_REC_INTS; out[16] = RD_PROBE_INTS;
 }
 
 void sample_segments(hipStream_t s, const PolyFrame *frames_host, int nb, int max_records, int iw, int ih, int nentry, int pack_records) {

@@ -152,6 +152,8 @@ static_assert(RD_PACK_FLAGS == RD_PACK_POLYCTR + RD_PACK_POLYCTR_INTS && RD_PACK
 // per segment, 15 probe points: {boundary id, table slot owner, 4 box values} -> out[(seg*15 + k)*6 ..]
 // pack (may be null): the hand-over block - counters / flags, pack_records records, then their probes
 void sample_segments(hipStream_t s, const PolyFrame *frames, int nb, int max_records, int iw, int ih, int nentry, int pack_records);
+// the constants the crafted cases of the vote stage are placed by (rd_votes_limits; the header documents the order)
+void votes_limits(int out[24]);
 
 // ---- rd_k_post.hip: segments + probes -> rectangles on the device (candidate funnel + pose estimation, one wave per candidate)
 size_t post_scratch_ints();      // ints of PolyFrame::post_scratch

@@ -1,4 +1,4 @@
-// rectdetect-mi355x: the stages' test taps - the device post-process, the polyline stage and the region stage on inputs of the caller, each once, on a stream and
+// rectdetect-mi355x: the stages' test taps - the device post-process, the polyline stage, the region stage and the vote stage on inputs of the caller, each on a stream and
 // buffers of its own.  None touches a detector; what a tap shares with the frame path it calls (rd_detector.h), it does not restate.
 #include "rd_detector.h"
 
@@ -174,6 +174,97 @@ int rd_region_planes_device(int device, int stage, int iw, int ih, const int32_t
   RD_HIP(hipStreamDestroy(st));
   dfree(d_sb); dfree(d_mm); dfree(d_tlist); dfree(d_claim); dfree(d_table); dfree(d_d2s); dfree(d_scratch2);
   dfree(d_boundary); dfree(d_bsrc); dfree(d_region); dfree(d_rsize); dfree(d_region0); dfree(d_pix);
+  return 0;
+}
+
+// ---- test taps of the vote stage (neither is on the frame path)
+void rd_votes_limits(int32_t out[RD_VOTES_LIMITS_INTS]) { rdk::votes_limits(out); }
+
+// The frame path's sparse tail on masks and boundary planes of the caller: per step rdk::polyline, rdk::polyline_ids, rdk::reduce_ls and rdk::sample_segments, one set of
+// launches for the step's nb frames.  Frame z keeps its scratch, list, table, claim and tlist from step to step, as a slot does from frame to frame; how a step undoes
+// the one before is the caller's choice (clean).  The planes hold ids, not links: refused in a -DRD_BOUNDARY_FLATTEN=0 build, as rd_postprocess_planes_device is.
+int rd_votes_planes_device(int device, int iw, int ih, int nsteps, int nb, const int32_t *masks, const int32_t *boundaries,
+                           const int32_t *ring_nonzero, const float *minerror, const int32_t *size_thre, const int32_t *form, int clean,
+                           int max_records, int pack_records, const int32_t *rflags, int32_t guard, int probes_ints, int pack_ints,
+                           int32_t *ids_out, void *lslist_out, int32_t *ctr_out, int32_t *table_out, int32_t *tlist_out, int32_t *claim_out, int32_t *probes_out, int32_t *pack_out) {
+  if (!RD_BOUNDARY_FLATTEN) exitf(-1, "rd_votes_planes_device: needs a build with RD_BOUNDARY_FLATTEN=1 (the plane holds ids, not links)\n");
+  if (!masks || !boundaries || !ring_nonzero || !minerror || !size_thre || !form || !rflags || !ids_out || !lslist_out || !ctr_out || !table_out || !tlist_out || !claim_out ||
+      !probes_out || !pack_out) return -1;
+  if (iw < 16 || ih < 16 || (long long)iw * ih >= (1ll << 25) || nsteps < 1 || nb < 1 || nb > RD_MAXB || (clean != 0 && clean != 1)) return -1;      // (rd_detector_create's limits)
+  // the sampling kernel's first RD_PACK_STATUS + RD_PACK_STATUS_INTS threads write the block's counters, flags, status words and header record, and the launch is sized by
+  // max_records * 15 threads: four records' threads cover them without counting on the launch's rounding to whole blocks, the tap asks for one more; the header record
+  // needs room in the block
+  if (max_records < 5 || pack_records < 1 || (long long)probes_ints < (long long)max_records * RD_PROBE_INTS ||
+      (long long)pack_ints < RD_PACK_RECORDS + (long long)pack_records * (RD_REC_INTS + RD_PROBE_INTS)) return -1;
+  for (int s = 0; s < nsteps; s++)
+    if ((form[s] != 0 && form[s] != 1) || size_thre[s] < 0) return -1;
+  RD_HIP(hipSetDevice(device));
+  const size_t N = (size_t)iw * ih;
+  const int n = (int)N, nentry = n * 4 / 5;
+  const size_t ls_bytes = N * 16;
+  // what frame z keeps: a scratch region plane with its marks and components (the planes of the labelling call whose last kernel undoes the tables), table, claim, tlist -
+  // one allocation, frame z's part z * zs bytes behind frame 0's, as a slot's planes lie
+  const size_t keep_ints = ((3 * N + (size_t)nentry * 7 + 1) + 63) / 64 * 64, zs = keep_ints * sizeof(int);
+  int *d_keep = dnew<int>(keep_ints * nb);
+  int *k_region = d_keep, *k_marks = k_region + N, *k_label = k_marks + N, *k_table = k_label + N, *k_claim = k_table + (size_t)nentry * 5, *k_tlist = k_claim + nentry;
+  int *d_rflags = dnew<int>((size_t)nb * 256);
+  hipStream_t st = NULL;
+  RD_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  RD_HIP(hipMemsetAsync(d_keep, 0, keep_ints * nb * sizeof(int), st));
+  RD_HIP(hipMemcpyAsync(d_rflags, rflags, (size_t)nb * 256 * sizeof(int), hipMemcpyHostToDevice, st));
+  rdk::PolyScratch *ps[RD_MAXB];
+  rdk::PolyFrame f[RD_MAXB];
+  int *d_mask[RD_MAXB], *d_boundary[RD_MAXB], *d_ids[RD_MAXB], *d_probes[RD_MAXB], *h_pack[RD_MAXB];
+  char *d_ls[RD_MAXB];
+  for (int z = 0; z < nb; z++) {
+    ps[z] = rdk::poly_scratch_create(iw, ih);
+    d_mask[z] = dnew<int>(N); d_boundary[z] = dnew<int>(N); d_ids[z] = dnew<int>(N); d_probes[z] = dnew<int>((size_t)probes_ints);
+    d_ls[z] = dnew<char>(ls_bytes + 56);
+    RD_HIP(hipMemsetAsync(d_ls[z], 0, ls_bytes + 56, st));
+    int *pack_dev = NULL;
+    RD_HIP(hipHostMalloc((void **)&h_pack[z], (size_t)pack_ints * sizeof(int), hipHostMallocDefault));
+    RD_HIP(hipHostGetDevicePointer((void **)&pack_dev, h_pack[z], 0));
+    memset(&f[z], 0, sizeof(f[z]));
+    f[z].ps = *ps[z]; f[z].in = d_mask[z]; f[z].lslist = d_ls[z]; f[z].ids = d_ids[z]; f[z].boundary = d_boundary[z];
+    f[z].table = k_table + z * keep_ints; f[z].claim = k_claim + z * keep_ints; f[z].tlist = k_tlist + z * keep_ints;
+    f[z].probes = d_probes[z]; f[z].pack = pack_dev; f[z].rflags = d_rflags + (size_t)z * 256;
+    rdk::reduce_ls_init(st, f[z].table, f[z].claim, f[z].tlist, nentry);
+  }
+  for (int s = 0; s < nsteps; s++) {
+    for (int z = 0; z < nb; z++) {
+      const size_t at = (size_t)s * nb + z;
+      RD_HIP(hipMemcpyAsync(d_mask[z], masks + at * N, N * sizeof(int), hipMemcpyHostToDevice, st));
+      RD_HIP(hipMemcpyAsync(d_boundary[z], boundaries + at * N, N * sizeof(int), hipMemcpyHostToDevice, st));
+      RD_HIP(hipMemsetD32Async((hipDeviceptr_t)d_probes[z], guard, (size_t)probes_ints, st));
+      for (int i = 0; i < pack_ints; i++) h_pack[z][i] = guard;      // (the step before has been waited for)
+    }
+    // clean 1: the frame path's order - the boundary labelling, whose last kernel undoes the tables' entries, then votes that are told so
+    if (clean) rdk::label8_boundary(st, k_label, k_marks, k_region, iw, ih, k_table, k_claim, k_tlist, nb, zs, RD_BOUNDARY_FLATTEN);
+    rdk::polyline(st, f, nb, (int)ls_bytes, ring_nonzero[s] ? 1 : 0, minerror[s], size_thre[s], iw, ih, form[s]);
+    rdk::polyline_ids(st, f, nb, n);
+    rdk::reduce_ls(st, f, nb, iw, ih, nentry, clean);
+    rdk::sample_segments(st, f, nb, max_records, iw, ih, nentry, pack_records);
+    rdrt::check_launch("rd_votes_planes_device");
+    for (int z = 0; z < nb; z++) {
+      const size_t at = (size_t)s * nb + z;
+      RD_HIP(hipMemcpyAsync(ids_out + at * N, d_ids[z], N * sizeof(int), hipMemcpyDeviceToHost, st));
+      RD_HIP(hipMemcpyAsync((char *)lslist_out + at * ls_bytes, d_ls[z], ls_bytes, hipMemcpyDeviceToHost, st));
+      RD_HIP(hipMemcpyAsync(ctr_out + at * 64, rdk::poly_scratch_counters(ps[z]), 64 * sizeof(int), hipMemcpyDeviceToHost, st));
+      RD_HIP(hipMemcpyAsync(table_out + at * nentry * 5, f[z].table, (size_t)nentry * 5 * sizeof(int), hipMemcpyDeviceToHost, st));
+      RD_HIP(hipMemcpyAsync(claim_out + at * nentry, f[z].claim, (size_t)nentry * sizeof(int), hipMemcpyDeviceToHost, st));
+      RD_HIP(hipMemcpyAsync(tlist_out + at * (nentry + 1), f[z].tlist, ((size_t)nentry + 1) * sizeof(int), hipMemcpyDeviceToHost, st));
+      RD_HIP(hipMemcpyAsync(probes_out + at * probes_ints, d_probes[z], (size_t)probes_ints * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    RD_HIP(hipStreamSynchronize(st));
+    for (int z = 0; z < nb; z++) memcpy(pack_out + ((size_t)s * nb + z) * pack_ints, h_pack[z], (size_t)pack_ints * sizeof(int));
+  }
+  RD_HIP(hipStreamDestroy(st));
+  for (int z = 0; z < nb; z++) {
+    RD_HIP(hipHostFree(h_pack[z]));
+    dfree(d_ls[z]); dfree(d_probes[z]); dfree(d_ids[z]); dfree(d_boundary[z]); dfree(d_mask[z]);
+    rdk::poly_scratch_destroy(ps[z]);
+  }
+  dfree(d_rflags); dfree(d_keep);
   return 0;
 }
 
