@@ -400,7 +400,7 @@ void rd_tensor_limits(int32_t out[4]);
  * ordinary rd_rectifier: rd_rectifier_enqueue, rd_rectifier_wait, rd_rectifier_destroy and rd_detector_rectify_polled work on it with every pixel format, frame
  * kind and output kind, and `out` holds n * rd_rectifier_patch_bytes(r) bytes. */
 rd_rectifier *rd_rectifier_create_tensor(int device, int pw, int ph, int max_quads, int njobs, const rd_tensor_spec *spec);
-/* the bytes of one quad's output: pw * ph * 3 for a rectifier made by rd_rectifier_create, rd_tensor_bytes or rd_scan_bytes of the spec for the others; 0 for NULL */
+/* the bytes of one quad's output: pw * ph * 3 for a rectifier made by rd_rectifier_create, rd_tensor_bytes, rd_scan_bytes or rd_grade_bytes of the spec for the others; 0 for NULL */
 size_t rd_rectifier_patch_bytes(const rd_rectifier *r);
 
 /* -- scanned pages: the quad as a clean page - the patch's luma divided by its local mean (shading correction) or compared with it (adaptive threshold), as bytes
@@ -441,6 +441,55 @@ void rd_scan_limits(int32_t out[8]);
  * an ordinary rd_rectifier: rd_rectifier_enqueue, rd_rectifier_wait, rd_rectifier_destroy and rd_detector_rectify_polled work on it with every pixel format, frame
  * kind and output kind, and `out` holds n * rd_rectifier_patch_bytes(r) bytes. */
 rd_rectifier *rd_rectifier_create_scan(int device, int pw, int ph, int max_quads, int njobs, const rd_scan_spec *spec);
+
+/* -- graded quads: not what is in the quad but whether this frame's view of it is worth keeping - per cell of a cells x cells grid over the patch how many pixels
+ * there are, how many are black, how many blown out, how many lie on an edge, and the sums from which mean, contrast and the variance of the Laplacian (sharpness)
+ * follow; optionally the patch's histogram (rd_k_grade.hip, rd_rectify.hip, rd_grade_host.c).  A few dozen bytes per quad instead of pw * ph.  Two launches per job:
+ * the G plane by the tensor kernel, then the statistics.  Exact, in integers, like everything above: tests/grade.py restates it in numpy.
+ *
+ * A spec is LEGAL for pw x ph when cells is 1, 2, 4 or 8, 0 <= dark <= 255, 0 <= bright <= 255, 0 <= edge <= 1020, oversample m is 1, 2 or 4, hist is 0 or 1, both
+ * reserved words are 0, pw >= cells and ph >= cells (no cell is empty), pw*m <= 16384 and ph*m <= 16384.
+ *
+ * Quad k:
+ *   1. G(i, j) is, byte for byte, the element of the tensor spec { RD_TENSOR_U8, RD_TENSOR_NHWC, RD_TENSOR_GRAY, m } for the same quad, frame, pw and ph (steps 1-4
+ *      of "model-ready tensors"; step 1 of "scanned pages" without the inversion).
+ *   2. L(i, j) = G(i-1, j) + G(i+1, j) + G(i, j-1) + G(i, j+1) - 4*G(i, j), every neighbour index clamped to the patch ([0, pw-1], [0, ph-1]: the border is
+ *      replicated).  |L| <= 4 * 255 = 1020.
+ *   3. Pixel (i, j) belongs to cell (cx, cy) = ((i*cells) / pw, (j*cells) / ph), integer divisions; the cell's record is number cy*cells + cx.  A pixel's L counts
+ *      in the pixel's own cell, whatever cells its neighbours lie in.
+ *   4. The record of a cell, over the pixels of the cell:  n = their count;  lo = how many have G <= dark;  hi = how many have G >= bright;  ne = how many have
+ *      |L| >= edge;  sg = the sum of G, sgg of G*G, sl of L, sll of L*L.
+ *      At 16384 x 16384 and cells = 1:  n <= 2^28,  sg <= 2^28 * 255,  sgg <= 2^28 * 65 025,  |sl| <= 2^28 * 1020,  sll <= 2^28 * 1 040 400 = 279 280 248 422 400 < 2^63:
+ *      int64 holds every sum, int32 every count.  int32 would not hold the sums: a 258 x 258 patch of 255s has sgg = 66 564 * 65 025 = 4 328 324 100 > 2^32, and a
+ *      64 x 128 checkerboard of 0 and 255 has sll > 2^32.
+ *   5. Output, quad k at out + k * rd_rectifier_patch_bytes(r): cells*cells records of 48 bytes (rd_grade_cell), record number c at byte 48*c; with hist set, 256
+ *      uint32_t follow them: word v counts the pixels of the whole patch with G == v.  patch_bytes = 48*cells*cells + 1024*hist.
+ *      An invalid quad (status 0) gives all-zero bytes.  The job's n * rd_rectifier_patch_bytes(r) bytes are written and nothing else.  The bytes are complete when
+ *      rd_rectifier_wait returns: they are zeroed and added to on the job's stream, and no intermediate value is visible in them after the wait.  `out` must be
+ *      8-byte aligned for a grade rectifier: rd_rectifier_enqueue (and rd_detector_rectify_polled) return -1 with nothing enqueued when it is not. */
+typedef struct { int32_t cells, dark, bright, edge, oversample, hist, reserved[2]; } rd_grade_spec;   /* 32 bytes */
+typedef struct { int32_t n, lo, hi, ne; int64_t sg, sgg, sl, sll; } rd_grade_cell;                   /* 48 bytes */
+/* host only, no GPU needed (rd_grade_host.c).  1 when the spec is legal for pw x ph, else 0 (a NULL spec too) */
+int rd_grade_spec_ok(const rd_grade_spec *spec, int pw, int ph);
+/* the bytes of one quad's output: 48 * cells * cells + 1024 * hist; 0 for a spec that is not legal for pw x ph */
+size_t rd_grade_bytes(const rd_grade_spec *spec, int pw, int ph);
+/* step 3: the number of the record that pixel (i, j) counts in; -1 for a spec that is not legal for pw x ph or a pixel outside the patch */
+int rd_grade_cell_of(const rd_grade_spec *spec, int pw, int ph, int i, int j);
+/* out[0] <- the legal cells ORed together (1 | 2 | 4 | 8), out[1] <- the legal oversamplings ORed together (1 | 2 | 4), out[2] <- the largest edge (1020),
+ * out[3], out[4] <- the width and the height, in pixels, of the tile a block of the kernel reduces, out[5] <- sizeof(rd_grade_cell) (48), out[6] <- the bytes of
+ * the histogram (1024), out[7] <- 0 */
+void rd_grade_limits(int32_t out[8]);
+/* the variance of the Laplacian over a cell, the usual measure of focus: 0 for n == 0 (or a NULL cell), else, in double, uncontracted, in exactly this order,
+ * ((double)sll - ((double)sl * (double)sl) / (double)n) / (double)n.  Records may be added field by field first: the sharpness of a whole patch is that of the sum */
+double rd_grade_sharpness(const rd_grade_cell *cell);
+/* the smallest v in 0 .. 255 with cum(v) * den >= num * total, cum(v) = hist[0] + .. + hist[v], total = cum(255), in 64-bit integers: the value below which num / den
+ * of the pixels lie (1, 100: the 1st percentile; 99, 100: the 99th - a `white` for a scan spec from the page itself).  -1 for a NULL hist, den < 1, den > 1 048 576
+ * (the products then fit 64 bits: total < 2^40), num < 0, num > den or an empty histogram */
+int rd_grade_percentile(const uint32_t hist[256], int num, int den);
+/* A rectifier whose jobs write graded quads.  NULL for the bad arguments of rd_rectifier_create, a NULL spec or a spec that is not legal for pw x ph.  The handle is
+ * an ordinary rd_rectifier: rd_rectifier_enqueue, rd_rectifier_wait, rd_rectifier_destroy and rd_detector_rectify_polled work on it with every pixel format, frame
+ * kind and output kind, and `out` holds n * rd_rectifier_patch_bytes(r) bytes, 8-byte aligned. */
+rd_rectifier *rd_rectifier_create_grade(int device, int pw, int ph, int max_quads, int njobs, const rd_grade_spec *spec);
 
 /* ---- annotated frames: rectangles' outlines and line segments drawn INTO a frame on the device (rd_k_annotate.hip, rd_annotate.hip) - the picture vidrect.cpp /
  * rect.cpp (showRect) and vidpoly.cpp / poly.cpp make with OpenCV's line() on the host, for frames that never leave HBM.  OpenCV's round brush is not restated; the

@@ -12,7 +12,7 @@ Mirrors of the reference programs' call sequences:
   * :class:`PolylineDetector` - its polyline kind: poly.cpp / vidpoly.cpp per frame, several frames in flight
   * :class:`Rectifier` - the ``rd_rectifier`` extension: what is inside detected quads as upright patches of fixed size, or - with a
     :func:`tensor_spec` - as model-ready tensors (float, planar, normalised, box-filtered), or - with a :func:`scan_spec` - as scanned pages (shading-corrected
-    gray, bilevel bytes or packed bit rows)
+    gray, bilevel bytes or packed bit rows), or - with a :func:`grade_spec` - as graded quads (per-cell sharpness, exposure and glare records, a histogram)
   * :class:`Annotator` - the ``rd_annotator`` extension: rectangles' outlines and line segments drawn into frames on the device
   * :class:`Compositor` - the ``rd_compositor`` extension: a colour or an image written into the quads of a frame on the device
   * :class:`Matcher` - the ``rd_matcher`` extension: which template of a library is inside each quad, decided on the device
@@ -53,6 +53,11 @@ TENSOR_NUMPY = {TENSOR_U8: np.dtype(np.uint8), TENSOR_F16: np.dtype(np.float16),
 SCAN_FLAT, SCAN_BILEVEL, SCAN_BITS = range(3)
 SCAN_SPEC_DTYPE = np.dtype([(n, "<i4") for n in ("mode", "radius", "k", "d", "white", "oversample", "invert", "reserved")])
 assert SCAN_SPEC_DTYPE.itemsize == 32
+# a rectifier's grade spec and the record of a cell (rd_grade_spec, rd_grade_cell; the contract is in include/rectdetect_hip.h, "graded quads")
+GRADE_SPEC_DTYPE = np.dtype([("cells", "<i4"), ("dark", "<i4"), ("bright", "<i4"), ("edge", "<i4"), ("oversample", "<i4"), ("hist", "<i4"), ("reserved", "<i4", (2,))])
+GRADE_CELL_DTYPE = np.dtype([("n", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("ne", "<i4"), ("sg", "<i8"), ("sgg", "<i8"), ("sl", "<i8"), ("sll", "<i8")])
+assert GRADE_SPEC_DTYPE.itemsize == 32 and GRADE_CELL_DTYPE.itemsize == 48
+GRADE_CELL_BYTES, GRADE_HIST_BYTES, GRADE_MAX_EDGE = 48, 1024, 1020
 ANNOT_SEG_ALL, ANNOT_SEG_CHAINS = 0, 1
 
 # pixel formats of enqueue_planes (rd_detector_enqueue_planes; the conversion contract is in include/rectdetect_hip.h)
@@ -144,6 +149,14 @@ def _declare(L):
         "rd_scan_pixel": (ci, [vp, ci, ci, ci, vp, vp]),
         "rd_scan_limits": (None, [vp]),
         "rd_rectifier_create_scan": (vp, [ci, ci, ci, ci, ci, vp]),
+        # graded quads (rd_rectify.hip, rd_grade_host.c)
+        "rd_grade_spec_ok": (ci, [vp, ci, ci]),
+        "rd_grade_bytes": (cz, [vp, ci, ci]),
+        "rd_grade_cell_of": (ci, [vp, ci, ci, ci, ci]),
+        "rd_grade_limits": (None, [vp]),
+        "rd_grade_sharpness": (cd, [vp]),
+        "rd_grade_percentile": (ci, [vp, ci, ci]),
+        "rd_rectifier_create_grade": (vp, [ci, ci, ci, ci, ci, vp]),
         # annotated frames (rd_annotate.hip)
         "rd_annot_covers": (ci, [vp, ci, ci]),
         "rd_annot_touches": (ci, [vp, ci, ci, ci, ci]),
@@ -806,19 +819,84 @@ def scan_limits():
     return {"modes": bits(int(a[0])), "oversamplings": tuple(1 << k for k in bits(int(a[1]))), "max_radius": int(a[2]), "tile_w": int(a[3]), "tile_h": int(a[4])}
 
 
+def grade_spec(cells=4, dark=8, bright=247, edge=64, oversample=1, hist=False):
+    """an rd_grade_spec as a GRADE_SPEC_DTYPE record: a cells x cells grid of records (1, 2, 4 or 8), a pixel is black at G <= dark, blown out at G >= bright, on an
+    edge at |L| >= edge, oversample 1, 2 or 4, hist for the patch's 256-bin histogram behind the records.  Whether it is legal is decided where it is used
+    (grade_spec_ok, Rectifier)."""
+    s = np.zeros((), GRADE_SPEC_DTYPE)
+    s["cells"], s["dark"], s["bright"], s["edge"], s["oversample"], s["hist"] = cells, dark, bright, edge, oversample, int(hist)
+    return s
+
+
+def _grade_arg(spec):
+    return np.ascontiguousarray(spec, dtype=GRADE_SPEC_DTYPE).reshape(())
+
+
+def grade_spec_ok(spec, pw, ph):
+    """whether a grade spec is legal for pw x ph patches (rd_grade_spec_ok); runs without a GPU"""
+    return bool(lib().rd_grade_spec_ok(_grade_arg(spec).ctypes.data, int(pw), int(ph)))
+
+
+def grade_bytes(spec, pw, ph):
+    """the bytes of one quad's records and histogram, 0 for a spec that is not legal (rd_grade_bytes); runs without a GPU"""
+    return int(lib().rd_grade_bytes(_grade_arg(spec).ctypes.data, int(pw), int(ph)))
+
+
+def grade_cell_of(spec, pw, ph, i, j):
+    """the number of the record pixel (i, j) counts in, -1 for a spec that is not legal or a pixel outside the patch (rd_grade_cell_of); runs without a GPU"""
+    return int(lib().rd_grade_cell_of(_grade_arg(spec).ctypes.data, int(pw), int(ph), int(i), int(j)))
+
+
+def grade_limits():
+    """{"cells", "oversamplings", "max_edge", "tile_w", "tile_h", "cell_bytes", "hist_bytes"}: the legal values of a grade spec's fields, the kernel's tile and the
+    sizes of the output's parts (rd_grade_limits); runs without a GPU"""
+    a = np.zeros(8, np.int32)
+    lib().rd_grade_limits(a.ctypes.data)
+    bits = lambda v: tuple(1 << k for k in range(31) if v >> k & 1)
+    return {"cells": bits(int(a[0])), "oversamplings": bits(int(a[1])), "max_edge": int(a[2]), "tile_w": int(a[3]), "tile_h": int(a[4]), "cell_bytes": int(a[5]), "hist_bytes": int(a[6])}
+
+
+def grade_sharpness(cell):
+    """the variance of the Laplacian over one GRADE_CELL_DTYPE record, 0.0 for an empty one (rd_grade_sharpness); runs without a GPU"""
+    c = np.ascontiguousarray(cell, dtype=GRADE_CELL_DTYPE).reshape(())
+    return float(lib().rd_grade_sharpness(c.ctypes.data))
+
+
+def grade_percentile(hist, num, den=100):
+    """the smallest gray value below or at which num / den of a 256-bin histogram's pixels lie, -1 for bad arguments or an empty histogram (rd_grade_percentile);
+    runs without a GPU"""
+    h = np.ascontiguousarray(hist, dtype=np.uint32).reshape(256)
+    return int(lib().rd_grade_percentile(h.ctypes.data, int(num), int(den)))
+
+
+def grade_view(arr, spec):
+    """a grade job's bytes (what Rectifier.rectify returns, or any (n, patch_bytes) uint8 array) as (the records, a GRADE_CELL_DTYPE array of shape (n, cells, cells)
+    indexed [quad, cy, cx], the histograms as an (n, 256) uint32 array or None without hist)"""
+    c = int(spec["cells"])
+    a = np.ascontiguousarray(arr, dtype=np.uint8)
+    a = a.reshape(-1, GRADE_CELL_BYTES * c * c + (GRADE_HIST_BYTES if int(spec["hist"]) else 0))
+    cells = np.ascontiguousarray(a[:, :GRADE_CELL_BYTES * c * c]).view(GRADE_CELL_DTYPE).reshape(len(a), c, c)
+    hist = np.ascontiguousarray(a[:, GRADE_CELL_BYTES * c * c:]).view(np.uint32).reshape(len(a), 256) if int(spec["hist"]) else None
+    return cells, hist
+
+
 class Rectifier(_Service):
     """The rd_rectifier extension: pw x ph BGR patches of up to max_quads quads per job, njobs jobs in flight (the contract: include/rectdetect_hip.h).  With
     tensor=tensor_spec(...) a job writes model-ready tensors instead ("model-ready tensors" there), with scan=scan_spec(...) scanned pages ("scanned pages"):
-    `out` then holds n * patch_bytes bytes of shape(n) and dtype."""
+    `out` then holds n * patch_bytes bytes of shape(n) and dtype.  With grade=grade_spec(...) a job writes graded quads ("graded quads"): n rows of patch_bytes bytes, 8-byte aligned, which
+    grade_view takes apart."""
     _name = "rectifier"
 
-    def __init__(self, pw, ph, max_quads=64, njobs=2, device=0, tensor=None, scan=None):
-        if tensor is not None and scan is not None:
-            raise ValueError("Rectifier: tensor= and scan= exclude each other")
+    def __init__(self, pw, ph, max_quads=64, njobs=2, device=0, tensor=None, scan=None, grade=None):
+        if (tensor is not None) + (scan is not None) + (grade is not None) > 1:
+            raise ValueError("Rectifier: tensor=, scan= and grade= exclude each other")
         self.pw, self.ph, self.max_quads, self.njobs = pw, ph, max_quads, njobs
         self.tensor = None if tensor is None else _spec_arg(tensor).copy()
         self.scan = None if scan is None else _scan_arg(scan).copy()
-        if self.scan is not None:
+        self.grade = None if grade is None else _grade_arg(grade).copy()
+        if self.grade is not None:
+            self._create(device, pw, ph, max_quads, njobs, self.grade.ctypes.data, ctor="create_grade")
+        elif self.scan is not None:
             self._create(device, pw, ph, max_quads, njobs, self.scan.ctypes.data, ctor="create_scan")
         elif self.tensor is None:
             self._create(device, pw, ph, max_quads, njobs)
@@ -836,7 +914,9 @@ class Rectifier(_Service):
         return TENSOR_NUMPY[int(self.tensor["dtype"])] if self.tensor is not None else np.dtype(np.uint8)
 
     def shape(self, n):
-        """the shape of a job of n quads: (n, ph, pw, C) or, under TENSOR_NCHW, (n, C, ph, pw); scanned pages: (n, ph, pw) or, under SCAN_BITS, (n, ph, (pw + 7) // 8)"""
+        """the shape of a job of n quads: (n, ph, pw, C) or, under TENSOR_NCHW, (n, C, ph, pw); scanned pages: (n, ph, pw) or, under SCAN_BITS, (n, ph, (pw + 7) // 8); graded quads: (n, patch_bytes)"""
+        if self.grade is not None:
+            return (n, self.patch_bytes)
         if self.scan is not None:
             return (n, self.ph, (self.pw + 7) // 8 if int(self.scan["mode"]) == SCAN_BITS else self.pw)
         if self.tensor is None:

@@ -189,6 +189,12 @@ void rectify_tensor(hipStream_t s, void *out, int fmt, const rdpix::PixFrame &sr
 // rectify_tensor made of the same quads with { U8, NHWC, GRAY, spec.oversample } (quad k's at plane + k * pw * ph), one launch (quad = blockIdx.z)
 void scan(hipStream_t s, uint8_t *out, const uint8_t *plane, const RectifyQuad *quads, int n, int pw, int ph, const rd_scan_spec &spec);
 
+// ---- rd_k_grade.hip: graded quads (the contract: rectdetect_hip.h, "graded quads")
+// the records (and histograms) of n quads of pw x ph pixels under spec (legal for pw x ph: rd_grade_spec_ok) ADDED to quad k's rd_grade_bytes(spec, pw, ph) bytes at
+// out + k * that (8-byte aligned; cleared by the caller, on s), from the G plane rectify_tensor made of the same quads with { U8, NHWC, GRAY, spec.oversample }
+// (quad k's at plane + k * pw * ph), one launch (quad = blockIdx.z); an invalid quad's bytes are left as they are
+void grade(hipStream_t s, uint8_t *out, const uint8_t *plane, const RectifyQuad *quads, int n, int pw, int ph, const rd_grade_spec &spec);
+
 // ---- rd_k_match.hip: matched quads (the contract: rectdetect_hip.h, "matched quads")
 // the signatures of n quads of one frame: quad k's G * G int8 values at sig + k * G * G (zeros for an invalid quad), its sa, saa ADDED to sums[2k], sums[2k+1]
 // (cleared by the caller); G in {8, 16, 32, 64}, m in {1, 2, 4}
