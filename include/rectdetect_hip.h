@@ -400,7 +400,7 @@ void rd_tensor_limits(int32_t out[4]);
  * ordinary rd_rectifier: rd_rectifier_enqueue, rd_rectifier_wait, rd_rectifier_destroy and rd_detector_rectify_polled work on it with every pixel format, frame
  * kind and output kind, and `out` holds n * rd_rectifier_patch_bytes(r) bytes. */
 rd_rectifier *rd_rectifier_create_tensor(int device, int pw, int ph, int max_quads, int njobs, const rd_tensor_spec *spec);
-/* the bytes of one quad's output: pw * ph * 3 for a rectifier made by rd_rectifier_create, rd_tensor_bytes, rd_scan_bytes or rd_grade_bytes of the spec for the others; 0 for NULL */
+/* the bytes of one quad's output: pw * ph * 3 for a rectifier made by rd_rectifier_create, rd_tensor_bytes, rd_scan_bytes, rd_grade_bytes or rd_code_bytes of the spec for the others; 0 for NULL */
 size_t rd_rectifier_patch_bytes(const rd_rectifier *r);
 
 /* -- scanned pages: the quad as a clean page - the patch's luma divided by its local mean (shading correction) or compared with it (adaptive threshold), as bytes
@@ -490,6 +490,75 @@ int rd_grade_percentile(const uint32_t hist[256], int num, int den);
  * an ordinary rd_rectifier: rd_rectifier_enqueue, rd_rectifier_wait, rd_rectifier_destroy and rd_detector_rectify_polled work on it with every pixel format, frame
  * kind and output kind, and `out` holds n * rd_rectifier_patch_bytes(r) bytes, 8-byte aligned. */
 rd_rectifier *rd_rectifier_create_grade(int device, int pw, int ph, int max_quads, int njobs, const rd_grade_spec *spec);
+
+/* -- decoded quads: what the quad SAYS - a square grid code (an ArUco / AprilTag-style fiducial, a board marker, the data cells of a label: a ring of `border`
+ * cells round an n x n payload of dark and light cells) read per cell from the patch, and its id in a dictionary by Hamming distance over the four rotations
+ * (rd_k_code.hip, rd_rectify.hip, rd_code_host.c).  48 bytes per quad instead of pw * ph.  Two launches per job: the G plane by the tensor kernel, then one block
+ * per quad for everything else.  Exact, in integers, like everything above: tests/code.py restates it in numpy and Python integers.
+ *
+ * With C = n + 2*border a spec is LEGAL for pw x ph when 3 <= n <= 8, border is 1 or 2, 0 <= inset <= 3, polarity is 0 or 1, oversample m is 1, 2 or 4,
+ * 0 <= contrast <= 255, 0 <= max_border <= C*C - n*n, 0 <= max_hamming <= n*n, pw <= 1024 and ph <= 1024, and pw >= C and ph >= C when inset is 0, pw >= 4*C and
+ * ph >= 4*C when it is not.  Under these bounds no cell is without a counted pixel (step 2; below 4*C with an inset cells do come out empty, first at C + 1), every
+ * cell sum fits int32 and 256*sg fits uint32 (step 3).
+ *
+ * A dictionary is ndict <= 4096 codes of 64 bits, bit r*n + c the payload cell in row r and column c, the bits at and above n*n zero; it is uploaded once, when the
+ * rectifier is made.  ndict = 0 reads raw bits only.
+ *
+ * Quad k:
+ *   1. G(i, j) is, byte for byte, the element of the tensor spec { RD_TENSOR_U8, RD_TENSOR_NHWC, RD_TENSOR_GRAY, m } for the same quad, frame, pw and ph (step 1 of
+ *      "graded quads").
+ *   2. The cell of a pixel, by the pixel's centre: cx = ((2*i + 1)*C) / (2*pw), fx = ((2*i + 1)*C) % (2*pw); cy, fy the same from j and ph.  The pixel COUNTS when
+ *      inset*pw <= 4*fx <= (8 - inset)*pw and inset*ph <= 4*fy <= (8 - inset)*ph: the outer inset/8 of a cell on every side is ignored - that is where the
+ *      neighbours bleed in.  The cell's number is cy*C + cx.
+ *   3. Per cell over its counted pixels: cnt their count, sg the sum of G, M = (256*sg) / cnt, an integer division: the mean in 8.8 fixed point.  With an inset of 0
+ *      a cell is at most ceil(pw / C) x ceil(ph / C) <= 205 x 205 pixels: 256*sg <= 42 025 * 255 * 256 = 2 743 392 000 needs uint32 - the kernel and the host
+ *      divide unsigned; M <= 65 280.
+ *   4. lo = min M and hi = max M over the C*C cells.  light = 2*M > lo + hi;  v = light XOR polarity;  margin = the minimum over the cells of |2*M - (lo + hi)|.
+ *      A constant patch has every light = 0 (and margin 0).
+ *   5. border_errors = how many cells of the outer `border` rings (row or column < border or >= C - border) have v = 1.  The payload cell in row r and column c of
+ *      the inner n x n (cell (border + c, border + r)) gives bit r*n + c of `bits`.
+ *   6. A rotation by one quarter turn clockwise: rot1(P)[r][c] = P[n-1-c][r], that is bit r*n + c of rot1(P) is bit (n-1-c)*n + r of P; rot_k applies rot1 k times.
+ *   7. dist(id, k) = popcount(rot_k(bits) XOR dict[id]).  (hamming, id, rot) = the lexicographic minimum of (dist, id, k) over 0 <= id < ndict, 0 <= k < 4: the lowest
+ *      id wins a tie, then the lowest k.  second = the minimum dist over every (id', k) with id' != id, 65 when ndict < 2.  With ndict = 0: id = -1, rot = 0,
+ *      hamming = second = 65.
+ *   8. ok = (hi - lo >= 256*contrast) && border_errors <= max_border && (ndict == 0 || hamming <= max_hamming).
+ *   9. Output: one rd_code of 48 bytes, quad k's at out + 48*k, reserved = 0.  An invalid quad (status 0) gives 48 zero bytes.  Exactly n * 48 bytes are written.
+ *      `out` must be 8-byte aligned: rd_rectifier_enqueue (and rd_detector_rectify_polled) return -1 with nothing enqueued when it is not. */
+typedef struct { int32_t n, border, inset, polarity, oversample, contrast, max_border, max_hamming; } rd_code_spec;                /* 32 bytes */
+typedef struct { uint64_t bits; int32_t id, rot, hamming, second, border_errors, lo, hi, margin, ok, reserved; } rd_code;         /* 48 bytes */
+/* host only, no GPU needed (rd_code_host.c).  1 when the spec is legal for pw x ph, else 0 (a NULL spec too) */
+int rd_code_spec_ok(const rd_code_spec *spec, int pw, int ph);
+/* the bytes of one quad's output: 48; 0 for a spec that is not legal for pw x ph */
+size_t rd_code_bytes(const rd_code_spec *spec, int pw, int ph);
+/* step 2: the number of the cell pixel (i, j) lies in, and whether it counts (1 or 0) to *counted (may be NULL); -1, *counted untouched, for a spec that is not
+ * legal for pw x ph or a pixel outside the patch */
+int rd_code_cell_of(const rd_code_spec *spec, int pw, int ph, int i, int j, int *counted);
+/* step 6: rot_k(bits) of an n x n payload, k taken modulo 4 (negative k: counter-clockwise); 0 for n outside 3 .. 8; bits at and above n*n are dropped */
+uint64_t rd_code_rotate(uint64_t bits, int n, int k);
+/* out[0] <- the smallest n (3), out[1] <- the largest (8), out[2] <- the largest border (2), out[3] <- the largest inset (3), out[4] <- the legal oversamplings ORed
+ * together (1 | 2 | 4), out[5] <- the largest pw and ph (1024), out[6] <- the largest ndict (4096), out[7] <- sizeof(rd_code) (48) */
+void rd_code_limits(int32_t out[8]);
+/* what max_hamming a dictionary bears: the smallest popcount(rot_k(dict[a]) XOR dict[b]) over a < b and k = 0 .. 3, and popcount(rot_k(dict[a]) XOR dict[a]) over
+ * k = 1 .. 3 (a code that looks like itself turned has distance 0: its rot cannot be told).  65 for ndict = 0; -1 for n outside 3 .. 8, ndict outside 0 .. 4096, a
+ * NULL dict with ndict > 0, or an entry with bits at or above n*n */
+int rd_code_distance(const uint64_t *dict, int ndict, int n);
+/* a deterministic greedy dictionary.  State s = seed; a candidate: s += 0x9E3779B97F4A7C15; z = s; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ * z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^= z >> 31 (splitmix64, everything modulo 2^64); cand = z & (2^(n*n) - 1).  It is accepted, and appended to out,
+ * when rd_code_distance of the accepted codes with it stays >= min_dist.  Stops after `count` accepted codes or `tries` candidates; returns how many it accepted.
+ * -1 for n outside 3 .. 8, count outside 0 .. 4096, min_dist < 0, tries < 0 or a NULL out with count > 0 */
+int rd_code_dictionary(int n, int count, int min_dist, uint64_t seed, int tries, uint64_t *out);
+/* the gray image of a code, (C*cell_px)^2 bytes, rows of C*cell_px: the ring has v = 0, payload cell (r, c) has v = bit r*n + c, a cell is light when
+ * v XOR polarity, and light cells are 255, dark cells 0.  Only n, border and polarity of the spec are read.  Returns the bytes written; 0, nothing written, for a NULL
+ * argument, n, border or polarity out of range, cell_px outside 1 .. 64 or bits at or above n*n */
+size_t rd_code_render(const rd_code_spec *spec, uint64_t bits, int cell_px, uint8_t *out);
+/* the corners from which a patch shows the code upright: out corner c = quad corner (c + 4 - rot) % 4 (4 x (x, y), patch order; rot taken modulo 4).  The quad to
+ * hand to a rectifier, the compositor or a pose consumer once rd_code::rot is known; reading it again gives rot 0 and the same id.  out may not alias quad */
+void rd_code_upright(const double quad[8], int rot, double out[8]);
+/* A rectifier whose jobs write decoded quads.  NULL for the bad arguments of rd_rectifier_create, a NULL spec or a spec that is not legal for pw x ph, ndict outside
+ * 0 .. 4096, a NULL dict with ndict > 0, or an entry with bits at or above n*n.  The dictionary is copied.  The handle is an ordinary rd_rectifier:
+ * rd_rectifier_enqueue, rd_rectifier_wait, rd_rectifier_destroy and rd_detector_rectify_polled work on it with every pixel format, frame kind and output kind,
+ * rd_rectifier_patch_bytes is 48, and `out` holds n * 48 bytes, 8-byte aligned. */
+rd_rectifier *rd_rectifier_create_code(int device, int pw, int ph, int max_quads, int njobs, const rd_code_spec *spec, const uint64_t *dict, int ndict);
 
 /* ---- annotated frames: rectangles' outlines and line segments drawn INTO a frame on the device (rd_k_annotate.hip, rd_annotate.hip) - the picture vidrect.cpp /
  * rect.cpp (showRect) and vidpoly.cpp / poly.cpp make with OpenCV's line() on the host, for frames that never leave HBM.  OpenCV's round brush is not restated; the

@@ -12,7 +12,8 @@ Mirrors of the reference programs' call sequences:
   * :class:`PolylineDetector` - its polyline kind: poly.cpp / vidpoly.cpp per frame, several frames in flight
   * :class:`Rectifier` - the ``rd_rectifier`` extension: what is inside detected quads as upright patches of fixed size, or - with a
     :func:`tensor_spec` - as model-ready tensors (float, planar, normalised, box-filtered), or - with a :func:`scan_spec` - as scanned pages (shading-corrected
-    gray, bilevel bytes or packed bit rows), or - with a :func:`grade_spec` - as graded quads (per-cell sharpness, exposure and glare records, a histogram)
+    gray, bilevel bytes or packed bit rows), or - with a :func:`grade_spec` - as graded quads (per-cell sharpness, exposure and glare records, a histogram),
+    or - with a :func:`code_spec` and a dictionary - as decoded quads (a grid code's payload, its id, rotation and Hamming distance)
   * :class:`Annotator` - the ``rd_annotator`` extension: rectangles' outlines and line segments drawn into frames on the device
   * :class:`Compositor` - the ``rd_compositor`` extension: a colour or an image written into the quads of a frame on the device
   * :class:`Matcher` - the ``rd_matcher`` extension: which template of a library is inside each quad, decided on the device
@@ -58,6 +59,11 @@ GRADE_SPEC_DTYPE = np.dtype([("cells", "<i4"), ("dark", "<i4"), ("bright", "<i4"
 GRADE_CELL_DTYPE = np.dtype([("n", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("ne", "<i4"), ("sg", "<i8"), ("sgg", "<i8"), ("sl", "<i8"), ("sll", "<i8")])
 assert GRADE_SPEC_DTYPE.itemsize == 32 and GRADE_CELL_DTYPE.itemsize == 48
 GRADE_CELL_BYTES, GRADE_HIST_BYTES, GRADE_MAX_EDGE = 48, 1024, 1020
+# a rectifier's code spec and the record of a quad (rd_code_spec, rd_code; the contract is in include/rectdetect_hip.h, "decoded quads")
+CODE_SPEC_DTYPE = np.dtype([("n", "<i4"), ("border", "<i4"), ("inset", "<i4"), ("polarity", "<i4"), ("oversample", "<i4"), ("contrast", "<i4"), ("max_border", "<i4"), ("max_hamming", "<i4")])
+CODE_DTYPE = np.dtype([("bits", "<u8"), ("id", "<i4"), ("rot", "<i4"), ("hamming", "<i4"), ("second", "<i4"), ("border_errors", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("margin", "<i4"), ("ok", "<i4"), ("reserved", "<i4")])
+assert CODE_SPEC_DTYPE.itemsize == 32 and CODE_DTYPE.itemsize == 48
+CODE_BYTES, CODE_MAX_DICT, CODE_NONE = 48, 4096, 65
 ANNOT_SEG_ALL, ANNOT_SEG_CHAINS = 0, 1
 
 # pixel formats of enqueue_planes (rd_detector_enqueue_planes; the conversion contract is in include/rectdetect_hip.h)
@@ -157,6 +163,17 @@ def _declare(L):
         "rd_grade_sharpness": (cd, [vp]),
         "rd_grade_percentile": (ci, [vp, ci, ci]),
         "rd_rectifier_create_grade": (vp, [ci, ci, ci, ci, ci, vp]),
+        # decoded quads (rd_rectify.hip, rd_code_host.c)
+        "rd_code_spec_ok": (ci, [vp, ci, ci]),
+        "rd_code_bytes": (cz, [vp, ci, ci]),
+        "rd_code_cell_of": (ci, [vp, ci, ci, ci, ci, vp]),
+        "rd_code_rotate": (ctypes.c_uint64, [ctypes.c_uint64, ci, ci]),
+        "rd_code_limits": (None, [vp]),
+        "rd_code_distance": (ci, [vp, ci, ci]),
+        "rd_code_dictionary": (ci, [ci, ci, ci, ctypes.c_uint64, ci, vp]),
+        "rd_code_render": (cz, [vp, ctypes.c_uint64, ci, vp]),
+        "rd_code_upright": (None, [vp, ci, vp]),
+        "rd_rectifier_create_code": (vp, [ci, ci, ci, ci, ci, vp, vp, ci]),
         # annotated frames (rd_annotate.hip)
         "rd_annot_covers": (ci, [vp, ci, ci]),
         "rd_annot_touches": (ci, [vp, ci, ci, ci, ci]),
@@ -880,21 +897,120 @@ def grade_view(arr, spec):
     return cells, hist
 
 
+def code_spec(n=6, border=1, inset=2, polarity=0, oversample=1, contrast=32, max_border=0, max_hamming=0):
+    """an rd_code_spec as a CODE_SPEC_DTYPE record: an n x n payload (3 .. 8) inside `border` rings (1 or 2), the outer inset/8 of every cell ignored (0 .. 3),
+    polarity 0 for a dark ring with light ones, 1 for the opposite, oversample 1, 2 or 4; ok asks for hi - lo >= 256 * contrast, at most max_border ring cells
+    wrong and - with a dictionary - a Hamming distance of at most max_hamming.  Whether it is legal is decided where it is used (code_spec_ok, Rectifier)."""
+    s = np.zeros((), CODE_SPEC_DTYPE)
+    s["n"], s["border"], s["inset"], s["polarity"], s["oversample"], s["contrast"], s["max_border"], s["max_hamming"] = n, border, inset, polarity, oversample, contrast, max_border, max_hamming
+    return s
+
+
+def _code_arg(spec):
+    return np.ascontiguousarray(spec, dtype=CODE_SPEC_DTYPE).reshape(())
+
+
+def _dict_arg(dictionary):
+    return np.zeros(0, np.uint64) if dictionary is None else np.ascontiguousarray(dictionary, dtype=np.uint64).reshape(-1)
+
+
+def code_spec_ok(spec, pw, ph):
+    """whether a code spec is legal for pw x ph patches (rd_code_spec_ok); runs without a GPU"""
+    return bool(lib().rd_code_spec_ok(_code_arg(spec).ctypes.data, int(pw), int(ph)))
+
+
+def code_bytes(spec, pw, ph):
+    """the bytes of one quad's record, 48, or 0 for a spec that is not legal (rd_code_bytes); runs without a GPU"""
+    return int(lib().rd_code_bytes(_code_arg(spec).ctypes.data, int(pw), int(ph)))
+
+
+def code_cell_of(spec, pw, ph, i, j):
+    """(the number of the cell pixel (i, j) lies in, whether it counts); (-1, False) for a spec that is not legal or a pixel outside the patch (rd_code_cell_of);
+    runs without a GPU"""
+    counted = ctypes.c_int(0)
+    cell = int(lib().rd_code_cell_of(_code_arg(spec).ctypes.data, int(pw), int(ph), int(i), int(j), ctypes.addressof(counted)))
+    return cell, bool(counted.value)
+
+
+def code_rotate(bits, n, k=1):
+    """an n x n payload turned by k quarter turns clockwise (rd_code_rotate); runs without a GPU"""
+    return int(lib().rd_code_rotate(int(bits), int(n), int(k)))
+
+
+def code_limits():
+    """{"min_n", "max_n", "max_border", "max_inset", "oversamplings", "max_side", "max_dict", "code_bytes"} (rd_code_limits); runs without a GPU"""
+    a = np.zeros(8, np.int32)
+    lib().rd_code_limits(a.ctypes.data)
+    return {"min_n": int(a[0]), "max_n": int(a[1]), "max_border": int(a[2]), "max_inset": int(a[3]), "oversamplings": tuple(1 << k for k in range(31) if int(a[4]) >> k & 1),
+            "max_side": int(a[5]), "max_dict": int(a[6]), "code_bytes": int(a[7])}
+
+
+def code_distance(dictionary, n):
+    """the smallest Hamming distance between two entries in any rotation and between an entry and itself turned - what max_hamming the dictionary bears; 65 for an
+    empty one (rd_code_distance); runs without a GPU.  ValueError for an n, a size or an entry that is not legal"""
+    d = _dict_arg(dictionary)
+    r = int(lib().rd_code_distance(d.ctypes.data if len(d) else None, len(d), int(n)))
+    if r < 0:
+        raise ValueError("rd_code_distance: invalid arguments (%d entries, n %r)" % (len(d), n))
+    return r
+
+
+def code_dictionary(n, count, min_dist, seed=0, tries=1 << 20):
+    """up to `count` codes of n x n bits that keep min_dist from each other in every rotation and from themselves turned, the deterministic greedy choice among
+    `tries` splitmix64 candidates of `seed` (rd_code_dictionary): a uint64 array, shorter than count when the tries ran out; runs without a GPU"""
+    out = np.zeros(max(int(count), 1), np.uint64)
+    r = int(lib().rd_code_dictionary(int(n), int(count), int(min_dist), int(seed) & 0xFFFFFFFFFFFFFFFF, int(tries), out.ctypes.data))
+    if r < 0:
+        raise ValueError("rd_code_dictionary: invalid arguments (n %r, count %r, min_dist %r, tries %r)" % (n, count, min_dist, tries))
+    return out[:r].copy()
+
+
+def code_render(spec, bits, cell_px=8):
+    """the gray image of a code, a (C * cell_px, C * cell_px) uint8 array of 0 and 255 (rd_code_render); runs without a GPU"""
+    s = _code_arg(spec)
+    side = (int(s["n"]) + 2 * int(s["border"])) * int(cell_px)
+    out = np.zeros((max(side, 1), max(side, 1)), np.uint8)
+    if not 1 <= side <= 12 * 64 or lib().rd_code_render(s.ctypes.data, int(bits), int(cell_px), out.ctypes.data) != side * side:
+        raise ValueError("rd_code_render: invalid arguments (spec %r, bits %r, cell_px %r)" % (spec, bits, cell_px))
+    return out
+
+
+def code_upright(quad, rot):
+    """the (4, 2) corners from which a patch shows a code upright that was read with rd_code::rot = rot from `quad` (rd_code_upright); runs without a GPU"""
+    q = np.ascontiguousarray(quad, dtype=np.float64).reshape(8)
+    out = np.zeros(8, np.float64)
+    lib().rd_code_upright(q.ctypes.data, int(rot), out.ctypes.data)
+    return out.reshape(4, 2)
+
+
+def code_view(arr):
+    """a code job's bytes (what Rectifier.rectify returns, or any (n, 48) uint8 array) as a CODE_DTYPE array of n records"""
+    return np.ascontiguousarray(arr, dtype=np.uint8).reshape(-1, CODE_BYTES).view(CODE_DTYPE).reshape(-1)
+
+
 class Rectifier(_Service):
     """The rd_rectifier extension: pw x ph BGR patches of up to max_quads quads per job, njobs jobs in flight (the contract: include/rectdetect_hip.h).  With
     tensor=tensor_spec(...) a job writes model-ready tensors instead ("model-ready tensors" there), with scan=scan_spec(...) scanned pages ("scanned pages"):
     `out` then holds n * patch_bytes bytes of shape(n) and dtype.  With grade=grade_spec(...) a job writes graded quads ("graded quads"): n rows of patch_bytes bytes, 8-byte aligned, which
-    grade_view takes apart."""
+    grade_view takes apart.  With code=code_spec(...) and dictionary=a uint64 array (or None: raw bits only) a job writes decoded quads ("decoded quads"): n rows of
+    48 bytes, 8-byte aligned, which code_view turns into records."""
     _name = "rectifier"
 
-    def __init__(self, pw, ph, max_quads=64, njobs=2, device=0, tensor=None, scan=None, grade=None):
-        if (tensor is not None) + (scan is not None) + (grade is not None) > 1:
-            raise ValueError("Rectifier: tensor=, scan= and grade= exclude each other")
+    def __init__(self, pw, ph, max_quads=64, njobs=2, device=0, tensor=None, scan=None, grade=None, code=None, dictionary=None):
+        if (tensor is not None) + (scan is not None) + (grade is not None) + (code is not None) > 1:
+            raise ValueError("Rectifier: tensor=, scan=, grade= and code= exclude each other")
+        if dictionary is not None and code is None:
+            raise ValueError("Rectifier: dictionary= goes with code=")
         self.pw, self.ph, self.max_quads, self.njobs = pw, ph, max_quads, njobs
         self.tensor = None if tensor is None else _spec_arg(tensor).copy()
         self.scan = None if scan is None else _scan_arg(scan).copy()
         self.grade = None if grade is None else _grade_arg(grade).copy()
-        if self.grade is not None:
+        self.code = None if code is None else _code_arg(code).copy()
+        self.dictionary = None if code is None else _dict_arg(dictionary).copy()
+        if self.code is not None:
+            d = self.dictionary
+            self._create(device, pw, ph, max_quads, njobs, self.code.ctypes.data, d.ctypes.data if len(d) else None, len(d), ctor="create_code")
+        elif self.grade is not None:
             self._create(device, pw, ph, max_quads, njobs, self.grade.ctypes.data, ctor="create_grade")
         elif self.scan is not None:
             self._create(device, pw, ph, max_quads, njobs, self.scan.ctypes.data, ctor="create_scan")
@@ -914,8 +1030,8 @@ class Rectifier(_Service):
         return TENSOR_NUMPY[int(self.tensor["dtype"])] if self.tensor is not None else np.dtype(np.uint8)
 
     def shape(self, n):
-        """the shape of a job of n quads: (n, ph, pw, C) or, under TENSOR_NCHW, (n, C, ph, pw); scanned pages: (n, ph, pw) or, under SCAN_BITS, (n, ph, (pw + 7) // 8); graded quads: (n, patch_bytes)"""
-        if self.grade is not None:
+        """the shape of a job of n quads: (n, ph, pw, C) or, under TENSOR_NCHW, (n, C, ph, pw); scanned pages: (n, ph, pw) or, under SCAN_BITS, (n, ph, (pw + 7) // 8); graded and decoded quads: (n, patch_bytes)"""
+        if self.grade is not None or self.code is not None:
             return (n, self.patch_bytes)
         if self.scan is not None:
             return (n, self.ph, (self.pw + 7) // 8 if int(self.scan["mode"]) == SCAN_BITS else self.pw)

@@ -195,6 +195,14 @@ void scan(hipStream_t s, uint8_t *out, const uint8_t *plane, const RectifyQuad *
 // (quad k's at plane + k * pw * ph), one launch (quad = blockIdx.z); an invalid quad's bytes are left as they are
 void grade(hipStream_t s, uint8_t *out, const uint8_t *plane, const RectifyQuad *quads, int n, int pw, int ph, const rd_grade_spec &spec);
 
+// ---- rd_k_code.hip: decoded quads (the contract: rectdetect_hip.h, "decoded quads")
+// the rd_code records of n quads of pw x ph pixels under spec (legal for pw x ph: rd_code_spec_ok), quad k's WRITTEN whole to out + k * 48 (8-byte aligned; zeros for an
+// invalid quad), from the G plane rectify_tensor made of the same quads with { U8, NHWC, GRAY, spec.oversample } (quad k's at plane + k * pw * ph) and ndict <= 4096
+// codes in device memory (dict may be null when ndict is 0), one launch (quad = blockIdx.x).  The kernel reads WHOLE 16-byte words: up to 15 bytes in front of a quad's
+// plane (its neighbour's) and up to 15 behind the last one - so plane must lie on a 16-byte boundary and plane_bytes, the readable bytes from there, must be at least
+// n * pw * ph + RD_CODE_PLANE_PAD; the launcher aborts otherwise
+void code(hipStream_t s, uint8_t *out, const uint8_t *plane, size_t plane_bytes, const RectifyQuad *quads, int n, int pw, int ph, const rd_code_spec &spec, const uint64_t *dict, int ndict);
+
 // ---- rd_k_match.hip: matched quads (the contract: rectdetect_hip.h, "matched quads")
 // the signatures of n quads of one frame: quad k's G * G int8 values at sig + k * G * G (zeros for an invalid quad), its sa, saa ADDED to sums[2k], sums[2k+1]
 // (cleared by the caller); G in {8, 16, 32, 64}, m in {1, 2, 4}

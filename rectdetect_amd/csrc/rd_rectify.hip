@@ -1,8 +1,9 @@
 // rectdetect-mi355x: the rectifier - rectified patches of quads behind the detector's poll (the contract: include/rectdetect_hip.h, "rectified patches";
 // the kernels: rd_k_rectify.hip and, for a rectifier made with a tensor spec, rd_k_tensor.hip ("model-ready tensors"); made with a scan spec, rd_k_tensor.hip into a
-// G plane of the rectifier's own and rd_k_scan.hip from there ("scanned pages"); made with a grade spec, the same G plane and rd_k_grade.hip ("graded quads"); the jobs in flight, the frame's checks and its way to the device: rd_jobs.h).
+// G plane of the rectifier's own and rd_k_scan.hip from there ("scanned pages"); made with a grade spec, the same G plane and rd_k_grade.hip ("graded quads"); made with a code spec and a dictionary, the same G plane and rd_k_code.hip ("decoded quads"); the jobs in flight, the frame's checks and its way to the device: rd_jobs.h).
 #include "rd_jobs.h"
 #include "rd_kernels.h"
+#include "rd_code_tile.h"
 #include <math.h>
 #include <stdio.h>
 
@@ -11,14 +12,18 @@ using namespace rdjob;
 struct rd_rectifier {
   Ring ring;                                // (first: rd_jobs.h)
   int pw, ph;
-  size_t patch_bytes;                       // of one quad's output: pw * ph * 3, or rd_tensor_bytes / rd_scan_bytes / rd_grade_bytes of the spec
+  size_t patch_bytes;                       // of one quad's output: pw * ph * 3, or rd_tensor_bytes / rd_scan_bytes / rd_grade_bytes / rd_code_bytes of the spec
   int tensor;                               // made by rd_rectifier_create_tensor: jobs launch rdk::rectify_tensor with `spec`
   rd_tensor_spec spec;
   int scan;                                 // made by rd_rectifier_create_scan: jobs launch rdk::rectify_tensor with `spec` ({ U8, NHWC, GRAY, m }) into d_plane, then rdk::scan with `sspec`
   rd_scan_spec sspec;
   int grade;                                // made by rd_rectifier_create_grade: the same G plane, then the stream zeroes the job's output and rdk::grade adds to it under `gspec`
   rd_grade_spec gspec;
-  uint8_t **d_plane;                        // per slot: the G planes of max_quads quads, pw * ph bytes each (allocated on first use; scan and grade rectifiers only)
+  int code;                                 // made by rd_rectifier_create_code: the same G plane, then rdk::code writes a record per quad under `cspec` from the ndict codes at d_dict
+  rd_code_spec cspec;
+  uint64_t *d_dict;                         // (NULL when ndict is 0)
+  int ndict;
+  uint8_t **d_plane;                        // per slot: the G planes of max_quads quads, pw * ph bytes each (allocated on first use; scan, grade and code rectifiers only)
   rdk::RectifyQuad *d_quads, *h_quads;      // njobs blocks of max_quads each, a job's at slot * max_quads: pinned staging and their place in the device array
   uint8_t **d_out;                          // per slot: max_quads patches on their way to pinned host memory (allocated on first use)
   DevBuf frame;                             // host and pinned frames travel through here
@@ -72,12 +77,18 @@ static void gray_plane(rd_rectifier *r, int njobs, int oversample) {
   r->d_plane = (uint8_t **)calloc(njobs, sizeof(uint8_t *));
 }
 
-// spec == NULL, sspec == NULL and gspec == NULL: the classic rectifier
-static rd_rectifier *rectifier_create(int device, int pw, int ph, int max_quads, int njobs, const rd_tensor_spec *spec, const rd_scan_spec *sspec = NULL, const rd_grade_spec *gspec = NULL) {
+// spec == NULL, sspec == NULL, gspec == NULL and cspec == NULL: the classic rectifier
+static rd_rectifier *rectifier_create(int device, int pw, int ph, int max_quads, int njobs, const rd_tensor_spec *spec, const rd_scan_spec *sspec = NULL, const rd_grade_spec *gspec = NULL,
+                                      const rd_code_spec *cspec = NULL, const uint64_t *dict = NULL, int ndict = 0) {
   if (pw < 1 || ph < 1 || pw > 16384 || ph > 16384 || max_quads < 1 || max_quads > 65535 || !ring_args_ok(device, njobs)) return NULL;
   if (spec && !rd_tensor_spec_ok(spec, pw, ph)) return NULL;
   if (sspec && !rd_scan_spec_ok(sspec, pw, ph)) return NULL;
   if (gspec && !rd_grade_spec_ok(gspec, pw, ph)) return NULL;
+  if (cspec) {
+    if (!rd_code_spec_ok(cspec, pw, ph) || ndict < 0 || ndict > RD_CODE_MAX_DICT || (ndict > 0 && !dict)) return NULL;
+    const int bits = cspec->n * cspec->n;
+    for (int k = 0; k < ndict; k++) if (bits < 64 && (dict[k] >> bits)) return NULL;      // (a bit at or above n * n)
+  }
   rd_rectifier *r = (rd_rectifier *)calloc(1, sizeof(*r));
   ring_create(&r->ring, RD_MAGIC_RECTIFIER, device, max_quads, njobs);
   r->pw = pw; r->ph = ph;
@@ -92,6 +103,15 @@ static rd_rectifier *rectifier_create(int device, int pw, int ph, int max_quads,
     r->grade = 1; r->gspec = *gspec;
     r->patch_bytes = rd_grade_bytes(gspec, pw, ph);
     gray_plane(r, njobs, gspec->oversample);
+  }
+  if (cspec) {
+    r->code = 1; r->cspec = *cspec; r->ndict = ndict;
+    r->patch_bytes = rd_code_bytes(cspec, pw, ph);
+    gray_plane(r, njobs, cspec->oversample);
+    if (ndict > 0) {
+      RD_HIP(hipMalloc((void **)&r->d_dict, (size_t)ndict * sizeof(uint64_t)));
+      RD_HIP(hipMemcpy(r->d_dict, dict, (size_t)ndict * sizeof(uint64_t), hipMemcpyHostToDevice));
+    }
   }
   const size_t nq = (size_t)njobs * max_quads;
   RD_HIP(hipMalloc((void **)&r->d_quads, nq * sizeof(rdk::RectifyQuad)));
@@ -114,6 +134,10 @@ rd_rectifier *rd_rectifier_create_grade(int device, int pw, int ph, int max_quad
   return spec ? rectifier_create(device, pw, ph, max_quads, njobs, NULL, NULL, spec) : NULL;
 }
 
+rd_rectifier *rd_rectifier_create_code(int device, int pw, int ph, int max_quads, int njobs, const rd_code_spec *spec, const uint64_t *dict, int ndict) {
+  return spec ? rectifier_create(device, pw, ph, max_quads, njobs, NULL, NULL, NULL, spec, dict, ndict) : NULL;
+}
+
 size_t rd_rectifier_patch_bytes(const rd_rectifier *r) { return r ? r->patch_bytes : 0; }
 
 void rd_rectifier_destroy(rd_rectifier *r) {
@@ -123,6 +147,7 @@ void rd_rectifier_destroy(rd_rectifier *r) {
   ring_destroy(g);
   for (int k = 0; k < njobs; k++) if (r->d_out[k]) RD_HIP(hipFree(r->d_out[k]));
   for (int k = 0; k < njobs; k++) if (r->d_plane && r->d_plane[k]) RD_HIP(hipFree(r->d_plane[k]));
+  if (r->d_dict) RD_HIP(hipFree(r->d_dict));
   RD_HIP(hipFree(r->d_quads));
   RD_HIP(hipHostFree(r->h_quads));
   r->frame.release();
@@ -142,7 +167,7 @@ long rd_rectifier_enqueue(rd_rectifier *r, int format, const void *const planes[
   if (n < 0 || n > g->per_job || (n > 0 && (!quads || !out))) return -1;
   RD_HIP(hipSetDevice(g->device));
   if (n > 0 && !is_kind(out, out_kind)) return -1;
-  if (n > 0 && r->grade && ((uintptr_t)out & 7)) return -1;      // (the records' 64-bit sums)
+  if (n > 0 && (r->grade || r->code) && ((uintptr_t)out & 7)) return -1;      // (the records' 64-bit sums; rd_code::bits)
   const int slot = ring_claim(g, who, n);
   rdk::RectifyQuad *h_quads = r->h_quads + (size_t)slot * g->per_job, *d_quads = r->d_quads + (size_t)slot * g->per_job;
   for (int k = 0; k < n; k++) {
@@ -163,11 +188,13 @@ long rd_rectifier_enqueue(rd_rectifier *r, int format, const void *const planes[
       if (!r->d_out[slot]) RD_HIP(hipMalloc((void **)&r->d_out[slot], (size_t)g->per_job * r->patch_bytes));      // (on first use: a rectifier that writes to device memory only has none)
       dst = r->d_out[slot];
     }
-    if (r->scan || r->grade) {
-      if (!r->d_plane[slot]) RD_HIP(hipMalloc((void **)&r->d_plane[slot], (size_t)g->per_job * r->pw * r->ph));      // (on first use, like d_out)
+    if (r->scan || r->grade || r->code) {
+      const size_t plane_bytes = (size_t)g->per_job * r->pw * r->ph + (r->code ? RD_CODE_PLANE_PAD : 0);      // (rdk::code reads whole 16-byte words, and is told how far it may)
+      if (!r->d_plane[slot]) RD_HIP(hipMalloc((void **)&r->d_plane[slot], plane_bytes));      // (on first use, like d_out)
       rdk::rectify_tensor(g->st, r->d_plane[slot], format, src, d_quads, n, r->pw, r->ph, r->spec);
-      rdrt::check_launch(r->scan ? "scanned pages: the G plane" : "graded quads: the G plane");
+      rdrt::check_launch(r->scan ? "scanned pages: the G plane" : r->grade ? "graded quads: the G plane" : "decoded quads: the G plane");
       if (r->scan) rdk::scan(g->st, dst, r->d_plane[slot], d_quads, n, r->pw, r->ph, r->sspec);
+      else if (r->code) rdk::code(g->st, dst, r->d_plane[slot], plane_bytes, d_quads, n, r->pw, r->ph, r->cspec, r->d_dict, r->ndict);
       else {
         RD_HIP(hipMemsetAsync(dst, 0, (size_t)n * r->patch_bytes, g->st));      // the kernel ADDS to the records; an invalid quad's stay as they are here
         rdk::grade(g->st, dst, r->d_plane[slot], d_quads, n, r->pw, r->ph, r->gspec);
