@@ -106,6 +106,11 @@ template <typename T>
 __device__ __forceinline__ T &at32(T *base, unsigned idx) { return *(T *)((char *)base + (idx << 2)); }
 template <typename T>
 __device__ __forceinline__ const T &at32(const T *base, unsigned idx) { return *(const T *)((const char *)base + (idx << 2)); }
+// the same with the byte offset itself (a thread that walks rows adds the row's bytes to the offset it has: no shift per access)
+template <typename T>
+__device__ __forceinline__ T &atb(T *base, unsigned off) { return *(T *)((char *)base + off); }
+template <typename T>
+__device__ __forceinline__ const T &atb(const T *base, unsigned off) { return *(const T *)((const char *)base + off); }
 // the same for any element size: element `idx`, byte offset idx * sizeof(T) in 32 bits
 template <typename T>
 __device__ __forceinline__ T &atu(T *base, unsigned idx) { return *(T *)((char *)base + idx * (unsigned)sizeof(T)); }
@@ -166,6 +171,21 @@ __device__ __forceinline__ rd_tile rd_block_tile(int gdim) {
   rd_tile t;
   if (nz == 8) { t.z = b & 7; const int q = b >> 3; t.y = q / gx; t.x = q - t.y * gx; }
   else { const int per = gx * gy; t.z = b / per; const int q = b - t.z * per; t.y = q / gx; t.x = q - t.y * gx; }
+  return t;
+}
+// the block's frame alone (rd_block_tile().z without the tile's divisions): for a kernel that tests a word of its frame before it works out anything else
+__device__ __forceinline__ int rd_block_frame(int gdim) {
+  const int gx = gdim & 4095, gy = (gdim >> 12) & 4095, nz = gdim >> 24, b = (int)blockIdx.x;
+  return nz == 8 ? (b & 7) : b / (gx * gy);
+}
+// ... and its tile once the frame z = rd_block_frame(gdim) is known: the same tile as rd_block_tile's
+__device__ __forceinline__ rd_tile rd_block_tile_of(int gdim, int z) {
+  const int gx = gdim & 4095, gy = (gdim >> 12) & 4095, nz = gdim >> 24, b = (int)blockIdx.x;
+  rd_tile t;
+  t.z = z;
+  const int q = nz == 8 ? b >> 3 : b - z * (gx * gy);
+  t.y = q / gx;
+  t.x = q - t.y * gx;
   return t;
 }
 // RD_ZSHIFT for such a kernel: the frame is rd_block_tile().z, not blockIdx.z

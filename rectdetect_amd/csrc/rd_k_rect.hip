@@ -815,6 +815,11 @@ __global__ __launch_bounds__(256) void k_region_init(int *__restrict__ A, int *_
 // Memory-latency bound: every thread handles RR_PX pixels below one another - each is the other's vertical neighbour, so a column of six
 // costs 6 + 2 + 12 label loads instead of 30 (measured at full rate, same box: 2, 3, 4, 6, 8 pixels: 2056, 2080, 2083 / 2067, 2079, 2062
 // frames/s) - and issues all of their label loads before using any, then the first pointer jumps together.
+// What a wave executes (profiles/NOTES_region_round.md): from round 3 on most waves of a launch change nothing, so the body is written for them.  A tile that lies
+// inside the frame with its ring (INNER: 88 % of the tiles of a 1920x1080 frame) computes no bounds test and no clamped address; the smallest neighbour is found on the
+// words as loaded and shifted once; the hooking part - dedupe, hash, guarded atomics - lies behind one test of "any lane of this wave changes something"; and a launch
+// behind the settled one reads its frame's flag before anything else.  Per wave of k_region_round<3>: 223 -> 159 vector, 205 -> 153 scalar, 16 -> 4.5 LDS instructions
+// on the bench stream; the kernel's time follows only in part (40.2 -> 37.6 us per frame): it waits for its two dependent trips to memory, as said above.
 #ifndef RR_PX
 #define RR_PX 8
 #endif
@@ -823,9 +828,6 @@ __global__ __launch_bounds__(256) void k_region_init(int *__restrict__ A, int *_
                          //  8 x 4 2669-2722, 8 x 12 2607-2623 - smaller blocks give their wave slots back sooner; before, with the loads one after the other, 2 / 4 / 8 rows: 2094 / 2118 / 2124.)
 #endif
 #define RR_MBITS 3
-#ifndef RR_DPP
-#define RR_DPP 1           // the left / right neighbours' words from the neighbouring lanes (0: loaded)
-#endif
 #ifndef RR_DEEP
 #define RR_DEEP 3          // rounds in which the trees are still the chains of the initial links (a pixel's parent is 1, 10, 91 rows above it)
 #endif
@@ -833,98 +835,98 @@ __device__ __forceinline__ int rr_label(const int *X, unsigned q) { return at32(
 // (Block -> tile and frame: rd_block_tile, rd_device.h - a tile's neighbours and the pixels its labels name, the rows above it, are served by the L2 that fetched
 //  them for the neighbouring tiles: 64 % of this kernel's L2 requests missed before.)
 // PHASE: 1 = launch 1 (proposals meet in the tile), 2 = the other launches that climb raw chains (every pixel hooks its own parent), 3 = the rest (parents combined per block)
-template <int PHASE>
-__global__ __launch_bounds__(64 * RR_TY) void k_region_round(int *X, int *Y, const u64 *__restrict__ allow, int iw, int ih, int *flags, int round, size_t zs, int gdim) {
-  const rd_tile rd_b = rd_block_tile(gdim);
-  if (rd_b.x < 0) return;
-  const int bx = rd_b.x, by = rd_b.y;
-  RD_ZSHIFTZ(rd_b.z, zs, X, Y, allow, flags);
-  if (round > 0 && flags[round - 1] == 0) return;
-  __shared__ int hk[PHASE == 3 ? 512 : 1], hv[PHASE == 3 ? 512 : 1];
-  __shared__ int tmin[PHASE == 1 ? 64 * RR_TY * RR_PX : 1];      // launch 1 only: the smallest proposal for each pixel of the block's tile (see below)
+// INNER: the block's tile and the one-pixel ring around it lie inside the frame (a wave-uniform test the kernel makes once): every pixel of the tile exists and so does every
+// neighbour, so a row's addresses are a scalar row base plus the lane - no `valid`, no select, no clamp.  Border tiles run the same body with the tests.
+template <int PHASE, bool INNER>
+__device__ __forceinline__ void rr_tile(const int *X, int *Y, const u64 *__restrict__ allow, int iw, int ih, int *flags, int round, int bx, int by, int *hk, int *hv, int *tmin) {
   const int tid = rd_ty() * 64 + threadIdx.x;
   constexpr bool near = PHASE == 1;           // the trees are still the first launch's: a pixel's parent lies ~10 rows above it, mostly inside the tile
-  if (PHASE == 3) for (int t = tid; t < 512; t += 64 * RR_TY) { hk[t] = -1; hv[t] = 0x7fffffff; }
-  if (near) for (int t = tid; t < 64 * RR_TY * RR_PX; t += 64 * RR_TY) tmin[t] = 0x7fffffff;
-  if (PHASE != 2) __syncthreads();
   const int mark = 1 + round % 7, mark_prev = round > 0 ? 1 + (round - 1) % 7 : 8;      // (8: matches nothing - before round 0 no plane lags)
   // (A wave takes 64 pixels of RR_PX rows.  In the launches that climb raw chains the 64 lanes of a row land on ~20 different 64-byte lines per jump - the chains of neighbouring
   //  columns fall out of step wherever a vertical run ends, 7 % of the pixels of the bench stream - and footprints 16 pixels wide and 4 RR_PX rows tall halve that (simulated: 159 -> 74
   //  lines per pixel row in launch 1); measured +0.3 % with blocks of 8 x 6, -1.5 % with 4 x 8: the lines are not what those launches wait for.  profiles/NOTES_r05.md.)
   const int lx = (int)threadIdx.x, ly = rd_ty() * RR_PX;      // column and first row inside the block's 64 x (RR_TY * RR_PX) tile
   const int yb = by * (RR_TY * RR_PX) + ly;      // the thread's RR_PX pixels lie below one another: each is the other's vertical neighbour
-  const int x = bx * 64 + lx;
-  int p0[RR_PX], og[RR_PX], g[RR_PX], nx[RR_PX], w0[RR_PX];
+  const int x0 = bx * 64, x = x0 + lx;
+  const unsigned rowb = (unsigned)iw << 2;       // bytes of a row of a label plane
+  unsigned pb[RR_PX];       // the pixels' BYTE offsets in a label plane (an invalid pixel's: 0)
+  int og[RR_PX], g[RR_PX], nx[RR_PX], w0[RR_PX];
   unsigned a[RR_PX];
-  bool valid[RR_PX], todo[RR_PX];
+  bool valid[RR_PX], act[RR_PX], todo[RR_PX];       // (valid, act: tested in border tiles only)
   {
-    // (unsigned element indices: the loads take the plane's base from scalar registers and a 32-bit offset, no 64-bit address arithmetic per access.
+    // (unsigned 32-bit offsets: the loads take the plane's base from scalar registers and a 32-bit offset, no 64-bit address arithmetic per access.
     //  Every load of this kernel is UNCONDITIONAL, with the address of a pixel that exists where the value is not wanted: a load under a condition becomes a
     //  branch with a wait for ALL loads in flight behind it - the thread's loads then travel one after the other.)
     int l[RR_PX][5];
+    int ed[RR_PX];
     static_assert(RR_PX == 8, "the allow bytes of a thread's 8 rows are one word (k_region_init)");
-    const bool colin = x < iw && yb < ih;
-    const u64 aw = allow[colin ? (size_t)(yb >> 3) * iw + x : 0];
-#pragma unroll
-    for (int k = 0; k < RR_PX; k++) {
-      const int y = yb + k;
-      valid[k] = x < iw && y < ih;
-      p0[k] = valid[k] ? y * iw + x : 0;
-      a[k] = valid[k] ? (unsigned)(aw >> (8 * k)) & 0xffu : 0u;
-      l[k][0] = at32(X, (unsigned)p0[k]);
-    }
     // neighbours: above / below inside the thread's own column, or one load each for the first and the last row; left / right from the neighbouring LANES (wave shifts,
-    // no memory instruction) - the wave's outermost lanes take theirs from one more load per row in which the lower half of the wave asks for the pixel left of the tile
-    // and the upper half for the pixel right of it (two addresses per load).  Addresses clamped into the plane; whether a neighbour counts depends on the allow bits,
-    // which are 0 towards anything outside the frame.
-    l[0][1] = at32(X, (unsigned)((valid[0] && yb > 0) ? p0[0] - iw : p0[0]));
-    l[RR_PX - 1][4] = at32(X, (unsigned)((valid[RR_PX - 1] && yb + RR_PX - 1 < ih - 1) ? p0[RR_PX - 1] + iw : p0[RR_PX - 1]));
-#if RR_DPP
-    {
-      const int x0 = bx * 64;
-      const bool lowhalf = threadIdx.x < 32;
-      const int xe = lowhalf ? x0 - 1 : x0 + 64;
-      int ed[RR_PX];
+    // no memory instruction) - the wave's outermost lanes take theirs from one more load per row (`ed`) in which the lower half of the wave asks for the pixel left of the
+    // tile and the upper half for the pixel right of it (two addresses per load).
+    if (INNER) {
+      const unsigned tb = (unsigned)(yb * iw + x0) << 2;      // the wave's first row at the tile's first column: scalar
+      const u64 aw = atu(allow, (unsigned)((yb >> 3) * iw + x0) + (unsigned)lx);
+      const unsigned b0 = tb + ((unsigned)lx << 2), e0 = tb + (lx < 32 ? 0u - 4u : 256u);
+#pragma unroll
+      for (int k = 0; k < RR_PX; k++) {
+        valid[k] = true;
+        pb[k] = b0 + (unsigned)k * rowb;
+        a[k] = (unsigned)(aw >> (8 * k)) & 0xffu;
+        l[k][0] = atb(X, pb[k]);
+      }
+      l[0][1] = atb(X, pb[0] - rowb);
+      l[RR_PX - 1][4] = atb(X, pb[RR_PX - 1] + rowb);
+#pragma unroll
+      for (int k = 0; k < RR_PX; k++) ed[k] = atb(X, e0 + (unsigned)k * rowb);
+    } else {
+      // Addresses clamped into the plane; whether a neighbour counts depends on the allow bits, which are 0 towards anything outside the frame.
+      const bool colin = x < iw && yb < ih;
+      const u64 aw = allow[colin ? (size_t)(yb >> 3) * iw + x : 0];
 #pragma unroll
       for (int k = 0; k < RR_PX; k++) {
         const int y = yb + k;
-        ed[k] = at32(X, (unsigned)((y < ih && xe >= 0 && xe < iw) ? y * iw + xe : p0[k]));
+        valid[k] = x < iw && y < ih;
+        pb[k] = valid[k] ? (unsigned)(y * iw + x) << 2 : 0u;
+        a[k] = valid[k] ? (unsigned)(aw >> (8 * k)) & 0xffu : 0u;
+        l[k][0] = atb(X, pb[k]);
       }
+      l[0][1] = atb(X, (valid[0] && yb > 0) ? pb[0] - rowb : pb[0]);
+      l[RR_PX - 1][4] = atb(X, (valid[RR_PX - 1] && yb + RR_PX - 1 < ih - 1) ? pb[RR_PX - 1] + rowb : pb[RR_PX - 1]);
+      const int xe = lx < 32 ? x0 - 1 : x0 + 64;
 #pragma unroll
       for (int k = 0; k < RR_PX; k++) {
-        l[k][2] = __builtin_amdgcn_update_dpp(ed[k], l[k][0], 0x138, 0xf, 0xf, false);      // wave_shr:1 - lane i takes lane i - 1's word, lane 0 keeps `ed` (the pixel left of the tile)
-        l[k][3] = __builtin_amdgcn_update_dpp(ed[k], l[k][0], 0x130, 0xf, 0xf, false);      // wave_shl:1 - lane i takes lane i + 1's word, lane 63 keeps `ed` (the pixel right of the tile)
+        const int y = yb + k;
+        ed[k] = atb(X, (y < ih && xe >= 0 && xe < iw) ? (unsigned)(y * iw + xe) << 2 : pb[k]);
       }
     }
-#else
 #pragma unroll
     for (int k = 0; k < RR_PX; k++) {
-      l[k][2] = at32(X, (unsigned)((valid[k] && x > 0) ? p0[k] - 1 : p0[k]));
-      l[k][3] = at32(X, (unsigned)((valid[k] && x < iw - 1) ? p0[k] + 1 : p0[k]));
+      l[k][2] = __builtin_amdgcn_update_dpp(ed[k], l[k][0], 0x138, 0xf, 0xf, false);      // wave_shr:1 - lane i takes lane i - 1's word, lane 0 keeps `ed` (the pixel left of the tile)
+      l[k][3] = __builtin_amdgcn_update_dpp(ed[k], l[k][0], 0x130, 0xf, 0xf, false);      // wave_shl:1 - lane i takes lane i + 1's word, lane 63 keeps `ed` (the pixel right of the tile)
     }
-#endif
 #pragma unroll
     for (int k = 0; k < RR_PX; k++) {       // (the neighbours inside the thread's own column: no loads; an invalid pixel's word is never used - its neighbour above is on the ring)
       if (k > 0) l[k][1] = l[k - 1][0];
       if (k < RR_PX - 1) l[k][4] = l[k + 1][0];
     }
+    // The smallest label among the pixel itself and the neighbours it may adopt from, taken on the WORDS as loaded and shifted once.  A word is label << 3 | mark with
+    // 0 <= mark < 8: of two words with different labels the one with the smaller label is the smaller word whatever their marks are (the labels differ by at least one, the
+    // marks by less than 8), so the smallest word carries the smallest label, and words of the same label differ in their marks only, which the shift drops:
+    // min(words) >> 3 == min(words >> 3).  A neighbour that is not allowed counts as +infinity (bit c of `a` spread over a word selects the word or 0x7fffffff: two
+    // operations per neighbour, no compares); the pixel's own word is always among the candidates and is below 2^28, so +infinity never wins and never reaches the shift.
 #pragma unroll
     for (int k = 0; k < RR_PX; k++) {
-      int e[5];
       w0[k] = l[k][0];
-#pragma unroll
-      for (int c = 0; c < 5; c++) e[c] = l[k][c] >> RR_MBITS;
-      og[k] = e[0];
-      // the smallest label among the pixel itself and the neighbours it may adopt from: a neighbour that is not allowed counts as
-      // +infinity (bit k of `a` spread over a word selects the label or 0x7fffffff: two operations per neighbour, no compares)
-      int m = e[0];
+      int m = w0[k];
 #pragma unroll
       for (int c = 1; c < 5; c++) {
         const int t = __builtin_amdgcn_sbfe((int)a[k], c - 1, 1);      // -1 if allowed, else 0
-        const int xk = (e[c] & t) | (0x7fffffff & ~t);
+        const int xk = (l[k][c] & t) | (0x7fffffff & ~t);
         m = xk < m ? xk : m;
       }
-      g[k] = (a[k] & 16) ? m : e[0];
+      og[k] = w0[k] >> RR_MBITS;
+      g[k] = m >> RR_MBITS;           // (a pixel that does not act has no neighbour bits either - k_region_init sets them together with bit 4 or not at all: m is its own word)
+      act[k] = INNER || (a[k] & 16);      // (bit 4: the pixel is not on the frame's ring - every pixel of an inner tile)
     }
   }
   // rc:328: the eight pointer jumps (a root maps to itself), level by level for the thread's RR_PX pixels together: seven dependent
@@ -933,10 +935,10 @@ __global__ __launch_bounds__(64 * RR_TY) void k_region_round(int *X, int *Y, con
 #pragma unroll
   for (int k = 0; k < RR_PX; k++) {
     const int v = rr_label(X, (unsigned)g[k]);      // (g is a pixel index for every lane: a pixel that does not act holds its own label)
-    nx[k] = (a[k] & 16) ? v : g[k];
+    nx[k] = act[k] ? v : g[k];
   }
   for (int j = 1; j < 8; j++) {
-    bool moving = false;
+    bool moving = false;      // (written as one compare over an OR of XORs the compiler makes the same eight compares of it: profiles/NOTES_region_round.md)
 #pragma unroll
     for (int k = 0; k < RR_PX; k++) moving = moving || nx[k] != g[k];
     if (!__any(moving)) break;
@@ -946,11 +948,11 @@ __global__ __launch_bounds__(64 * RR_TY) void k_region_round(int *X, int *Y, con
   bool any_todo = false;
 #pragma unroll
   for (int k = 0; k < RR_PX; k++) {
-    g[k] = (a[k] & 16) ? nx[k] : og[k];          // (after the loop nx is one jump ahead of g, or equal to it; ring pixels keep their label)
-    todo[k] = (a[k] & 16) && g[k] != og[k];
+    g[k] = act[k] ? nx[k] : og[k];          // (after the loop nx is one jump ahead of g, or equal to it; ring pixels keep their label)
+    todo[k] = g[k] != og[k];
     // the pixel's own word in Y: its new label (marked), or - where Y lags behind - the label it keeps
     const bool lag = (w0[k] & 7) == mark_prev;
-    if (!near && valid[k] && (todo[k] || lag)) atomicMin(&Y[p0[k]], (g[k] << RR_MBITS) | (todo[k] ? mark : 0));     // (no value comes back: the thread does not wait for it; g == og unless todo)
+    if (!near && (INNER || valid[k]) && (todo[k] || lag)) atomicMin(&atb(Y, pb[k]), (g[k] << RR_MBITS) | (todo[k] ? mark : 0));     // (no value comes back: the thread does not wait for it; g == og unless todo)
     any_todo = any_todo || todo[k];
   }
   if (near) {
@@ -982,12 +984,12 @@ __global__ __launch_bounds__(64 * RR_TY) void k_region_round(int *X, int *Y, con
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < RR_PX; k++) {
-      if (!valid[k]) continue;
+      if (!INNER && !valid[k]) continue;
       const bool lag = (w0[k] & 7) == mark_prev;
       int w = (todo[k] || lag) ? ((g[k] << RR_MBITS) | (todo[k] ? mark : 0)) : 0x7fffffff;
       const int h = tmin[(ly + k) * 64 + lx];
       if (h != 0x7fffffff) { const int wh = (h << RR_MBITS) | mark; w = wh < w ? wh : w; }
-      if (w != 0x7fffffff) atomicMin(&Y[p0[k]], w);
+      if (w != 0x7fffffff) atomicMin(&atb(Y, pb[k]), w);
     }
     if (__any(any_todo) && threadIdx.x == 0) flags[round] = 1;
     return;
@@ -998,39 +1000,65 @@ __global__ __launch_bounds__(64 * RR_TY) void k_region_round(int *X, int *Y, con
     const int w = (val << RR_MBITS) | mark;
     if (w < ld_agent(&Y[key])) atomicMin(&Y[key], w);
   };
-  bool need[RR_PX];
-#pragma unroll
-  for (int k = 0; k < RR_PX; k++) {
-    // a lane whose (parent, proposal) pair repeats its left neighbour's adds nothing to a min: skip it (most lanes inside a region)
-    const int pog = __shfl_up(og[k], 1), pg = __shfl_up(g[k], 1), pt = __shfl_up((int)todo[k], 1);
-    need[k] = todo[k] && !(threadIdx.x > 0 && pt && pog == og[k] && pg == g[k]);
-  }
-  if (PHASE == 2) {       // the first rounds climb the raw chains: every pixel has a parent of its own (the pixel above it), nothing to combine
-    // (guard and atomic pixel by pixel: a guard only saves its atomic when the parent's own thread has written already, and the later it looks the more often that is - the
-    //  eight guards read together made this launch 195 instead of 151 us; no guards at all cost 3 % of the frame rate: the atomics are what is expensive)
-#pragma unroll
-    for (int k = 0; k < RR_PX; k++) { const int w = (g[k] << RR_MBITS) | mark; if (need[k] && w < ld_agent(&Y[og[k]])) atomicMin(&Y[og[k]], w); }
-  } else {
+  // From round 3 on most waves change nothing: such a wave has nothing to hook and executes nothing of what follows but the test.
+  if (__any(any_todo)) {
+    bool need[RR_PX];
 #pragma unroll
     for (int k = 0; k < RR_PX; k++) {
-      if (!need[k]) continue;
-      unsigned h = ((unsigned)og[k] * 2654435761u) >> 23;
-      int probes = 0;
-      for (;;) {
-        const int kprev = atomicCAS(&hk[h], -1, og[k]);
-        if (kprev == -1 || kprev == og[k]) { atomicMin(&hv[h], g[k]); break; }
-        h = (h + 1) & 511;
-        if (++probes == 16) { hook(og[k], g[k]); break; }
+      // a lane whose (parent, proposal) pair repeats its left neighbour's adds nothing to a min: skip it (most lanes inside a region).  The neighbour's pair comes by the
+      // wave shift of the front (wave_shr:1, no LDS instruction), lane 0 takes (0, 0).  The neighbour's `todo` need not travel: todo == (g != og) for every pixel (a pixel
+      // that does not act keeps g = og), so a pair equal to this pixel's pair (og, g) with g != og is a pair that acts - and (0, 0) only equals the pair of a pixel that does not.
+      const int pog = __builtin_amdgcn_mov_dpp(og[k], 0x138, 0xf, 0xf, true), pg = __builtin_amdgcn_mov_dpp(g[k], 0x138, 0xf, 0xf, true);
+      need[k] = todo[k] && (pog != og[k] || pg != g[k]);
+    }
+    if (PHASE == 2) {       // the first rounds climb the raw chains: every pixel has a parent of its own (the pixel above it), nothing to combine
+      // (guard and atomic pixel by pixel: a guard only saves its atomic when the parent's own thread has written already, and the later it looks the more often that is - the
+      //  eight guards read together made this launch 195 instead of 151 us; no guards at all cost 3 % of the frame rate: the atomics are what is expensive)
+#pragma unroll
+      for (int k = 0; k < RR_PX; k++) { const int w = (g[k] << RR_MBITS) | mark; if (need[k] && w < ld_agent(&Y[og[k]])) atomicMin(&Y[og[k]], w); }
+    } else {
+#pragma unroll
+      for (int k = 0; k < RR_PX; k++) {
+        if (!need[k]) continue;
+        unsigned h = ((unsigned)og[k] * 2654435761u) >> 23;
+        int probes = 0;
+        for (;;) {
+          const int kprev = atomicCAS(&hk[h], -1, og[k]);
+          if (kprev == -1 || kprev == og[k]) { atomicMin(&hv[h], g[k]); break; }
+          h = (h + 1) & 511;
+          if (++probes == 16) { hook(og[k], g[k]); break; }
+        }
       }
     }
+    if (threadIdx.x == 0) flags[round] = 1;
   }
-  if (__any(any_todo) && threadIdx.x == 0) flags[round] = 1;
   if (PHASE != 3) return;
   __syncthreads();
   for (int t = tid; t < 512; t += 64 * RR_TY) {
     const int key = hk[t];
     if (key != -1) hook(key, hv[t]);
   }
+}
+
+template <int PHASE>
+__global__ __launch_bounds__(64 * RR_TY) void k_region_round(int *X, int *Y, const u64 *__restrict__ allow, int iw, int ih, int *flags, int round, size_t zs, int gdim) {
+  // the exit first: a launch behind the settled one needs its frame's flag and nothing else - not its tile, not the other planes
+  const int z = rd_block_frame(gdim);
+  if (round > 0 && *(const int *)((const char *)(flags + (round - 1)) + (size_t)z * zs) == 0) return;
+  const rd_tile rd_b = rd_block_tile_of(gdim, z);
+  if (rd_b.x < 0) return;
+  const int bx = rd_b.x, by = rd_b.y;
+  RD_ZSHIFTZ(rd_b.z, zs, X, Y, allow, flags);
+  __shared__ int hk[PHASE == 3 ? 512 : 1], hv[PHASE == 3 ? 512 : 1];
+  __shared__ int tmin[PHASE == 1 ? 64 * RR_TY * RR_PX : 1];      // launch 1 only: the smallest proposal for each pixel of the block's tile (rr_tile)
+  const int tid = rd_ty() * 64 + threadIdx.x;
+  if (PHASE == 3) for (int t = tid; t < 512; t += 64 * RR_TY) { hk[t] = -1; hv[t] = 0x7fffffff; }
+  if (PHASE == 1) for (int t = tid; t < 64 * RR_TY * RR_PX; t += 64 * RR_TY) tmin[t] = 0x7fffffff;
+  if (PHASE != 2) __syncthreads();
+  // the tile and its one-pixel ring inside the frame (scalar): 28 x 32 of the 30 x 34 tiles of a 1920x1080 frame
+  const bool inner = bx > 0 && by > 0 && bx * 64 + 65 <= iw && by * (RR_TY * RR_PX) + RR_TY * RR_PX + 1 <= ih;
+  if (inner) rr_tile<PHASE, true>(X, Y, allow, iw, ih, flags, round, bx, by, hk, hv, tmin);
+  else rr_tile<PHASE, false>(X, Y, allow, iw, ih, flags, round, bx, by, hk, hv, tmin);
 }
 
 // rc:336-346: out[label]++ for every pixel.  Most pixels belong to a handful of huge regions, so counts are
