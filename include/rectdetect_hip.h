@@ -400,7 +400,7 @@ void rd_tensor_limits(int32_t out[4]);
  * ordinary rd_rectifier: rd_rectifier_enqueue, rd_rectifier_wait, rd_rectifier_destroy and rd_detector_rectify_polled work on it with every pixel format, frame
  * kind and output kind, and `out` holds n * rd_rectifier_patch_bytes(r) bytes. */
 rd_rectifier *rd_rectifier_create_tensor(int device, int pw, int ph, int max_quads, int njobs, const rd_tensor_spec *spec);
-/* the bytes of one quad's output: pw * ph * 3 for a rectifier made by rd_rectifier_create, rd_tensor_bytes, rd_scan_bytes, rd_grade_bytes or rd_code_bytes of the spec for the others; 0 for NULL */
+/* the bytes of one quad's output: pw * ph * 3 for a rectifier made by rd_rectifier_create, rd_tensor_bytes, rd_scan_bytes, rd_grade_bytes, rd_code_bytes or rd_blob_bytes of the spec for the others; 0 for NULL */
 size_t rd_rectifier_patch_bytes(const rd_rectifier *r);
 
 /* -- scanned pages: the quad as a clean page - the patch's luma divided by its local mean (shading correction) or compared with it (adaptive threshold), as bytes
@@ -559,6 +559,67 @@ void rd_code_upright(const double quad[8], int rot, double out[8]);
  * rd_rectifier_enqueue, rd_rectifier_wait, rd_rectifier_destroy and rd_detector_rectify_polled work on it with every pixel format, frame kind and output kind,
  * rd_rectifier_patch_bytes is 48, and `out` holds n * 48 bytes, 8-byte aligned. */
 rd_rectifier *rd_rectifier_create_code(int device, int pw, int ph, int max_quads, int njobs, const rd_code_spec *spec, const uint64_t *dict, int ndict);
+
+/* -- page components: the quad's page as OBJECTS - the connected ink regions of the bilevel page, each reduced to a record (bounding box, area, first pixel, coordinate
+ * sums), a head of counts per quad, and optionally the page with everything outside the area filter removed (despeckle) - what OCR and layout engines, form readers
+ * and dot counters take next, and what a G4 / JBIG2 encoder wants gone (rd_k_blob.hip, rd_rectify.hip, rd_blob_host.c).  Exact, in integers, like everything above:
+ * tests/blobs.py restates it in numpy and Python integers, rd_blob_page_host states it in C.
+ *
+ * A spec is LEGAL for pw x ph when 0 <= radius <= 63, 0 <= k <= 255, 0 <= d <= 255 and d == 0 when radius == 0, oversample m is 1, 2 or 4, invert is 0 or 1,
+ * connectivity is 4 or 8, 1 <= min_area <= 1<<22, max_area == 0 (no upper bound) or min_area <= max_area <= 1<<22, 1 <= max_blobs <= 4096, page is 0 or 1, both
+ * reserved words are 0, pw >= 1, ph >= 1, pw*m <= 16384, ph*m <= 16384 and pw*ph <= 1<<22.
+ *
+ * Quad k:
+ *   1. Ink.  G is, byte for byte, step 1 of "scanned pages": the { RD_TENSOR_U8, RD_TENSOR_NHWC, RD_TENSOR_GRAY, m } tensor, inverted where `invert` says so.
+ *      radius >= 1: ink is step 3 of "scanned pages" with the same radius, k, d.  radius == 0: a fixed level, ink = G <= k (the inside of a large dark area - a filled
+ *      check box, a dot, an LED - is never ink under an adaptive threshold).
+ *   2. Components.  A component is a maximal set of ink pixels connected through 4 or 8 neighbours inside the patch.  Its `first` is the smallest j*pw + i among its
+ *      pixels, `area` their count, x0, y0, x1, y1 their inclusive bounding box, sx and sy the sums of i and of j over them (int64: the sums of a full 2048 x 2048 page,
+ *      4 292 870 144, do not fit int32).
+ *   3. Kept.  A component is KEPT when min_area <= area and (max_area == 0 or area <= max_area).
+ *   4. Head (rd_blob_head, 32 bytes): ink = ink pixels; all = components before the filter; found = kept components; written = min(found, max_blobs); ink_kept =
+ *      pixels of kept components; largest = the largest area before the filter, 0 without ink; flags = bit 0 (RD_BLOB_OVERFLOW) set when found > max_blobs; reserved = 0.
+ *   5. Records.  max_blobs records (rd_blob, 40 bytes) follow the head: the first `written` are the kept components in ascending `first`; on overflow the ones with
+ *      the smallest `first` survive - a rule, not an accident of scheduling; the rest are zero bytes.
+ *   6. Page.  With page == 1 the cleaned page follows at offset 32 + 40*max_blobs: the kept components only - all of them, whatever max_blobs - in the RD_SCAN_BITS
+ *      layout with pad bits 0, padded with zero bytes to a multiple of 8 (records stay 8-aligned from quad to quad).
+ *   7. Sizes.  rd_blob_bytes = 32 + 40*max_blobs, plus ((((pw + 7) >> 3)*ph + 7) & ~7) with a page.  An invalid quad (status 0) gives all-zero bytes.  The job's
+ *      n * rd_rectifier_patch_bytes(r) bytes are written and nothing else; they are complete when rd_rectifier_wait returns.  `out` must be 8-byte aligned:
+ *      rd_rectifier_enqueue (and rd_detector_rectify_polled) return -1 with nothing enqueued when it is not.
+ *
+ * Launches per job: the G plane by the tensor kernel; the ink bits by the scan kernel in RD_SCAN_BITS mode (radius >= 1: no new arithmetic, a difference from a scan
+ * job is impossible by construction) or by a threshold kernel (radius == 0); then the component stage: labels per tile in LDS, tiles joined across their borders,
+ * areas per run, kept roots ranked in raster order, records and the cleaned page per run (rd_k_blob.hip's head comment).  Scratch: 8 bytes per page pixel per quad
+ * of a job slot, allocated on first use. */
+#define RD_BLOB_OVERFLOW 1      /* rd_blob_head::flags: more kept components than max_blobs */
+typedef struct { int32_t radius, k, d, oversample, invert, connectivity, min_area, max_area, max_blobs, page, reserved[2]; } rd_blob_spec;   /* 48 bytes */
+typedef struct { int32_t ink, all, found, written, ink_kept, largest, flags, reserved; } rd_blob_head;                                    /* 32 bytes */
+typedef struct { int32_t x0, y0, x1, y1, area, first; int64_t sx, sy; } rd_blob;                                                          /* 40 bytes */
+/* host only, no GPU needed (rd_blob_host.c).  1 when the spec is legal for pw x ph, else 0 (a NULL spec too) */
+int rd_blob_spec_ok(const rd_blob_spec *spec, int pw, int ph);
+/* the bytes of one quad's output (step 7); 0 for a spec that is not legal for pw x ph */
+size_t rd_blob_bytes(const rd_blob_spec *spec, int pw, int ph);
+/* out[0] <- the legal connectivities as a bit set (bit v: value v is legal), out[1] <- the legal oversamplings ORed together (1 | 2 | 4), out[2] <- the largest
+ * radius, out[3] <- the largest max_blobs, out[4] <- the largest pw*ph, out[5], out[6] <- the width and the height, in pixels, of the tile a block of the tile kernel
+ * labels, out[7] <- 0 */
+void rd_blob_limits(int32_t out[8]);
+/* steps 2-7 for one page: `bits` is a pw x ph page in the RD_SCAN_BITS layout (its pad bits are ignored), `out` gets rd_blob_bytes(spec, pw, ph) bytes (8-byte
+ * aligned).  Only connectivity, min_area, max_area, max_blobs and page of the spec decide the result.  Returns 1; returns 0 and writes nothing for a NULL argument,
+ * a spec that is not legal for pw x ph, an `out` that is not 8-byte aligned or when its work space cannot be allocated.  The contract's statement in C, and the host
+ * baseline of tools/bench_blobs.py; nothing in the frame path calls it. */
+int rd_blob_page_host(const uint8_t *bits, int pw, int ph, const rd_blob_spec *spec, void *out);
+/* A rectifier whose jobs write page components.  NULL for the bad arguments of rd_rectifier_create, a NULL spec, a spec that is not legal for pw x ph, or
+ * (size_t)max_quads*pw*ph > 1<<27 (the scratch of a slot).  The handle is an ordinary rd_rectifier: rd_rectifier_enqueue, rd_rectifier_wait, rd_rectifier_destroy
+ * and rd_detector_rectify_polled work on it with every pixel format, frame kind and output kind, and `out` holds n * rd_rectifier_patch_bytes(r) bytes, 8-byte
+ * aligned. */
+rd_rectifier *rd_rectifier_create_blobs(int device, int pw, int ph, int max_quads, int njobs, const rd_blob_spec *spec);
+/* test tap: the component stage alone (steps 2-7) on n pages of the caller, through the job path's own launch function (rdk::blobs), so that crafted masks reach it
+ * unchanged.  `bits`: n pages of pw x ph in the RD_SCAN_BITS layout back to back, ((pw + 7) >> 3)*ph bytes each, pad bits ignored; `out`: n * rd_blob_bytes bytes.
+ * Both are host pointers.  Runs once on `device`, on a stream and scratch of its own, then frees everything.  info[0] = the path that ran (0: tiles and borders -
+ * the only one), [1] = kernel launches, [2] = memsets on the stream, [3], [4] = tiles in x and in y, [5] = 1 when the border kernel ran, [6], [7] = 0.
+ * Returns 0, or -1 without touching the device for a NULL pointer, n outside 1 .. 65535, a spec that is not legal for pw x ph (only the fields of steps 2-7 are
+ * read beyond that) or (size_t)n*pw*ph > 1<<27.  Needs a GPU (fatal without one); not called by the frame path. */
+int rd_blobs_pages_device(int device, const uint8_t *bits, int pw, int ph, int n, const rd_blob_spec *spec, void *out, int32_t info[8]);
 
 /* ---- annotated frames: rectangles' outlines and line segments drawn INTO a frame on the device (rd_k_annotate.hip, rd_annotate.hip) - the picture vidrect.cpp /
  * rect.cpp (showRect) and vidpoly.cpp / poly.cpp make with OpenCV's line() on the host, for frames that never leave HBM.  OpenCV's round brush is not restated; the

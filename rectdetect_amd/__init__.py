@@ -13,7 +13,8 @@ Mirrors of the reference programs' call sequences:
   * :class:`Rectifier` - the ``rd_rectifier`` extension: what is inside detected quads as upright patches of fixed size, or - with a
     :func:`tensor_spec` - as model-ready tensors (float, planar, normalised, box-filtered), or - with a :func:`scan_spec` - as scanned pages (shading-corrected
     gray, bilevel bytes or packed bit rows), or - with a :func:`grade_spec` - as graded quads (per-cell sharpness, exposure and glare records, a histogram),
-    or - with a :func:`code_spec` and a dictionary - as decoded quads (a grid code's payload, its id, rotation and Hamming distance)
+    or - with a :func:`code_spec` and a dictionary - as decoded quads (a grid code's payload, its id, rotation and Hamming distance), or - with a
+    :func:`blob_spec` - as page components (the connected ink regions of the bilevel page as boxes, areas and coordinate sums, and the despeckled page)
   * :class:`Annotator` - the ``rd_annotator`` extension: rectangles' outlines and line segments drawn into frames on the device
   * :class:`Compositor` - the ``rd_compositor`` extension: a colour or an image written into the quads of a frame on the device
   * :class:`Matcher` - the ``rd_matcher`` extension: which template of a library is inside each quad, decided on the device
@@ -64,6 +65,13 @@ CODE_SPEC_DTYPE = np.dtype([("n", "<i4"), ("border", "<i4"), ("inset", "<i4"), (
 CODE_DTYPE = np.dtype([("bits", "<u8"), ("id", "<i4"), ("rot", "<i4"), ("hamming", "<i4"), ("second", "<i4"), ("border_errors", "<i4"), ("lo", "<i4"), ("hi", "<i4"), ("margin", "<i4"), ("ok", "<i4"), ("reserved", "<i4")])
 assert CODE_SPEC_DTYPE.itemsize == 32 and CODE_DTYPE.itemsize == 48
 CODE_BYTES, CODE_MAX_DICT, CODE_NONE = 48, 4096, 65
+# a rectifier's blob spec, the head of a quad and the record of a component (rd_blob_spec, rd_blob_head, rd_blob; the contract is in include/rectdetect_hip.h, "page components")
+BLOB_SPEC_DTYPE = np.dtype([("radius", "<i4"), ("k", "<i4"), ("d", "<i4"), ("oversample", "<i4"), ("invert", "<i4"), ("connectivity", "<i4"), ("min_area", "<i4"), ("max_area", "<i4"),
+                            ("max_blobs", "<i4"), ("page", "<i4"), ("reserved", "<i4", (2,))])
+BLOB_HEAD_DTYPE = np.dtype([(n, "<i4") for n in ("ink", "all", "found", "written", "ink_kept", "largest", "flags", "reserved")])
+BLOB_DTYPE = np.dtype([("x0", "<i4"), ("y0", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("area", "<i4"), ("first", "<i4"), ("sx", "<i8"), ("sy", "<i8")])
+assert BLOB_SPEC_DTYPE.itemsize == 48 and BLOB_HEAD_DTYPE.itemsize == 32 and BLOB_DTYPE.itemsize == 40
+BLOB_HEAD_BYTES, BLOB_BYTES, BLOB_OVERFLOW = 32, 40, 1
 ANNOT_SEG_ALL, ANNOT_SEG_CHAINS = 0, 1
 
 # pixel formats of enqueue_planes (rd_detector_enqueue_planes; the conversion contract is in include/rectdetect_hip.h)
@@ -174,6 +182,13 @@ def _declare(L):
         "rd_code_render": (cz, [vp, ctypes.c_uint64, ci, vp]),
         "rd_code_upright": (None, [vp, ci, vp]),
         "rd_rectifier_create_code": (vp, [ci, ci, ci, ci, ci, vp, vp, ci]),
+        # page components (rd_rectify.hip, rd_blob_host.c)
+        "rd_blob_spec_ok": (ci, [vp, ci, ci]),
+        "rd_blob_bytes": (cz, [vp, ci, ci]),
+        "rd_blob_limits": (None, [vp]),
+        "rd_blob_page_host": (ci, [vp, ci, ci, vp, vp]),
+        "rd_rectifier_create_blobs": (vp, [ci, ci, ci, ci, ci, vp]),
+        "rd_blobs_pages_device": (ci, [ci, vp, ci, ci, ci, vp, vp, vp]),
         # annotated frames (rd_annotate.hip)
         "rd_annot_covers": (ci, [vp, ci, ci]),
         "rd_annot_touches": (ci, [vp, ci, ci, ci, ci]),
@@ -988,17 +1003,101 @@ def code_view(arr):
     return np.ascontiguousarray(arr, dtype=np.uint8).reshape(-1, CODE_BYTES).view(CODE_DTYPE).reshape(-1)
 
 
+def blob_spec(radius=15, k=26, d=0, oversample=1, invert=False, connectivity=8, min_area=1, max_area=0, max_blobs=256, page=False):
+    """an rd_blob_spec as a BLOB_SPEC_DTYPE record: the ink decision of a scan spec (radius, k, d, oversample, invert; radius 0: a fixed level, ink = G <= k),
+    components through 4 or 8 neighbours, kept when min_area <= area (and area <= max_area unless that is 0), at most max_blobs records per quad, page for the
+    cleaned page behind them.  Whether it is legal is decided where it is used (blob_spec_ok, Rectifier)."""
+    s = np.zeros((), BLOB_SPEC_DTYPE)
+    s["radius"], s["k"], s["d"], s["oversample"], s["invert"], s["connectivity"] = radius, k, d, oversample, int(invert), connectivity
+    s["min_area"], s["max_area"], s["max_blobs"], s["page"] = min_area, max_area, max_blobs, int(page)
+    return s
+
+
+def _blob_arg(spec):
+    return np.ascontiguousarray(spec, dtype=BLOB_SPEC_DTYPE).reshape(())
+
+
+def blob_spec_ok(spec, pw, ph):
+    """whether a blob spec is legal for pw x ph pages (rd_blob_spec_ok); runs without a GPU"""
+    return bool(lib().rd_blob_spec_ok(_blob_arg(spec).ctypes.data, int(pw), int(ph)))
+
+
+def blob_bytes(spec, pw, ph):
+    """the bytes of one quad's head, records and page, 0 for a spec that is not legal (rd_blob_bytes); runs without a GPU"""
+    return int(lib().rd_blob_bytes(_blob_arg(spec).ctypes.data, int(pw), int(ph)))
+
+
+def blob_limits():
+    """{"connectivities", "oversamplings", "max_radius", "max_blobs", "max_pixels", "tile_w", "tile_h"}: the legal values of a blob spec's fields and the tile kernel's
+    tile (rd_blob_limits); runs without a GPU"""
+    a = np.zeros(8, np.int32)
+    lib().rd_blob_limits(a.ctypes.data)
+    bits = lambda v: tuple(k for k in range(31) if v >> k & 1)
+    return {"connectivities": bits(int(a[0])), "oversamplings": tuple(1 << k for k in bits(int(a[1]))), "max_radius": int(a[2]), "max_blobs": int(a[3]), "max_pixels": int(a[4]),
+            "tile_w": int(a[5]), "tile_h": int(a[6])}
+
+
+def _bit_pages(bits, pw, ph):
+    b = np.ascontiguousarray(bits, dtype=np.uint8)
+    rb = (int(pw) + 7) // 8
+    if pw < 1 or ph < 1 or b.size == 0 or b.size % (rb * int(ph)):
+        raise ValueError("bit pages of %r bytes are not whole pages of %r x %r pixels" % (b.size, pw, ph))
+    return b.reshape(-1, int(ph), rb)
+
+
+def blob_page_host(bits, pw, ph, spec):
+    """steps 2-7 of "page components" for one pw x ph page in the SCAN_BITS layout, on the host (rd_blob_page_host): its blob_bytes bytes; runs without a GPU"""
+    b, s = _bit_pages(bits, pw, ph), _blob_arg(spec)
+    nb = blob_bytes(s, pw, ph)
+    out = np.zeros(max(nb, 8) // 8, np.uint64)      # (8-byte aligned)
+    if len(b) != 1 or not nb or not lib().rd_blob_page_host(b.ctypes.data, int(pw), int(ph), s.ctypes.data, out.ctypes.data):
+        raise ValueError("rd_blob_page_host: invalid arguments (%d pages of %r x %r, spec %r)" % (len(b), pw, ph, spec))
+    return out.view(np.uint8)[:nb].copy()
+
+
+def blob_view(arr, spec, pw, ph):
+    """a blobs job's bytes (what Rectifier.rectify returns, or any (n, patch_bytes) uint8 array) as (the heads, a BLOB_HEAD_DTYPE array of n; the records, a BLOB_DTYPE
+    array of shape (n, max_blobs) of which the first heads["written"] of a row count; the cleaned pages as an (n, ph, (pw + 7) // 8) uint8 array, or None without page)"""
+    s = _blob_arg(spec)
+    B, rb = int(s["max_blobs"]), (int(pw) + 7) // 8
+    nb = BLOB_HEAD_BYTES + BLOB_BYTES * B + (((rb * int(ph) + 7) & ~7) if int(s["page"]) else 0)
+    a = np.ascontiguousarray(arr, dtype=np.uint8).reshape(-1, nb)
+    heads = np.ascontiguousarray(a[:, :BLOB_HEAD_BYTES]).view(BLOB_HEAD_DTYPE).reshape(-1)
+    recs = np.ascontiguousarray(a[:, BLOB_HEAD_BYTES:BLOB_HEAD_BYTES + BLOB_BYTES * B]).view(BLOB_DTYPE).reshape(len(a), B)
+    at = BLOB_HEAD_BYTES + BLOB_BYTES * B
+    pages = np.ascontiguousarray(a[:, at:at + rb * int(ph)]).reshape(len(a), int(ph), rb) if int(s["page"]) else None
+    return heads, recs, pages
+
+
+def blobs_pages(bits, pw, ph, spec, device=0, guard=0):
+    """The component stage alone (rd_blobs_pages_device) on n pages of pw x ph pixels in the SCAN_BITS layout (any array of n * ph * ((pw + 7) // 8) bytes; pad bits are
+    ignored): ((n, blob_bytes) uint8, info = {"path", "launches", "memsets", "tiles_x", "tiles_y", "border"}).  guard > 0: the output lies between two runs of that
+    many bytes of 0xA5, which must come back untouched.  Needs a GPU."""
+    b, s = _bit_pages(bits, pw, ph), _blob_arg(spec)
+    n, nb = len(b), blob_bytes(s, pw, ph)
+    g = (int(guard) + 7) & ~7
+    buf = np.full((n * nb + 2 * g + 7) // 8, 0xA5A5A5A5A5A5A5A5, np.uint64).view(np.uint8)      # (8-byte aligned, like a job's out)
+    info = np.zeros(8, np.int32)
+    if not nb or lib().rd_blobs_pages_device(int(device), b.ctypes.data, int(pw), int(ph), n, s.ctypes.data, buf.ctypes.data + g, info.ctypes.data) != 0:
+        raise ValueError("rd_blobs_pages_device: invalid arguments (%d pages of %r x %r, spec %r)" % (n, pw, ph, spec))
+    if g and not (np.all(buf[:g] == 0xA5) and np.all(buf[g + n * nb:] == 0xA5)):
+        raise RuntimeError("rd_blobs_pages_device wrote outside its %d bytes" % (n * nb))
+    names = ("path", "launches", "memsets", "tiles_x", "tiles_y", "border")
+    return buf[g:g + n * nb].reshape(n, nb).copy(), {k: int(v) for k, v in zip(names, info)}
+
+
 class Rectifier(_Service):
     """The rd_rectifier extension: pw x ph BGR patches of up to max_quads quads per job, njobs jobs in flight (the contract: include/rectdetect_hip.h).  With
     tensor=tensor_spec(...) a job writes model-ready tensors instead ("model-ready tensors" there), with scan=scan_spec(...) scanned pages ("scanned pages"):
     `out` then holds n * patch_bytes bytes of shape(n) and dtype.  With grade=grade_spec(...) a job writes graded quads ("graded quads"): n rows of patch_bytes bytes, 8-byte aligned, which
     grade_view takes apart.  With code=code_spec(...) and dictionary=a uint64 array (or None: raw bits only) a job writes decoded quads ("decoded quads"): n rows of
-    48 bytes, 8-byte aligned, which code_view turns into records."""
+    48 bytes, 8-byte aligned, which code_view turns into records.  With blobs=blob_spec(...) a job writes page components ("page components"): n rows of patch_bytes
+    bytes, 8-byte aligned, which blob_view takes apart."""
     _name = "rectifier"
 
-    def __init__(self, pw, ph, max_quads=64, njobs=2, device=0, tensor=None, scan=None, grade=None, code=None, dictionary=None):
-        if (tensor is not None) + (scan is not None) + (grade is not None) + (code is not None) > 1:
-            raise ValueError("Rectifier: tensor=, scan=, grade= and code= exclude each other")
+    def __init__(self, pw, ph, max_quads=64, njobs=2, device=0, tensor=None, scan=None, grade=None, code=None, dictionary=None, blobs=None):
+        if (tensor is not None) + (scan is not None) + (grade is not None) + (code is not None) + (blobs is not None) > 1:
+            raise ValueError("Rectifier: tensor=, scan=, grade=, code= and blobs= exclude each other")
         if dictionary is not None and code is None:
             raise ValueError("Rectifier: dictionary= goes with code=")
         self.pw, self.ph, self.max_quads, self.njobs = pw, ph, max_quads, njobs
@@ -1007,7 +1106,10 @@ class Rectifier(_Service):
         self.grade = None if grade is None else _grade_arg(grade).copy()
         self.code = None if code is None else _code_arg(code).copy()
         self.dictionary = None if code is None else _dict_arg(dictionary).copy()
-        if self.code is not None:
+        self.blobs = None if blobs is None else _blob_arg(blobs).copy()
+        if self.blobs is not None:
+            self._create(device, pw, ph, max_quads, njobs, self.blobs.ctypes.data, ctor="create_blobs")
+        elif self.code is not None:
             d = self.dictionary
             self._create(device, pw, ph, max_quads, njobs, self.code.ctypes.data, d.ctypes.data if len(d) else None, len(d), ctor="create_code")
         elif self.grade is not None:
@@ -1030,8 +1132,8 @@ class Rectifier(_Service):
         return TENSOR_NUMPY[int(self.tensor["dtype"])] if self.tensor is not None else np.dtype(np.uint8)
 
     def shape(self, n):
-        """the shape of a job of n quads: (n, ph, pw, C) or, under TENSOR_NCHW, (n, C, ph, pw); scanned pages: (n, ph, pw) or, under SCAN_BITS, (n, ph, (pw + 7) // 8); graded and decoded quads: (n, patch_bytes)"""
-        if self.grade is not None or self.code is not None:
+        """the shape of a job of n quads: (n, ph, pw, C) or, under TENSOR_NCHW, (n, C, ph, pw); scanned pages: (n, ph, pw) or, under SCAN_BITS, (n, ph, (pw + 7) // 8); graded and decoded quads and page components: (n, patch_bytes)"""
+        if self.grade is not None or self.code is not None or self.blobs is not None:
             return (n, self.patch_bytes)
         if self.scan is not None:
             return (n, self.ph, (self.pw + 7) // 8 if int(self.scan["mode"]) == SCAN_BITS else self.pw)

@@ -203,6 +203,16 @@ void grade(hipStream_t s, uint8_t *out, const uint8_t *plane, const RectifyQuad 
 // n * pw * ph + RD_CODE_PLANE_PAD; the launcher aborts otherwise
 void code(hipStream_t s, uint8_t *out, const uint8_t *plane, size_t plane_bytes, const RectifyQuad *quads, int n, int pw, int ph, const rd_code_spec &spec, const uint64_t *dict, int ndict);
 
+// ---- rd_k_blob.hip: page components (the contract: rectdetect_hip.h, "page components")
+// radius == 0: the ink bits of n quads, ink = (inverted) G <= spec.k, quad k's ((pw + 7) >> 3) * ph bytes at bits + k * that in the RD_SCAN_BITS layout, from the G plane
+// rectify_tensor made of the same quads; an invalid quad's bits are left as they are (the component stage never reads them), one launch
+void blob_level(hipStream_t s, uint8_t *bits, const uint8_t *plane, const RectifyQuad *quads, int n, int pw, int ph, const rd_blob_spec &spec);
+// the component stage: steps 2-7 of n quads under spec (legal for pw x ph: rd_blob_spec_ok), quad k's rd_blob_bytes(spec, pw, ph) bytes at out + k * that (8-byte
+// aligned; zeroed here, on s).  labels, areas: n * pw * ph ints each, both overwritten; the quads' ink bits lie at the START of areas, quad k's at
+// (uint8_t *)areas + k * ((pw + 7) >> 3) * ph in the RD_SCAN_BITS layout (pad bits ignored).  quads may be null: every quad is valid (the test tap); otherwise an
+// invalid quad's bytes stay zero.  Three memsets and four or five launches (quad = blockIdx.z).  info (may be null): what rd_blobs_pages_device reports
+void blobs(hipStream_t s, uint8_t *out, int *labels, int *areas, const RectifyQuad *quads, int n, int pw, int ph, const rd_blob_spec &spec, int info[8]);
+
 // ---- rd_k_match.hip: matched quads (the contract: rectdetect_hip.h, "matched quads")
 // the signatures of n quads of one frame: quad k's G * G int8 values at sig + k * G * G (zeros for an invalid quad), its sa, saa ADDED to sums[2k], sums[2k+1]
 // (cleared by the caller); G in {8, 16, 32, 64}, m in {1, 2, 4}

@@ -1,9 +1,10 @@
 // rectdetect-mi355x: the rectifier - rectified patches of quads behind the detector's poll (the contract: include/rectdetect_hip.h, "rectified patches";
 // the kernels: rd_k_rectify.hip and, for a rectifier made with a tensor spec, rd_k_tensor.hip ("model-ready tensors"); made with a scan spec, rd_k_tensor.hip into a
-// G plane of the rectifier's own and rd_k_scan.hip from there ("scanned pages"); made with a grade spec, the same G plane and rd_k_grade.hip ("graded quads"); made with a code spec and a dictionary, the same G plane and rd_k_code.hip ("decoded quads"); the jobs in flight, the frame's checks and its way to the device: rd_jobs.h).
+// G plane of the rectifier's own and rd_k_scan.hip from there ("scanned pages"); made with a grade spec, the same G plane and rd_k_grade.hip ("graded quads"); made with a code spec and a dictionary, the same G plane and rd_k_code.hip ("decoded quads"); made with a blob spec, the same G plane, its ink bits by rd_k_scan.hip or rd_k_blob.hip's level kernel and rd_k_blob.hip's component stage ("page components"); the jobs in flight, the frame's checks and its way to the device: rd_jobs.h).
 #include "rd_jobs.h"
 #include "rd_kernels.h"
 #include "rd_code_tile.h"
+#include "rd_blob_tile.h"
 #include <math.h>
 #include <stdio.h>
 
@@ -12,7 +13,7 @@ using namespace rdjob;
 struct rd_rectifier {
   Ring ring;                                // (first: rd_jobs.h)
   int pw, ph;
-  size_t patch_bytes;                       // of one quad's output: pw * ph * 3, or rd_tensor_bytes / rd_scan_bytes / rd_grade_bytes / rd_code_bytes of the spec
+  size_t patch_bytes;                       // of one quad's output: pw * ph * 3, or rd_tensor_bytes / rd_scan_bytes / rd_grade_bytes / rd_code_bytes / rd_blob_bytes of the spec
   int tensor;                               // made by rd_rectifier_create_tensor: jobs launch rdk::rectify_tensor with `spec`
   rd_tensor_spec spec;
   int scan;                                 // made by rd_rectifier_create_scan: jobs launch rdk::rectify_tensor with `spec` ({ U8, NHWC, GRAY, m }) into d_plane, then rdk::scan with `sspec`
@@ -23,7 +24,10 @@ struct rd_rectifier {
   rd_code_spec cspec;
   uint64_t *d_dict;                         // (NULL when ndict is 0)
   int ndict;
-  uint8_t **d_plane;                        // per slot: the G planes of max_quads quads, pw * ph bytes each (allocated on first use; scan, grade and code rectifiers only)
+  int blob;                                 // made by rd_rectifier_create_blobs: the same G plane, then the ink bits - rdk::scan with `sspec` (RD_SCAN_BITS; radius >= 1) or rdk::blob_level - into the start of d_areas, then rdk::blobs under `bspec`
+  rd_blob_spec bspec;
+  int **d_labels, **d_areas;                // per slot: the component stage's two int planes of max_quads quads, pw * ph ints each (allocated on first use; blob rectifiers only)
+  uint8_t **d_plane;                        // per slot: the G planes of max_quads quads, pw * ph bytes each (allocated on first use; scan, grade, code and blob rectifiers only)
   rdk::RectifyQuad *d_quads, *h_quads;      // njobs blocks of max_quads each, a job's at slot * max_quads: pinned staging and their place in the device array
   uint8_t **d_out;                          // per slot: max_quads patches on their way to pinned host memory (allocated on first use)
   DevBuf frame;                             // host and pinned frames travel through here
@@ -77,13 +81,14 @@ static void gray_plane(rd_rectifier *r, int njobs, int oversample) {
   r->d_plane = (uint8_t **)calloc(njobs, sizeof(uint8_t *));
 }
 
-// spec == NULL, sspec == NULL, gspec == NULL and cspec == NULL: the classic rectifier
+// spec == NULL, sspec == NULL, gspec == NULL, cspec == NULL and bspec == NULL: the classic rectifier
 static rd_rectifier *rectifier_create(int device, int pw, int ph, int max_quads, int njobs, const rd_tensor_spec *spec, const rd_scan_spec *sspec = NULL, const rd_grade_spec *gspec = NULL,
-                                      const rd_code_spec *cspec = NULL, const uint64_t *dict = NULL, int ndict = 0) {
+                                      const rd_code_spec *cspec = NULL, const uint64_t *dict = NULL, int ndict = 0, const rd_blob_spec *bspec = NULL) {
   if (pw < 1 || ph < 1 || pw > 16384 || ph > 16384 || max_quads < 1 || max_quads > 65535 || !ring_args_ok(device, njobs)) return NULL;
   if (spec && !rd_tensor_spec_ok(spec, pw, ph)) return NULL;
   if (sspec && !rd_scan_spec_ok(sspec, pw, ph)) return NULL;
   if (gspec && !rd_grade_spec_ok(gspec, pw, ph)) return NULL;
+  if (bspec && (!rd_blob_spec_ok(bspec, pw, ph) || (size_t)max_quads * pw * ph > RD_BLOB_MAX_SLOT_PIXELS)) return NULL;
   if (cspec) {
     if (!rd_code_spec_ok(cspec, pw, ph) || ndict < 0 || ndict > RD_CODE_MAX_DICT || (ndict > 0 && !dict)) return NULL;
     const int bits = cspec->n * cspec->n;
@@ -113,6 +118,15 @@ static rd_rectifier *rectifier_create(int device, int pw, int ph, int max_quads,
       RD_HIP(hipMemcpy(r->d_dict, dict, (size_t)ndict * sizeof(uint64_t), hipMemcpyHostToDevice));
     }
   }
+  if (bspec) {
+    r->blob = 1; r->bspec = *bspec;
+    r->patch_bytes = rd_blob_bytes(bspec, pw, ph);
+    gray_plane(r, njobs, bspec->oversample);
+    const rd_scan_spec ink = { RD_SCAN_BITS, bspec->radius, bspec->k, bspec->d, 255, bspec->oversample, bspec->invert, 0 };      // (white: not read in this mode; radius 0 never reaches rdk::scan)
+    r->sspec = ink;
+    r->d_labels = (int **)calloc(njobs, sizeof(int *));
+    r->d_areas = (int **)calloc(njobs, sizeof(int *));
+  }
   const size_t nq = (size_t)njobs * max_quads;
   RD_HIP(hipMalloc((void **)&r->d_quads, nq * sizeof(rdk::RectifyQuad)));
   RD_HIP(hipHostMalloc((void **)&r->h_quads, nq * sizeof(rdk::RectifyQuad), hipHostMallocDefault));
@@ -138,6 +152,31 @@ rd_rectifier *rd_rectifier_create_code(int device, int pw, int ph, int max_quads
   return spec ? rectifier_create(device, pw, ph, max_quads, njobs, NULL, NULL, NULL, spec, dict, ndict) : NULL;
 }
 
+rd_rectifier *rd_rectifier_create_blobs(int device, int pw, int ph, int max_quads, int njobs, const rd_blob_spec *spec) {
+  return spec ? rectifier_create(device, pw, ph, max_quads, njobs, NULL, NULL, NULL, NULL, NULL, 0, spec) : NULL;
+}
+
+int rd_blobs_pages_device(int device, const uint8_t *bits, int pw, int ph, int n, const rd_blob_spec *spec, void *out, int32_t info[8]) {
+  if (!bits || !spec || !out || !info || n < 1 || n > 65535 || !rd_blob_spec_ok(spec, pw, ph) || (size_t)n * pw * ph > RD_BLOB_MAX_SLOT_PIXELS) return -1;
+  RD_HIP(hipSetDevice(device));
+  const size_t npix = (size_t)n * pw * ph, page_bytes = (size_t)((pw + 7) >> 3) * ph, bytes = (size_t)n * rd_blob_bytes(spec, pw, ph);
+  int *d_labels = NULL, *d_areas = NULL;
+  uint8_t *d_out = NULL;
+  hipStream_t st = NULL;
+  RD_HIP(hipMalloc((void **)&d_labels, npix * sizeof(int)));
+  RD_HIP(hipMalloc((void **)&d_areas, npix * sizeof(int)));
+  RD_HIP(hipMalloc((void **)&d_out, bytes));
+  RD_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  RD_HIP(hipMemcpyAsync(d_areas, bits, n * page_bytes, hipMemcpyHostToDevice, st));      // (where a job's ink decision puts them)
+  rdk::blobs(st, d_out, d_labels, d_areas, NULL, n, pw, ph, *spec, info);
+  rdrt::check_launch("rd_blobs_pages_device");
+  RD_HIP(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));
+  RD_HIP(hipStreamSynchronize(st));
+  RD_HIP(hipStreamDestroy(st));
+  RD_HIP(hipFree(d_out)); RD_HIP(hipFree(d_areas)); RD_HIP(hipFree(d_labels));
+  return 0;
+}
+
 size_t rd_rectifier_patch_bytes(const rd_rectifier *r) { return r ? r->patch_bytes : 0; }
 
 void rd_rectifier_destroy(rd_rectifier *r) {
@@ -147,12 +186,16 @@ void rd_rectifier_destroy(rd_rectifier *r) {
   ring_destroy(g);
   for (int k = 0; k < njobs; k++) if (r->d_out[k]) RD_HIP(hipFree(r->d_out[k]));
   for (int k = 0; k < njobs; k++) if (r->d_plane && r->d_plane[k]) RD_HIP(hipFree(r->d_plane[k]));
+  for (int k = 0; k < njobs; k++) if (r->d_labels && r->d_labels[k]) RD_HIP(hipFree(r->d_labels[k]));
+  for (int k = 0; k < njobs; k++) if (r->d_areas && r->d_areas[k]) RD_HIP(hipFree(r->d_areas[k]));
   if (r->d_dict) RD_HIP(hipFree(r->d_dict));
   RD_HIP(hipFree(r->d_quads));
   RD_HIP(hipHostFree(r->h_quads));
   r->frame.release();
   free(r->d_out);
   free(r->d_plane);
+  free(r->d_labels);
+  free(r->d_areas);
   free(r);
 }
 
@@ -167,7 +210,7 @@ long rd_rectifier_enqueue(rd_rectifier *r, int format, const void *const planes[
   if (n < 0 || n > g->per_job || (n > 0 && (!quads || !out))) return -1;
   RD_HIP(hipSetDevice(g->device));
   if (n > 0 && !is_kind(out, out_kind)) return -1;
-  if (n > 0 && (r->grade || r->code) && ((uintptr_t)out & 7)) return -1;      // (the records' 64-bit sums; rd_code::bits)
+  if (n > 0 && (r->grade || r->code || r->blob) && ((uintptr_t)out & 7)) return -1;      // (the records' 64-bit sums; rd_code::bits)
   const int slot = ring_claim(g, who, n);
   rdk::RectifyQuad *h_quads = r->h_quads + (size_t)slot * g->per_job, *d_quads = r->d_quads + (size_t)slot * g->per_job;
   for (int k = 0; k < n; k++) {
@@ -188,13 +231,22 @@ long rd_rectifier_enqueue(rd_rectifier *r, int format, const void *const planes[
       if (!r->d_out[slot]) RD_HIP(hipMalloc((void **)&r->d_out[slot], (size_t)g->per_job * r->patch_bytes));      // (on first use: a rectifier that writes to device memory only has none)
       dst = r->d_out[slot];
     }
-    if (r->scan || r->grade || r->code) {
+    if (r->scan || r->grade || r->code || r->blob) {
       const size_t plane_bytes = (size_t)g->per_job * r->pw * r->ph + (r->code ? RD_CODE_PLANE_PAD : 0);      // (rdk::code reads whole 16-byte words, and is told how far it may)
       if (!r->d_plane[slot]) RD_HIP(hipMalloc((void **)&r->d_plane[slot], plane_bytes));      // (on first use, like d_out)
       rdk::rectify_tensor(g->st, r->d_plane[slot], format, src, d_quads, n, r->pw, r->ph, r->spec);
-      rdrt::check_launch(r->scan ? "scanned pages: the G plane" : r->grade ? "graded quads: the G plane" : "decoded quads: the G plane");
+      rdrt::check_launch(r->scan ? "scanned pages: the G plane" : r->grade ? "graded quads: the G plane" : r->code ? "decoded quads: the G plane" : "page components: the G plane");
       if (r->scan) rdk::scan(g->st, dst, r->d_plane[slot], d_quads, n, r->pw, r->ph, r->sspec);
-      else if (r->code) rdk::code(g->st, dst, r->d_plane[slot], plane_bytes, d_quads, n, r->pw, r->ph, r->cspec, r->d_dict, r->ndict);
+      else if (r->blob) {
+        const size_t ints = (size_t)g->per_job * r->pw * r->ph;
+        if (!r->d_labels[slot]) RD_HIP(hipMalloc((void **)&r->d_labels[slot], ints * sizeof(int)));      // (on first use, like d_plane)
+        if (!r->d_areas[slot]) RD_HIP(hipMalloc((void **)&r->d_areas[slot], ints * sizeof(int)));
+        uint8_t *bits = (uint8_t *)r->d_areas[slot];      // (rd_k_blob.hip: the bits lie at the start of the area plane until the tile kernel has read them)
+        if (r->bspec.radius > 0) rdk::scan(g->st, bits, r->d_plane[slot], d_quads, n, r->pw, r->ph, r->sspec);
+        else rdk::blob_level(g->st, bits, r->d_plane[slot], d_quads, n, r->pw, r->ph, r->bspec);
+        rdrt::check_launch("page components: the ink bits");
+        rdk::blobs(g->st, dst, r->d_labels[slot], r->d_areas[slot], d_quads, n, r->pw, r->ph, r->bspec, NULL);
+      } else if (r->code) rdk::code(g->st, dst, r->d_plane[slot], plane_bytes, d_quads, n, r->pw, r->ph, r->cspec, r->d_dict, r->ndict);
       else {
         RD_HIP(hipMemsetAsync(dst, 0, (size_t)n * r->patch_bytes, g->st));      // the kernel ADDS to the records; an invalid quad's stay as they are here
         rdk::grade(g->st, dst, r->d_plane[slot], d_quads, n, r->pw, r->ph, r->gspec);
