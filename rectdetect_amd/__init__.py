@@ -19,6 +19,7 @@ Mirrors of the reference programs' call sequences:
   * :class:`Compositor` - the ``rd_compositor`` extension: a colour or an image written into the quads of a frame on the device
   * :class:`Matcher` - the ``rd_matcher`` extension: which template of a library is inside each quad, decided on the device
 """
+import collections
 import ctypes
 import os
 
@@ -771,6 +772,39 @@ class _Service:
             self.h = None
 
 
+# one output kind of the Rectifier: the spec's dtype, the C prefix of rd_<prefix>_spec_ok and rd_<prefix>_bytes, the constructor rd_rectifier_<ctor>, whether a job's
+# output is opaque rows of (n, patch_bytes) for the kind's *_view to take apart, and what one quad's output is called
+_Kind = collections.namedtuple("_Kind", "dtype prefix ctor rows what")
+_KINDS = {      # by the Rectifier's keyword
+    "tensor": _Kind(TENSOR_SPEC_DTYPE, "rd_tensor", "create_tensor", False, "tensor"),
+    "scan": _Kind(SCAN_SPEC_DTYPE, "rd_scan", "create_scan", False, "page"),
+    "grade": _Kind(GRADE_SPEC_DTYPE, "rd_grade", "create_grade", True, "records and histogram"),
+    "code": _Kind(CODE_SPEC_DTYPE, "rd_code", "create_code", True, "record (48)"),
+    "blobs": _Kind(BLOB_SPEC_DTYPE, "rd_blob", "create_blobs", True, "head, records and page"),
+}
+
+
+def _spec_of(kind, spec):
+    return np.ascontiguousarray(spec, dtype=_KINDS[kind].dtype).reshape(())
+
+
+def _spec_fns(kind):
+    """(<kind>_spec_ok, <kind>_bytes): the two questions every kind's spec answers without a GPU"""
+    k = _KINDS[kind]
+
+    def spec_ok(spec, pw, ph):
+        return bool(getattr(lib(), k.prefix + "_spec_ok")(_spec_of(kind, spec).ctypes.data, int(pw), int(ph)))
+
+    def nbytes(spec, pw, ph):
+        return int(getattr(lib(), k.prefix + "_bytes")(_spec_of(kind, spec).ctypes.data, int(pw), int(ph)))
+
+    noun = k.prefix[3:]
+    spec_ok.__name__, nbytes.__name__ = noun + "_spec_ok", noun + "_bytes"
+    spec_ok.__doc__ = "whether a %s spec is legal for pw x ph outputs (%s_spec_ok); runs without a GPU" % (noun, k.prefix)
+    nbytes.__doc__ = "the bytes of one quad's %s, 0 for a spec that is not legal (%s_bytes); runs without a GPU" % (k.what, k.prefix)
+    return spec_ok, nbytes
+
+
 def tensor_spec(dtype, layout, channels, oversample=1, scale=(1, 1, 1), bias=(0, 0, 0)):
     """an rd_tensor_spec as a TENSOR_SPEC_DTYPE record: dtype TENSOR_U8 / F16 / BF16 / F32, layout TENSOR_NHWC / NCHW, channels TENSOR_BGR / RGB / GRAY, oversample 1, 2
     or 4, scale and bias per OUTPUT channel (a number: the same for all).  Whether it is legal is decided where it is used (tensor_spec_ok, Rectifier)."""
@@ -780,24 +814,13 @@ def tensor_spec(dtype, layout, channels, oversample=1, scale=(1, 1, 1), bias=(0,
     return s
 
 
-def _spec_arg(spec):
-    return np.ascontiguousarray(spec, dtype=TENSOR_SPEC_DTYPE).reshape(())
-
-
-def tensor_spec_ok(spec, pw, ph):
-    """whether a spec is legal for pw x ph outputs (rd_tensor_spec_ok); runs without a GPU"""
-    return bool(lib().rd_tensor_spec_ok(_spec_arg(spec).ctypes.data, int(pw), int(ph)))
-
-
-def tensor_bytes(spec, pw, ph):
-    """the bytes of one quad's tensor, 0 for a spec that is not legal (rd_tensor_bytes); runs without a GPU"""
-    return int(lib().rd_tensor_bytes(_spec_arg(spec).ctypes.data, int(pw), int(ph)))
+tensor_spec_ok, tensor_bytes = _spec_fns("tensor")
 
 
 def tensor_element(spec, c, S):
     """the bytes of one element of channel c from its box sum S (rd_tensor_element: step 4 of the contract); runs without a GPU"""
     out = np.zeros(4, np.uint8)
-    n = lib().rd_tensor_element(_spec_arg(spec).ctypes.data, int(c), int(S), out.ctypes.data)
+    n = lib().rd_tensor_element(_spec_of("tensor", spec).ctypes.data, int(c), int(S), out.ctypes.data)
     if n <= 0:
         raise ValueError("rd_tensor_element: invalid arguments (spec %r, channel %r)" % (spec, c))
     return out[:n].tobytes()
@@ -820,25 +843,14 @@ def scan_spec(mode, radius=15, k=26, d=0, white=230, oversample=1, invert=False)
     return s
 
 
-def _scan_arg(spec):
-    return np.ascontiguousarray(spec, dtype=SCAN_SPEC_DTYPE).reshape(())
-
-
-def scan_spec_ok(spec, pw, ph):
-    """whether a scan spec is legal for pw x ph pages (rd_scan_spec_ok); runs without a GPU"""
-    return bool(lib().rd_scan_spec_ok(_scan_arg(spec).ctypes.data, int(pw), int(ph)))
-
-
-def scan_bytes(spec, pw, ph):
-    """the bytes of one quad's page, 0 for a spec that is not legal (rd_scan_bytes); runs without a GPU"""
-    return int(lib().rd_scan_bytes(_scan_arg(spec).ctypes.data, int(pw), int(ph)))
+scan_spec_ok, scan_bytes = _spec_fns("scan")
 
 
 def scan_pixel(spec, G0, N, T):
     """(ink, flat) of one pixel from its gray value G0, its window's pixel count N and the window's sum T of the (inverted) values (rd_scan_pixel: steps 3 and 4 of
     the contract); runs without a GPU"""
     out = np.zeros(2, np.uint8)
-    if not lib().rd_scan_pixel(_scan_arg(spec).ctypes.data, int(G0), int(N), int(T), out.ctypes.data, out.ctypes.data + 1):
+    if not lib().rd_scan_pixel(_spec_of("scan", spec).ctypes.data, int(G0), int(N), int(T), out.ctypes.data, out.ctypes.data + 1):
         raise ValueError("rd_scan_pixel: invalid arguments (spec %r, G0 %r, N %r, T %r)" % (spec, G0, N, T))
     return int(out[0]), int(out[1])
 
@@ -860,23 +872,12 @@ def grade_spec(cells=4, dark=8, bright=247, edge=64, oversample=1, hist=False):
     return s
 
 
-def _grade_arg(spec):
-    return np.ascontiguousarray(spec, dtype=GRADE_SPEC_DTYPE).reshape(())
-
-
-def grade_spec_ok(spec, pw, ph):
-    """whether a grade spec is legal for pw x ph patches (rd_grade_spec_ok); runs without a GPU"""
-    return bool(lib().rd_grade_spec_ok(_grade_arg(spec).ctypes.data, int(pw), int(ph)))
-
-
-def grade_bytes(spec, pw, ph):
-    """the bytes of one quad's records and histogram, 0 for a spec that is not legal (rd_grade_bytes); runs without a GPU"""
-    return int(lib().rd_grade_bytes(_grade_arg(spec).ctypes.data, int(pw), int(ph)))
+grade_spec_ok, grade_bytes = _spec_fns("grade")
 
 
 def grade_cell_of(spec, pw, ph, i, j):
     """the number of the record pixel (i, j) counts in, -1 for a spec that is not legal or a pixel outside the patch (rd_grade_cell_of); runs without a GPU"""
-    return int(lib().rd_grade_cell_of(_grade_arg(spec).ctypes.data, int(pw), int(ph), int(i), int(j)))
+    return int(lib().rd_grade_cell_of(_spec_of("grade", spec).ctypes.data, int(pw), int(ph), int(i), int(j)))
 
 
 def grade_limits():
@@ -921,29 +922,18 @@ def code_spec(n=6, border=1, inset=2, polarity=0, oversample=1, contrast=32, max
     return s
 
 
-def _code_arg(spec):
-    return np.ascontiguousarray(spec, dtype=CODE_SPEC_DTYPE).reshape(())
-
-
 def _dict_arg(dictionary):
     return np.zeros(0, np.uint64) if dictionary is None else np.ascontiguousarray(dictionary, dtype=np.uint64).reshape(-1)
 
 
-def code_spec_ok(spec, pw, ph):
-    """whether a code spec is legal for pw x ph patches (rd_code_spec_ok); runs without a GPU"""
-    return bool(lib().rd_code_spec_ok(_code_arg(spec).ctypes.data, int(pw), int(ph)))
-
-
-def code_bytes(spec, pw, ph):
-    """the bytes of one quad's record, 48, or 0 for a spec that is not legal (rd_code_bytes); runs without a GPU"""
-    return int(lib().rd_code_bytes(_code_arg(spec).ctypes.data, int(pw), int(ph)))
+code_spec_ok, code_bytes = _spec_fns("code")
 
 
 def code_cell_of(spec, pw, ph, i, j):
     """(the number of the cell pixel (i, j) lies in, whether it counts); (-1, False) for a spec that is not legal or a pixel outside the patch (rd_code_cell_of);
     runs without a GPU"""
     counted = ctypes.c_int(0)
-    cell = int(lib().rd_code_cell_of(_code_arg(spec).ctypes.data, int(pw), int(ph), int(i), int(j), ctypes.addressof(counted)))
+    cell = int(lib().rd_code_cell_of(_spec_of("code", spec).ctypes.data, int(pw), int(ph), int(i), int(j), ctypes.addressof(counted)))
     return cell, bool(counted.value)
 
 
@@ -982,7 +972,7 @@ def code_dictionary(n, count, min_dist, seed=0, tries=1 << 20):
 
 def code_render(spec, bits, cell_px=8):
     """the gray image of a code, a (C * cell_px, C * cell_px) uint8 array of 0 and 255 (rd_code_render); runs without a GPU"""
-    s = _code_arg(spec)
+    s = _spec_of("code", spec)
     side = (int(s["n"]) + 2 * int(s["border"])) * int(cell_px)
     out = np.zeros((max(side, 1), max(side, 1)), np.uint8)
     if not 1 <= side <= 12 * 64 or lib().rd_code_render(s.ctypes.data, int(bits), int(cell_px), out.ctypes.data) != side * side:
@@ -1013,18 +1003,7 @@ def blob_spec(radius=15, k=26, d=0, oversample=1, invert=False, connectivity=8, 
     return s
 
 
-def _blob_arg(spec):
-    return np.ascontiguousarray(spec, dtype=BLOB_SPEC_DTYPE).reshape(())
-
-
-def blob_spec_ok(spec, pw, ph):
-    """whether a blob spec is legal for pw x ph pages (rd_blob_spec_ok); runs without a GPU"""
-    return bool(lib().rd_blob_spec_ok(_blob_arg(spec).ctypes.data, int(pw), int(ph)))
-
-
-def blob_bytes(spec, pw, ph):
-    """the bytes of one quad's head, records and page, 0 for a spec that is not legal (rd_blob_bytes); runs without a GPU"""
-    return int(lib().rd_blob_bytes(_blob_arg(spec).ctypes.data, int(pw), int(ph)))
+blob_spec_ok, blob_bytes = _spec_fns("blobs")
 
 
 def blob_limits():
@@ -1047,7 +1026,7 @@ def _bit_pages(bits, pw, ph):
 
 def blob_page_host(bits, pw, ph, spec):
     """steps 2-7 of "page components" for one pw x ph page in the SCAN_BITS layout, on the host (rd_blob_page_host): its blob_bytes bytes; runs without a GPU"""
-    b, s = _bit_pages(bits, pw, ph), _blob_arg(spec)
+    b, s = _bit_pages(bits, pw, ph), _spec_of("blobs", spec)
     nb = blob_bytes(s, pw, ph)
     out = np.zeros(max(nb, 8) // 8, np.uint64)      # (8-byte aligned)
     if len(b) != 1 or not nb or not lib().rd_blob_page_host(b.ctypes.data, int(pw), int(ph), s.ctypes.data, out.ctypes.data):
@@ -1058,7 +1037,7 @@ def blob_page_host(bits, pw, ph, spec):
 def blob_view(arr, spec, pw, ph):
     """a blobs job's bytes (what Rectifier.rectify returns, or any (n, patch_bytes) uint8 array) as (the heads, a BLOB_HEAD_DTYPE array of n; the records, a BLOB_DTYPE
     array of shape (n, max_blobs) of which the first heads["written"] of a row count; the cleaned pages as an (n, ph, (pw + 7) // 8) uint8 array, or None without page)"""
-    s = _blob_arg(spec)
+    s = _spec_of("blobs", spec)
     B, rb = int(s["max_blobs"]), (int(pw) + 7) // 8
     nb = BLOB_HEAD_BYTES + BLOB_BYTES * B + (((rb * int(ph) + 7) & ~7) if int(s["page"]) else 0)
     a = np.ascontiguousarray(arr, dtype=np.uint8).reshape(-1, nb)
@@ -1073,7 +1052,7 @@ def blobs_pages(bits, pw, ph, spec, device=0, guard=0):
     """The component stage alone (rd_blobs_pages_device) on n pages of pw x ph pixels in the SCAN_BITS layout (any array of n * ph * ((pw + 7) // 8) bytes; pad bits are
     ignored): ((n, blob_bytes) uint8, info = {"path", "launches", "memsets", "tiles_x", "tiles_y", "border"}).  guard > 0: the output lies between two runs of that
     many bytes of 0xA5, which must come back untouched.  Needs a GPU."""
-    b, s = _bit_pages(bits, pw, ph), _blob_arg(spec)
+    b, s = _bit_pages(bits, pw, ph), _spec_of("blobs", spec)
     n, nb = len(b), blob_bytes(s, pw, ph)
     g = (int(guard) + 7) & ~7
     buf = np.full((n * nb + 2 * g + 7) // 8, 0xA5A5A5A5A5A5A5A5, np.uint64).view(np.uint8)      # (8-byte aligned, like a job's out)
@@ -1096,30 +1075,24 @@ class Rectifier(_Service):
     _name = "rectifier"
 
     def __init__(self, pw, ph, max_quads=64, njobs=2, device=0, tensor=None, scan=None, grade=None, code=None, dictionary=None, blobs=None):
-        if (tensor is not None) + (scan is not None) + (grade is not None) + (code is not None) + (blobs is not None) > 1:
+        given = {"tensor": tensor, "scan": scan, "grade": grade, "code": code, "blobs": blobs}
+        kinds = [k for k in _KINDS if given[k] is not None]
+        if len(kinds) > 1:
             raise ValueError("Rectifier: tensor=, scan=, grade=, code= and blobs= exclude each other")
         if dictionary is not None and code is None:
             raise ValueError("Rectifier: dictionary= goes with code=")
         self.pw, self.ph, self.max_quads, self.njobs = pw, ph, max_quads, njobs
-        self.tensor = None if tensor is None else _spec_arg(tensor).copy()
-        self.scan = None if scan is None else _scan_arg(scan).copy()
-        self.grade = None if grade is None else _grade_arg(grade).copy()
-        self.code = None if code is None else _code_arg(code).copy()
+        for k in _KINDS:      # self.tensor, self.scan, self.grade, self.code, self.blobs: the kind's spec, None for every other
+            setattr(self, k, None if given[k] is None else _spec_of(k, given[k]).copy())
         self.dictionary = None if code is None else _dict_arg(dictionary).copy()
-        self.blobs = None if blobs is None else _blob_arg(blobs).copy()
-        if self.blobs is not None:
-            self._create(device, pw, ph, max_quads, njobs, self.blobs.ctypes.data, ctor="create_blobs")
-        elif self.code is not None:
+        self._kind = _KINDS[kinds[0]] if kinds else None      # (None: BGR patches)
+        args, ctor = (device, pw, ph, max_quads, njobs), "create"
+        if kinds:
+            args, ctor = args + (getattr(self, kinds[0]).ctypes.data,), self._kind.ctor
+        if code is not None:
             d = self.dictionary
-            self._create(device, pw, ph, max_quads, njobs, self.code.ctypes.data, d.ctypes.data if len(d) else None, len(d), ctor="create_code")
-        elif self.grade is not None:
-            self._create(device, pw, ph, max_quads, njobs, self.grade.ctypes.data, ctor="create_grade")
-        elif self.scan is not None:
-            self._create(device, pw, ph, max_quads, njobs, self.scan.ctypes.data, ctor="create_scan")
-        elif self.tensor is None:
-            self._create(device, pw, ph, max_quads, njobs)
-        else:
-            self._create(device, pw, ph, max_quads, njobs, self.tensor.ctypes.data, ctor="create_tensor")
+            args += (d.ctypes.data if len(d) else None, len(d))
+        self._create(*args, ctor=ctor)
 
     @property
     def patch_bytes(self):
@@ -1133,7 +1106,7 @@ class Rectifier(_Service):
 
     def shape(self, n):
         """the shape of a job of n quads: (n, ph, pw, C) or, under TENSOR_NCHW, (n, C, ph, pw); scanned pages: (n, ph, pw) or, under SCAN_BITS, (n, ph, (pw + 7) // 8); graded and decoded quads and page components: (n, patch_bytes)"""
-        if self.grade is not None or self.code is not None or self.blobs is not None:
+        if self._kind is not None and self._kind.rows:
             return (n, self.patch_bytes)
         if self.scan is not None:
             return (n, self.ph, (self.pw + 7) // 8 if int(self.scan["mode"]) == SCAN_BITS else self.pw)

@@ -1,6 +1,11 @@
 // rectdetect-mi355x: the rectifier - rectified patches of quads behind the detector's poll (the contract: include/rectdetect_hip.h, "rectified patches";
-// the kernels: rd_k_rectify.hip and, for a rectifier made with a tensor spec, rd_k_tensor.hip ("model-ready tensors"); made with a scan spec, rd_k_tensor.hip into a
-// G plane of the rectifier's own and rd_k_scan.hip from there ("scanned pages"); made with a grade spec, the same G plane and rd_k_grade.hip ("graded quads"); made with a code spec and a dictionary, the same G plane and rd_k_code.hip ("decoded quads"); made with a blob spec, the same G plane, its ink bits by rd_k_scan.hip or rd_k_blob.hip's level kernel and rd_k_blob.hip's component stage ("page components"); the jobs in flight, the frame's checks and its way to the device: rd_jobs.h).
+// the jobs in flight, the frame's checks and its way to the device: rd_jobs.h).  A rectifier is of one kind, and the kind decides a job's launches:
+//   PATCHES  rd_k_rectify.hip;
+//   TENSOR   rd_k_tensor.hip under the job's own spec ("model-ready tensors");
+//   SCAN     rd_k_tensor.hip into a G plane of the rectifier's own, rd_k_scan.hip from there ("scanned pages");
+//   GRADE    the same G plane, the job's output zeroed, rd_k_grade.hip ("graded quads");
+//   CODE     the same G plane, rd_k_code.hip with the rectifier's dictionary ("decoded quads");
+//   BLOBS    the same G plane, its ink bits by rd_k_scan.hip or rd_k_blob.hip's level kernel, rd_k_blob.hip's component stage ("page components").
 #include "rd_jobs.h"
 #include "rd_kernels.h"
 #include "rd_code_tile.h"
@@ -10,28 +15,38 @@
 
 using namespace rdjob;
 
+enum Kind { PATCHES, TENSOR, SCAN, GRADE, CODE, BLOBS };      // which rd_rectifier_create* made it
+
+static bool has_records(Kind k) { return k == GRADE || k == CODE || k == BLOBS; }      // `out` is 8-byte aligned (the records' 64-bit sums; rd_code::bits)
+
+struct SlotScratch {                        // a job slot's scratch in device memory, every member allocated on first use (scratch())
+  uint8_t *out;                             // max_quads outputs on their way to pinned host memory (a rectifier that writes to device memory only has none)
+  uint8_t *plane;                           // the G planes of max_quads quads, pw * ph bytes each, RD_CODE_PLANE_PAD more for CODE (kinds with a G plane only)
+  int *labels, *areas;                      // the component stage's two int planes of max_quads quads, pw * ph ints each (BLOBS only)
+};
+
 struct rd_rectifier {
   Ring ring;                                // (first: rd_jobs.h)
+  Kind kind;
   int pw, ph;
   size_t patch_bytes;                       // of one quad's output: pw * ph * 3, or rd_tensor_bytes / rd_scan_bytes / rd_grade_bytes / rd_code_bytes / rd_blob_bytes of the spec
-  int tensor;                               // made by rd_rectifier_create_tensor: jobs launch rdk::rectify_tensor with `spec`
-  rd_tensor_spec spec;
-  int scan;                                 // made by rd_rectifier_create_scan: jobs launch rdk::rectify_tensor with `spec` ({ U8, NHWC, GRAY, m }) into d_plane, then rdk::scan with `sspec`
-  rd_scan_spec sspec;
-  int grade;                                // made by rd_rectifier_create_grade: the same G plane, then the stream zeroes the job's output and rdk::grade adds to it under `gspec`
-  rd_grade_spec gspec;
-  int code;                                 // made by rd_rectifier_create_code: the same G plane, then rdk::code writes a record per quad under `cspec` from the ndict codes at d_dict
-  rd_code_spec cspec;
+  rd_tensor_spec spec;                      // TENSOR: the job's own; kinds with a G plane: { U8, NHWC, GRAY, m }
+  rd_scan_spec sspec;                       // SCAN: the job's own; BLOBS: the ink decision of bspec as RD_SCAN_BITS (radius >= 1)
+  rd_grade_spec gspec;                      // GRADE
+  rd_code_spec cspec;                       // CODE: a record per quad from the ndict codes at d_dict
   uint64_t *d_dict;                         // (NULL when ndict is 0)
   int ndict;
-  int blob;                                 // made by rd_rectifier_create_blobs: the same G plane, then the ink bits - rdk::scan with `sspec` (RD_SCAN_BITS; radius >= 1) or rdk::blob_level - into the start of d_areas, then rdk::blobs under `bspec`
-  rd_blob_spec bspec;
-  int **d_labels, **d_areas;                // per slot: the component stage's two int planes of max_quads quads, pw * ph ints each (allocated on first use; blob rectifiers only)
-  uint8_t **d_plane;                        // per slot: the G planes of max_quads quads, pw * ph bytes each (allocated on first use; scan, grade, code and blob rectifiers only)
+  rd_blob_spec bspec;                       // BLOBS
   rdk::RectifyQuad *d_quads, *h_quads;      // njobs blocks of max_quads each, a job's at slot * max_quads: pinned staging and their place in the device array
-  uint8_t **d_out;                          // per slot: max_quads patches on their way to pinned host memory (allocated on first use)
+  SlotScratch *slots;                       // one per job slot
   DevBuf frame;                             // host and pinned frames travel through here
 };
+
+// a member of a slot's scratch: allocated on first use
+template <class T> static T *scratch(T **member, size_t bytes) {
+  if (!*member) RD_HIP(hipMalloc((void **)member, bytes));
+  return *member;
+}
 
 extern "C" {
 
@@ -75,85 +90,90 @@ void rd_rectify_coefficients(const double quad[8], double coef[8], int *status) 
   if (status) *status = 1;
 }
 
-// the G plane's spec: step 1 of "scanned pages" and of "graded quads" IS this tensor
-static void gray_plane(rd_rectifier *r, int njobs, int oversample) {
-  r->spec.dtype = RD_TENSOR_U8; r->spec.layout = RD_TENSOR_NHWC; r->spec.channels = RD_TENSOR_GRAY; r->spec.oversample = oversample;
-  r->d_plane = (uint8_t **)calloc(njobs, sizeof(uint8_t *));
-}
-
-// spec == NULL, sspec == NULL, gspec == NULL, cspec == NULL and bspec == NULL: the classic rectifier
-static rd_rectifier *rectifier_create(int device, int pw, int ph, int max_quads, int njobs, const rd_tensor_spec *spec, const rd_scan_spec *sspec = NULL, const rd_grade_spec *gspec = NULL,
-                                      const rd_code_spec *cspec = NULL, const uint64_t *dict = NULL, int ndict = 0, const rd_blob_spec *bspec = NULL) {
-  if (pw < 1 || ph < 1 || pw > 16384 || ph > 16384 || max_quads < 1 || max_quads > 65535 || !ring_args_ok(device, njobs)) return NULL;
-  if (spec && !rd_tensor_spec_ok(spec, pw, ph)) return NULL;
-  if (sspec && !rd_scan_spec_ok(sspec, pw, ph)) return NULL;
-  if (gspec && !rd_grade_spec_ok(gspec, pw, ph)) return NULL;
-  if (bspec && (!rd_blob_spec_ok(bspec, pw, ph) || (size_t)max_quads * pw * ph > RD_BLOB_MAX_SLOT_PIXELS)) return NULL;
-  if (cspec) {
-    if (!rd_code_spec_ok(cspec, pw, ph) || ndict < 0 || ndict > RD_CODE_MAX_DICT || (ndict > 0 && !dict)) return NULL;
-    const int bits = cspec->n * cspec->n;
-    for (int k = 0; k < ndict; k++) if (bits < 64 && (dict[k] >> bits)) return NULL;      // (a bit at or above n * n)
-  }
-  rd_rectifier *r = (rd_rectifier *)calloc(1, sizeof(*r));
-  ring_create(&r->ring, RD_MAGIC_RECTIFIER, device, max_quads, njobs);
-  r->pw = pw; r->ph = ph;
-  r->patch_bytes = spec ? rd_tensor_bytes(spec, pw, ph) : (size_t)pw * ph * 3;
-  if (spec) { r->tensor = 1; r->spec = *spec; }
-  if (sspec) {
-    r->scan = 1; r->sspec = *sspec;
-    r->patch_bytes = rd_scan_bytes(sspec, pw, ph);
-    gray_plane(r, njobs, sspec->oversample);
-  }
-  if (gspec) {
-    r->grade = 1; r->gspec = *gspec;
-    r->patch_bytes = rd_grade_bytes(gspec, pw, ph);
-    gray_plane(r, njobs, gspec->oversample);
-  }
-  if (cspec) {
-    r->code = 1; r->cspec = *cspec; r->ndict = ndict;
-    r->patch_bytes = rd_code_bytes(cspec, pw, ph);
-    gray_plane(r, njobs, cspec->oversample);
-    if (ndict > 0) {
-      RD_HIP(hipMalloc((void **)&r->d_dict, (size_t)ndict * sizeof(uint64_t)));
-      RD_HIP(hipMemcpy(r->d_dict, dict, (size_t)ndict * sizeof(uint64_t), hipMemcpyHostToDevice));
+// whether rd_rectifier_create* makes a rectifier of these: decided before anything is allocated
+static bool create_args_ok(int device, int pw, int ph, int max_quads, int njobs, Kind kind, const void *spec, const uint64_t *dict, int ndict) {
+  if (pw < 1 || ph < 1 || pw > 16384 || ph > 16384 || max_quads < 1 || max_quads > 65535 || !ring_args_ok(device, njobs)) return false;
+  if (kind != PATCHES && !spec) return false;
+  switch (kind) {
+    case PATCHES: return true;
+    case TENSOR: return rd_tensor_spec_ok((const rd_tensor_spec *)spec, pw, ph);
+    case SCAN: return rd_scan_spec_ok((const rd_scan_spec *)spec, pw, ph);
+    case GRADE: return rd_grade_spec_ok((const rd_grade_spec *)spec, pw, ph);
+    case BLOBS: return rd_blob_spec_ok((const rd_blob_spec *)spec, pw, ph) && (size_t)max_quads * pw * ph <= RD_BLOB_MAX_SLOT_PIXELS;
+    case CODE: {
+      const rd_code_spec *c = (const rd_code_spec *)spec;
+      if (!rd_code_spec_ok(c, pw, ph) || ndict < 0 || ndict > RD_CODE_MAX_DICT || (ndict > 0 && !dict)) return false;
+      const int bits = c->n * c->n;
+      for (int k = 0; k < ndict; k++) if (bits < 64 && (dict[k] >> bits)) return false;      // (a bit at or above n * n)
+      return true;
     }
   }
-  if (bspec) {
-    r->blob = 1; r->bspec = *bspec;
-    r->patch_bytes = rd_blob_bytes(bspec, pw, ph);
-    gray_plane(r, njobs, bspec->oversample);
-    const rd_scan_spec ink = { RD_SCAN_BITS, bspec->radius, bspec->k, bspec->d, 255, bspec->oversample, bspec->invert, 0 };      // (white: not read in this mode; radius 0 never reaches rdk::scan)
-    r->sspec = ink;
-    r->d_labels = (int **)calloc(njobs, sizeof(int *));
-    r->d_areas = (int **)calloc(njobs, sizeof(int *));
+  return false;
+}
+
+// the G plane's spec: step 1 of SCAN, GRADE, CODE and BLOBS IS this tensor
+static void gray_plane(rd_rectifier *r, int oversample) {
+  r->spec.dtype = RD_TENSOR_U8; r->spec.layout = RD_TENSOR_NHWC; r->spec.channels = RD_TENSOR_GRAY; r->spec.oversample = oversample;
+}
+
+// every kind's constructor: `spec` is the kind's own rd_*_spec (PATCHES: none), dict / ndict CODE's dictionary
+static rd_rectifier *rectifier_create(int device, int pw, int ph, int max_quads, int njobs, Kind kind, const void *spec, const uint64_t *dict, int ndict) {
+  if (!create_args_ok(device, pw, ph, max_quads, njobs, kind, spec, dict, ndict)) return NULL;
+  rd_rectifier *r = (rd_rectifier *)calloc(1, sizeof(*r));
+  ring_create(&r->ring, RD_MAGIC_RECTIFIER, device, max_quads, njobs);
+  r->kind = kind; r->pw = pw; r->ph = ph;
+  switch (kind) {
+    case PATCHES: r->patch_bytes = (size_t)pw * ph * 3; break;
+    case TENSOR: r->spec = *(const rd_tensor_spec *)spec; r->patch_bytes = rd_tensor_bytes(&r->spec, pw, ph); break;
+    case SCAN: r->sspec = *(const rd_scan_spec *)spec; r->patch_bytes = rd_scan_bytes(&r->sspec, pw, ph); gray_plane(r, r->sspec.oversample); break;
+    case GRADE: r->gspec = *(const rd_grade_spec *)spec; r->patch_bytes = rd_grade_bytes(&r->gspec, pw, ph); gray_plane(r, r->gspec.oversample); break;
+    case CODE:
+      r->cspec = *(const rd_code_spec *)spec; r->patch_bytes = rd_code_bytes(&r->cspec, pw, ph); gray_plane(r, r->cspec.oversample);
+      r->ndict = ndict;
+      if (ndict > 0) {
+        RD_HIP(hipMalloc((void **)&r->d_dict, (size_t)ndict * sizeof(uint64_t)));
+        RD_HIP(hipMemcpy(r->d_dict, dict, (size_t)ndict * sizeof(uint64_t), hipMemcpyHostToDevice));
+      }
+      break;
+    case BLOBS: {
+      r->bspec = *(const rd_blob_spec *)spec; r->patch_bytes = rd_blob_bytes(&r->bspec, pw, ph); gray_plane(r, r->bspec.oversample);
+      const rd_scan_spec ink = { RD_SCAN_BITS, r->bspec.radius, r->bspec.k, r->bspec.d, 255, r->bspec.oversample, r->bspec.invert, 0 };      // (white: not read in this mode; radius 0 never reaches rdk::scan)
+      r->sspec = ink;
+      break;
+    }
   }
   const size_t nq = (size_t)njobs * max_quads;
   RD_HIP(hipMalloc((void **)&r->d_quads, nq * sizeof(rdk::RectifyQuad)));
   RD_HIP(hipHostMalloc((void **)&r->h_quads, nq * sizeof(rdk::RectifyQuad), hipHostMallocDefault));
-  r->d_out = (uint8_t **)calloc(njobs, sizeof(uint8_t *));
+  r->slots = (SlotScratch *)calloc(njobs, sizeof(SlotScratch));
   return r;
 }
 
-rd_rectifier *rd_rectifier_create(int device, int pw, int ph, int max_quads, int njobs) { return rectifier_create(device, pw, ph, max_quads, njobs, NULL); }
+// the kinds without a dictionary
+static rd_rectifier *rectifier_create(int device, int pw, int ph, int max_quads, int njobs, Kind kind, const void *spec) {
+  return rectifier_create(device, pw, ph, max_quads, njobs, kind, spec, NULL, 0);
+}
+
+rd_rectifier *rd_rectifier_create(int device, int pw, int ph, int max_quads, int njobs) { return rectifier_create(device, pw, ph, max_quads, njobs, PATCHES, NULL); }
 
 rd_rectifier *rd_rectifier_create_tensor(int device, int pw, int ph, int max_quads, int njobs, const rd_tensor_spec *spec) {
-  return spec ? rectifier_create(device, pw, ph, max_quads, njobs, spec) : NULL;
+  return rectifier_create(device, pw, ph, max_quads, njobs, TENSOR, spec);
 }
 
 rd_rectifier *rd_rectifier_create_scan(int device, int pw, int ph, int max_quads, int njobs, const rd_scan_spec *spec) {
-  return spec ? rectifier_create(device, pw, ph, max_quads, njobs, NULL, spec) : NULL;
+  return rectifier_create(device, pw, ph, max_quads, njobs, SCAN, spec);
 }
 
 rd_rectifier *rd_rectifier_create_grade(int device, int pw, int ph, int max_quads, int njobs, const rd_grade_spec *spec) {
-  return spec ? rectifier_create(device, pw, ph, max_quads, njobs, NULL, NULL, spec) : NULL;
+  return rectifier_create(device, pw, ph, max_quads, njobs, GRADE, spec);
 }
 
 rd_rectifier *rd_rectifier_create_code(int device, int pw, int ph, int max_quads, int njobs, const rd_code_spec *spec, const uint64_t *dict, int ndict) {
-  return spec ? rectifier_create(device, pw, ph, max_quads, njobs, NULL, NULL, NULL, spec, dict, ndict) : NULL;
+  return rectifier_create(device, pw, ph, max_quads, njobs, CODE, spec, dict, ndict);
 }
 
 rd_rectifier *rd_rectifier_create_blobs(int device, int pw, int ph, int max_quads, int njobs, const rd_blob_spec *spec) {
-  return spec ? rectifier_create(device, pw, ph, max_quads, njobs, NULL, NULL, NULL, NULL, NULL, 0, spec) : NULL;
+  return rectifier_create(device, pw, ph, max_quads, njobs, BLOBS, spec);
 }
 
 int rd_blobs_pages_device(int device, const uint8_t *bits, int pw, int ph, int n, const rd_blob_spec *spec, void *out, int32_t info[8]) {
@@ -184,18 +204,15 @@ void rd_rectifier_destroy(rd_rectifier *r) {
   Ring *g = ring_of(r, RD_MAGIC_RECTIFIER, "rd_rectifier_destroy");
   const int njobs = g->njobs;
   ring_destroy(g);
-  for (int k = 0; k < njobs; k++) if (r->d_out[k]) RD_HIP(hipFree(r->d_out[k]));
-  for (int k = 0; k < njobs; k++) if (r->d_plane && r->d_plane[k]) RD_HIP(hipFree(r->d_plane[k]));
-  for (int k = 0; k < njobs; k++) if (r->d_labels && r->d_labels[k]) RD_HIP(hipFree(r->d_labels[k]));
-  for (int k = 0; k < njobs; k++) if (r->d_areas && r->d_areas[k]) RD_HIP(hipFree(r->d_areas[k]));
+  for (int k = 0; k < njobs; k++) {
+    void *const members[4] = { r->slots[k].out, r->slots[k].plane, r->slots[k].labels, r->slots[k].areas };
+    for (void *m : members) if (m) RD_HIP(hipFree(m));
+  }
   if (r->d_dict) RD_HIP(hipFree(r->d_dict));
   RD_HIP(hipFree(r->d_quads));
   RD_HIP(hipHostFree(r->h_quads));
   r->frame.release();
-  free(r->d_out);
-  free(r->d_plane);
-  free(r->d_labels);
-  free(r->d_areas);
+  free(r->slots);
   free(r);
 }
 
@@ -210,7 +227,7 @@ long rd_rectifier_enqueue(rd_rectifier *r, int format, const void *const planes[
   if (n < 0 || n > g->per_job || (n > 0 && (!quads || !out))) return -1;
   RD_HIP(hipSetDevice(g->device));
   if (n > 0 && !is_kind(out, out_kind)) return -1;
-  if (n > 0 && (r->grade || r->code || r->blob) && ((uintptr_t)out & 7)) return -1;      // (the records' 64-bit sums; rd_code::bits)
+  if (n > 0 && has_records(r->kind) && ((uintptr_t)out & 7)) return -1;
   const int slot = ring_claim(g, who, n);
   rdk::RectifyQuad *h_quads = r->h_quads + (size_t)slot * g->per_job, *d_quads = r->d_quads + (size_t)slot * g->per_job;
   for (int k = 0; k < n; k++) {
@@ -226,33 +243,51 @@ long rd_rectifier_enqueue(rd_rectifier *r, int format, const void *const planes[
       bring(g->st, who, L, src, planes, pitches, on_device);
     }
     RD_HIP(hipMemcpyAsync(d_quads, h_quads, (size_t)n * sizeof(rdk::RectifyQuad), hipMemcpyHostToDevice, g->st));
-    uint8_t *dst = (uint8_t *)out;
-    if (out_kind == RD_FRAME_HOST_PINNED) {
-      if (!r->d_out[slot]) RD_HIP(hipMalloc((void **)&r->d_out[slot], (size_t)g->per_job * r->patch_bytes));      // (on first use: a rectifier that writes to device memory only has none)
-      dst = r->d_out[slot];
-    }
-    if (r->scan || r->grade || r->code || r->blob) {
-      const size_t plane_bytes = (size_t)g->per_job * r->pw * r->ph + (r->code ? RD_CODE_PLANE_PAD : 0);      // (rdk::code reads whole 16-byte words, and is told how far it may)
-      if (!r->d_plane[slot]) RD_HIP(hipMalloc((void **)&r->d_plane[slot], plane_bytes));      // (on first use, like d_out)
-      rdk::rectify_tensor(g->st, r->d_plane[slot], format, src, d_quads, n, r->pw, r->ph, r->spec);
-      rdrt::check_launch(r->scan ? "scanned pages: the G plane" : r->grade ? "graded quads: the G plane" : r->code ? "decoded quads: the G plane" : "page components: the G plane");
-      if (r->scan) rdk::scan(g->st, dst, r->d_plane[slot], d_quads, n, r->pw, r->ph, r->sspec);
-      else if (r->blob) {
-        const size_t ints = (size_t)g->per_job * r->pw * r->ph;
-        if (!r->d_labels[slot]) RD_HIP(hipMalloc((void **)&r->d_labels[slot], ints * sizeof(int)));      // (on first use, like d_plane)
-        if (!r->d_areas[slot]) RD_HIP(hipMalloc((void **)&r->d_areas[slot], ints * sizeof(int)));
-        uint8_t *bits = (uint8_t *)r->d_areas[slot];      // (rd_k_blob.hip: the bits lie at the start of the area plane until the tile kernel has read them)
-        if (r->bspec.radius > 0) rdk::scan(g->st, bits, r->d_plane[slot], d_quads, n, r->pw, r->ph, r->sspec);
-        else rdk::blob_level(g->st, bits, r->d_plane[slot], d_quads, n, r->pw, r->ph, r->bspec);
-        rdrt::check_launch("page components: the ink bits");
-        rdk::blobs(g->st, dst, r->d_labels[slot], r->d_areas[slot], d_quads, n, r->pw, r->ph, r->bspec, NULL);
-      } else if (r->code) rdk::code(g->st, dst, r->d_plane[slot], plane_bytes, d_quads, n, r->pw, r->ph, r->cspec, r->d_dict, r->ndict);
-      else {
-        RD_HIP(hipMemsetAsync(dst, 0, (size_t)n * r->patch_bytes, g->st));      // the kernel ADDS to the records; an invalid quad's stay as they are here
-        rdk::grade(g->st, dst, r->d_plane[slot], d_quads, n, r->pw, r->ph, r->gspec);
+    SlotScratch *s = &r->slots[slot];
+    const int pw = r->pw, ph = r->ph;
+    const size_t npix = (size_t)g->per_job * pw * ph;
+    const size_t plane_bytes = npix + (r->kind == CODE ? RD_CODE_PLANE_PAD : 0);      // (rdk::code reads whole 16-byte words, and is told how far it may)
+    uint8_t *dst = out_kind == RD_FRAME_HOST_PINNED ? scratch(&s->out, (size_t)g->per_job * r->patch_bytes) : (uint8_t *)out;
+    auto g_plane = [&](const char *what) {      // step 1 of the kinds that have a G plane: the job's quads as { U8, NHWC, GRAY, m } tensors in the slot's own planes
+      uint8_t *plane = scratch(&s->plane, plane_bytes);
+      rdk::rectify_tensor(g->st, plane, format, src, d_quads, n, pw, ph, r->spec);
+      rdrt::check_launch(what);
+      return plane;
+    };
+    switch (r->kind) {
+      case PATCHES:
+        rdk::rectify(g->st, dst, format, src, d_quads, n, pw, ph);
+        break;
+      case TENSOR:
+        rdk::rectify_tensor(g->st, dst, format, src, d_quads, n, pw, ph, r->spec);
+        break;
+      case SCAN: {
+        const uint8_t *plane = g_plane("scanned pages: the G plane");
+        rdk::scan(g->st, dst, plane, d_quads, n, pw, ph, r->sspec);
+        break;
       }
-    } else if (r->tensor) rdk::rectify_tensor(g->st, dst, format, src, d_quads, n, r->pw, r->ph, r->spec);
-    else rdk::rectify(g->st, dst, format, src, d_quads, n, r->pw, r->ph);
+      case GRADE: {
+        const uint8_t *plane = g_plane("graded quads: the G plane");
+        RD_HIP(hipMemsetAsync(dst, 0, (size_t)n * r->patch_bytes, g->st));      // the kernel ADDS to the records; an invalid quad's stay as they are here
+        rdk::grade(g->st, dst, plane, d_quads, n, pw, ph, r->gspec);
+        break;
+      }
+      case CODE: {
+        const uint8_t *plane = g_plane("decoded quads: the G plane");
+        rdk::code(g->st, dst, plane, plane_bytes, d_quads, n, pw, ph, r->cspec, r->d_dict, r->ndict);
+        break;
+      }
+      case BLOBS: {
+        const uint8_t *plane = g_plane("page components: the G plane");
+        int *labels = scratch(&s->labels, npix * sizeof(int)), *areas = scratch(&s->areas, npix * sizeof(int));
+        uint8_t *bits = (uint8_t *)areas;      // (rd_k_blob.hip: the bits lie at the start of the area plane until the tile kernel has read them)
+        if (r->bspec.radius > 0) rdk::scan(g->st, bits, plane, d_quads, n, pw, ph, r->sspec);
+        else rdk::blob_level(g->st, bits, plane, d_quads, n, pw, ph, r->bspec);
+        rdrt::check_launch("page components: the ink bits");
+        rdk::blobs(g->st, dst, labels, areas, d_quads, n, pw, ph, r->bspec, NULL);
+        break;
+      }
+    }
     rdrt::check_launch("rectified patches");
     if (out_kind == RD_FRAME_HOST_PINNED) RD_HIP(hipMemcpyAsync(out, dst, (size_t)n * r->patch_bytes, hipMemcpyDeviceToHost, g->st));
   }

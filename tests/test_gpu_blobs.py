@@ -5,11 +5,8 @@ device / pinned output, radii 1, 8 and 63, oversampling 1, 2 and 4, both polarit
 empty and full jobs, argument errors, behind the poll of both detector kinds, into memory that torch allocated, and from the example program.  Every frame-path case
 also runs the RD_SCAN_BITS rectifier on the same job and compares the records with the restatement's steps 2-7 applied to THOSE bits, so that a failure names the
 launch at fault.  Every output lies between guard bytes that must not change.  No tolerance anywhere."""
-import ctypes
 import os
-import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -19,23 +16,15 @@ from rectdetect_amd import synth
 from tests import blobcases
 from tests import blobs
 from tests import helpers
-from tests import jobframes
 from tests import pixfmt
+from tests import rectjobs
 from tests import tensor
-from tests import test_gpu_scan as gs
-from tests.jobframes import L, cframe
+from tests.rectjobs import L, Out, STATUS, case, cframe, gray_planes, mem, run_job      # (mem: the fixture)
 
 pytestmark = pytest.mark.gpu
 TW, TH = blobcases.TW, blobcases.TH
 CASES = blobcases.cases()
-GUARD = 64
-
-
-@pytest.fixture
-def mem():
-    m = jobframes.Mem()
-    yield m
-    m.close()
+GUARD = rectjobs.GUARD
 
 
 def assert_rows(got, want, spec, pw, ph, what):
@@ -109,7 +98,7 @@ def bits_of_the_job(mem, fmt, planes, iw, ih, quads, pw, ph, spec):
     """the RD_SCAN_BITS rectifier on the same job: ((n, ph, rb) pages, status)"""
     srect = ra.Rectifier(pw, ph, max_quads=len(quads), njobs=1, scan=blobs.scan_spec(spec))
     try:
-        return gs.run_job(srect, mem, fmt, planes, iw, ih, quads)
+        return run_job(srect, mem, fmt, planes, iw, ih, quads)
     finally:
         srect.close()
 
@@ -124,13 +113,13 @@ def localise(got, status, bitpages, want, wstatus, spec, pw, ph, what):
 
 
 def reference(fmt, pw, ph, spec, sel=None, seed=0):
-    g, st = gs.gray_planes(fmt, pw, ph, int(spec["oversample"]), seed)
+    g, st = gray_planes(fmt, pw, ph, int(spec["oversample"]), seed)
     sel = list(range(len(st))) if sel is None else list(sel)
     return blobs.from_planes(g[sel], st[sel], spec), st[sel].copy()
 
 
 def check_specs(mem, fmt, pw, ph, specs, kinds=(("device", "device", 0),), seed=0):
-    iw, ih, planes, bgr, quads = gs.case(fmt, seed)
+    iw, ih, planes, bgr, quads = case(fmt, seed)
     for spec in specs:
         want, wstatus = reference(fmt, pw, ph, spec, seed=seed)
         bitpages = bits_of_the_job(mem, fmt, planes, iw, ih, quads, pw, ph, spec)[0] if int(spec["radius"]) else None
@@ -138,18 +127,18 @@ def check_specs(mem, fmt, pw, ph, specs, kinds=(("device", "device", 0),), seed=
         try:
             assert rect.patch_bytes == ra.blob_bytes(spec, pw, ph) == want.shape[1] and rect.dtype == np.uint8 and rect.shape(len(quads)) == want.shape
             for kind, out_kind, pad in kinds:
-                got, status = gs.run_job(rect, mem, fmt, planes, iw, ih, quads, kind, out_kind, pad)
+                got, status = run_job(rect, mem, fmt, planes, iw, ih, quads, kind, out_kind, pad)
                 localise(got, status, bitpages, want, wstatus, spec, pw, ph, "%s %s %dx%d %s frame, %s output, pad %d" % (ra.PIX_NAMES[fmt], blobs.name(spec), pw, ph, kind, out_kind, pad))
-                assert status.tolist() == gs.STATUS.tolist() and not got[1].any(), "an invalid quad gives zero bytes"
+                assert status.tolist() == STATUS.tolist() and not got[1].any(), "an invalid quad gives zero bytes"
         finally:
             rect.close()
 
 
 def test_shared_reference_is_the_restatement():
     spec = ra.blob_spec(2, 26, 0, 2, True, 4, 2, 0, 8, True)
-    iw, ih, planes, bgr, quads = gs.case(ra.PIX_BGR)
+    iw, ih, planes, bgr, quads = case(ra.PIX_BGR)
     a, b = reference(ra.PIX_BGR, 9, 5, spec), blobs.job(bgr, quads, 9, 5, spec)
-    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[1].tolist() == gs.STATUS.tolist() and a[0].shape == (4, ra.blob_bytes(spec, 9, 5))
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and a[1].tolist() == STATUS.tolist() and a[0].shape == (4, ra.blob_bytes(spec, 9, 5))
 
 
 @pytest.mark.parametrize("radius", (1, 8, 63))
@@ -187,7 +176,7 @@ def test_fixed_level_brings_the_catalogue_to_the_frame_path_unchanged(case, mem)
     assert st.tolist() == [1] and np.array_equal(g0.reshape(case.ph, case.pw) <= 100, case.mask), "the quad samples the frame pixel for pixel"
     rect = ra.Rectifier(case.pw, case.ph, max_quads=1, njobs=1, blobs=spec)
     try:
-        got, status = gs.run_job(rect, mem, ra.PIX_BGR, [frame], frame.shape[1], frame.shape[0], quad)
+        got, status = run_job(rect, mem, ra.PIX_BGR, [frame], frame.shape[1], frame.shape[0], quad)
     finally:
         rect.close()
     assert status.tolist() == [1]
@@ -208,7 +197,7 @@ def test_fixed_level_at_its_ends_and_inverted(mem):
         assert np.array_equal(ink, claim), (k, invert)
         rect = ra.Rectifier(pw, ph, max_quads=1, njobs=1, blobs=spec)
         try:
-            got, status = gs.run_job(rect, mem, ra.PIX_BGR, [frame], frame.shape[1], frame.shape[0], quad)
+            got, status = run_job(rect, mem, ra.PIX_BGR, [frame], frame.shape[1], frame.shape[0], quad)
         finally:
             rect.close()
         blobs.explain(got[0], blobs.page(ink, spec), spec, pw, ph, "k %d invert %d" % (k, invert))
@@ -231,7 +220,7 @@ def test_no_stale_scratch_in_two_rounds_on_one_slot(mem):
                 frame, quad = level_frame(m)
                 wide[:, q * (pw + 24):(q + 1) * (pw + 24)] = frame
                 quads.append(quad[0] + (q * (pw + 24), 0))
-            got, status = gs.run_job(rect, mem, ra.PIX_BGR, [wide], wide.shape[1], wide.shape[0], np.array(quads))
+            got, status = run_job(rect, mem, ra.PIX_BGR, [wide], wide.shape[1], wide.shape[0], np.array(quads))
             assert status.tolist() == [1] * 4
             assert_rows(got, np.stack([blobs.page(m, spec) for m in masks]), spec, pw, ph, "round %d" % rnd)
     finally:
@@ -247,10 +236,10 @@ def test_four_jobs_in_flight_on_four_frames(mem):
         for rnd in range(2):      # (the second round reuses every slot's planes)
             pending = []
             for k in range(njobs):
-                iw, ih, planes, bgr, quads = gs.case(ra.PIX_BGR, seed=k)
+                iw, ih, planes, bgr, quads = case(ra.PIX_BGR, seed=k)
                 sel = list(range(4))[k % 2:4 - k // 2] if rnd else list(range(4))
                 args, pitches, kw = mem.place("device", planes, 5)
-                out = gs.Out(mem, "device" if k % 2 == 0 else "pinned", len(sel) * rect.patch_bytes)
+                out = Out(mem, "device" if k % 2 == 0 else "pinned", len(sel) * rect.patch_bytes)
                 assert rect.enqueue(ra.PIX_BGR, args, pitches, iw, ih, quads[sel], out.ptr, out_pinned=k % 2 == 1, **kw) == rnd * njobs + k
                 pending.append((k, sel, out))
             for k, sel, out in pending:
@@ -264,22 +253,22 @@ def test_four_jobs_in_flight_on_four_frames(mem):
 
 
 def test_empty_job_and_full_job(mem):
-    iw, ih, planes, bgr, quads = gs.case(ra.PIX_RGBA)
+    iw, ih, planes, bgr, quads = case(ra.PIX_RGBA)
     pw, ph = 9, 5
     spec = ra.blob_spec(2, 26, 0, 4, False, 4, 1, 0, 8, True)
     want, wstatus = reference(ra.PIX_RGBA, pw, ph, spec)
     nmax = 2 * len(quads)
     rect = ra.Rectifier(pw, ph, max_quads=nmax, njobs=2, blobs=spec)
     try:
-        got, status = gs.run_job(rect, mem, ra.PIX_RGBA, planes, iw, ih, np.zeros((0, 4, 2)))      # n = 0: nothing written, nothing returned
+        got, status = run_job(rect, mem, ra.PIX_RGBA, planes, iw, ih, np.zeros((0, 4, 2)))      # n = 0: nothing written, nothing returned
         assert got.shape == (0, rect.patch_bytes) and len(status) == 0
         assert rect.enqueue(ra.PIX_RGBA, planes, None, iw, ih, np.zeros((0, 8)), None) == 1      # (no output buffer needed either)
         assert len(rect.wait()) == 0
         full = np.concatenate([quads, quads[::-1]])
-        got, status = gs.run_job(rect, mem, ra.PIX_RGBA, planes, iw, ih, full, "host", "pinned")      # n = max_quads
+        got, status = run_job(rect, mem, ra.PIX_RGBA, planes, iw, ih, full, "host", "pinned")      # n = max_quads
         localise(got, status, None, np.concatenate([want, want[::-1]]), np.concatenate([wstatus, wstatus[::-1]]), spec, pw, ph, "full job")
         with pytest.raises(ValueError):
-            gs.run_job(rect, mem, ra.PIX_RGBA, planes, iw, ih, np.concatenate([full, quads[:1]]))      # one more
+            run_job(rect, mem, ra.PIX_RGBA, planes, iw, ih, np.concatenate([full, quads[:1]]))      # one more
         conv = rect.rectify(bgr, quads)      # the convenience call
         assert_rows(conv, want, spec, pw, ph, "rectify()")
         heads, recs, pages = ra.blob_view(conv, spec, pw, ph)
@@ -290,7 +279,7 @@ def test_empty_job_and_full_job(mem):
 
 
 def test_argument_errors_return_minus_one_or_null_and_the_next_job_is_correct(mem):
-    iw, ih, planes, bgr, quads = gs.case(ra.PIX_BGR)
+    iw, ih, planes, bgr, quads = case(ra.PIX_BGR)
     pw, ph = TW + 1, 9
     spec = ra.blob_spec(8, 26, 0, 2, False, 8, 2, 100, 16, True)
     want, wstatus = reference(ra.PIX_BGR, pw, ph, spec)
@@ -315,24 +304,10 @@ def test_argument_errors_return_minus_one_or_null_and_the_next_job_is_correct(me
     assert h
     L().rd_rectifier_destroy(h)
     rect = ra.Rectifier(pw, ph, max_quads=len(quads), njobs=1, blobs=spec)
-    (dframe,), (pitch,), _ = mem.place("device", planes, 3)
-    out = gs.Out(mem, "device", len(quads) * rect.patch_bytes + 8)
-    pageable = np.zeros(len(quads) * rect.patch_bytes, np.uint8)
-    q = np.ascontiguousarray(quads).reshape(-1, 8)
-    P, I = ctypes.c_void_p * 3, ctypes.c_int * 3
-
-    def call(fmt=ra.PIX_BGR, pl=(dframe, None, None), pi=(pitch, 0, 0), w=iw, h=ih, kind=1, quads_p=q.ctypes.data, n=len(q), out_p=out.ptr, out_kind=1):
-        return L().rd_rectifier_enqueue(rect.h, fmt, P(*pl), I(*pi), w, h, kind, quads_p, n, out_p, out_kind)
-
-    errors = {"unknown format": dict(fmt=6), "NULL plane": dict(pl=(None, None, None)), "short pitch": dict(pi=(iw * 3 - 1, 0, 0)), "n < 0": dict(n=-1), "n > max_quads": dict(n=len(q) + 1),
-              "pageable out": dict(out_p=pageable.ctypes.data, out_kind=2), "unknown out_kind": dict(out_kind=0), "unknown on_device": dict(kind=3), "no size": dict(w=0),
-              "NULL quads": dict(quads_p=None), "NULL out": dict(out_p=None), "out misaligned by 4": dict(out_p=out.ptr + 4)}
+    out = Out(mem, "device", len(quads) * rect.patch_bytes + 8)
     try:
         assert out.ptr % 8 == 0
-        for name, kw in errors.items():
-            assert call(**kw) == -1, name
-            assert L().rd_rectifier_wait(rect.h, None) == -1, name + ": nothing may have been enqueued"
-        assert call() == 0      # the first job after all of them: sequence number 0, the right bytes
+        q = rectjobs.refused_enqueues(mem, rect, planes, iw, ih, quads, out, {"out misaligned by 4": dict(out_p=out.ptr + 4)})
         status = rect.wait()
         localise(out.fetch(len(q) * rect.patch_bytes).reshape(rect.shape(len(q))), status, None, want, wstatus, spec, pw, ph, "the job after the refused ones")
     finally:
@@ -340,50 +315,17 @@ def test_argument_errors_return_minus_one_or_null_and_the_next_job_is_correct(me
 
 
 # ---------------------------------------------------------------------------------------------- behind the detector's poll
-PW, PH = 100, 60
+PW, PH = rectjobs.PW, rectjobs.PH
 POLL_SPEC = ra.blob_spec(15, 26, 0, 2, False, 8, 3, 0, 128, True)
-TAN36 = gs.TAN36
 
 
 @pytest.mark.parametrize("kind", ["rect-host", "poly-device", "scaled"])
 def test_rectify_polled_behind_every_poll(kind, mem):
     """after Detector.poll and PolylineDetector.poll, on host frames and device frames, and on a frame that came in at scale 2 - quads in detector coordinates, the
     page from the full-size source (X = 2x + 0.5)"""
-    poly, scaled, device = kind.startswith("poly"), kind == "scaled", kind.endswith("device")
-    fmt = ra.PIX_NV12 if device else ra.PIX_BGR
-    scale = 2 if scaled else 1
-    dw, dh = gs.SIW // scale, gs.SIH // scale
-    det = ra.PolylineDetector(dw, dh, nslots=2) if poly else ra.Detector(dw, dh, nslots=2, aperture=TAN36)
-    rect = ra.Rectifier(PW, PH, max_quads=8, njobs=2, blobs=POLL_SPEC)
-    srect = ra.Rectifier(PW, PH, max_quads=8, njobs=2, scan=blobs.scan_spec(POLL_SPEC))
-    total = 0
-    try:
-        out, sout = gs.Out(mem, "device", 8 * rect.patch_bytes), gs.Out(mem, "device", 8 * srect.patch_bytes)
-        with pytest.raises(ValueError):      # nothing polled yet
-            det.rectify_polled(rect, gs.FIXED_QUAD, out.ptr)
-        for t, (planes, bgr) in enumerate(gs.stream_frames(fmt)[:2]):
-            if scaled:
-                det.enqueue_scaled(fmt, planes)
-            elif device:
-                args, pitches, kw = mem.place("device", planes, 8)
-                det.enqueue_planes(fmt, args, pitches, **kw)
-            else:
-                det.enqueue_planes(fmt, planes)
-            res = det.poll()[0] if poly else det.poll(TAN36)
-            quads = gs.FIXED_QUAD / scale if poly or len(res) == 0 else np.concatenate([ra.rect_quads(res)[:3], gs.FIXED_QUAD / scale])
-            assert det.rectify_polled(rect, quads, out.ptr) == t and det.rectify_polled(srect, quads, sout.ptr) == t
-            status, sstatus = rect.wait(), srect.wait()
-            got = out.fetch(len(quads) * rect.patch_bytes).reshape(rect.shape(len(quads)))
-            bitpages = sout.fetch(len(quads) * srect.patch_bytes).reshape(srect.shape(len(quads)))
-            want, wstatus = blobs.job(bgr, quads * 2.0 + 0.5 if scaled else quads, PW, PH, POLL_SPEC)
-            assert sstatus.tolist() == wstatus.tolist()
-            localise(got, status, bitpages, want, wstatus, POLL_SPEC, PW, PH, "%s frame %d" % (kind, t))
-            total += len(quads)
-        assert total > 2 or not kind.startswith("rect"), "the stream's frames hold rectangles"
-    finally:
-        rect.close()
-        srect.close()
-        det.close()
+    rectjobs.polled_behind_a_poll(mem, kind, dict(blobs=POLL_SPEC), lambda bgr, quads: blobs.job(bgr, quads, PW, PH, POLL_SPEC),
+                                  lambda got, status, bitpages, want, wstatus, what: localise(got, status, bitpages, want, wstatus, POLL_SPEC, PW, PH, what), beside=dict(scan=blobs.scan_spec(POLL_SPEC)),
+                                  nframes=2)
 
 
 # ---------------------------------------------------------------------------------------------- memory that torch allocated
@@ -405,8 +347,8 @@ torch.cuda.synchronize()      # the caller's own streams are done with the memor
 rect.enqueue(ra.PIX_BGR, (dframe,), (iw * 3,), iw, ih, quads, t.data_ptr(), on_device=True)
 status = rect.wait()          # after which the data is visible to every stream
 np.save(sys.argv[2] + "blobs.npy", t.cpu().numpy())
-np.save(sys.argv[2] + "status.npy", status)
-print("sum", int(t.sum().item()), flush=True)      # a torch op on the tensor afterwards
+np.save(sys.argv[2] + "blobs_status.npy", status)
+print("blobs sum", int(t.sum().item()), flush=True)      # a torch op on the tensor afterwards
 rect.close()
 ra.lib().rd_device_free(dframe)
 print("done", flush=True)
@@ -416,17 +358,13 @@ print("done", flush=True)
 def test_torch_tensors_are_written_through_data_ptr(tmp_path):
     """a torch.uint8 tensor allocated by torch on the device and written through data_ptr(), read back with t.cpu(): the restatement's bytes.  In a child process,
     because what is tested is a process that imports torch first and so holds one HIP runtime."""
-    pytest.importorskip("torch")
-    iw, ih, planes, bgr, quads = gs.case(ra.PIX_BGR)
+    iw, ih, planes, bgr, quads = case(ra.PIX_BGR)
     pw, ph = TW + 1, TH + 2
-    np.savez(tmp_path / "in.npz", frame=bgr, quads=quads, pw=pw, ph=ph)
-    r = subprocess.run([sys.executable, "-c", TORCH_CHILD, str(tmp_path / "in.npz"), str(tmp_path) + os.sep], cwd=helpers.ROOT, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "done" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
+    got, status, total = rectjobs.torch_child(tmp_path, TORCH_CHILD, ["blobs"], frame=bgr, quads=quads, pw=pw, ph=ph)["blobs"]
     spec = ra.blob_spec(8, 26, 0, 2, False, 8, 2, 0, 32, True)
     want, wstatus = reference(ra.PIX_BGR, pw, ph, spec)
-    got, status = np.load(tmp_path / "blobs.npy"), np.load(tmp_path / "status.npy")
     localise(got, status, None, want, wstatus, spec, pw, ph, "torch")
-    assert int(re.search(r"sum (\d+)", r.stdout).group(1)) == int(want.astype(np.int64).sum()), "torch summed the bytes the job wrote"
+    assert int(total) == int(want.astype(np.int64).sum()), "torch summed the bytes the job wrote"
 
 
 # ---------------------------------------------------------------------------------------------- the example program

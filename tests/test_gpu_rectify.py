@@ -15,20 +15,13 @@ from tests import jobframes
 from tests import pixfmt
 from tests import rectify
 from tests.jobframes import L, cframe
+from tests.rectjobs import TAN36, mem, noise_frame, stream_frames      # (mem: the fixture)
 
 pytestmark = pytest.mark.gpu
-TAN36 = float(np.tan(36.0 / 180.0 * np.pi))
 
 
 def golden(name):
     return np.load(os.path.join(helpers.GOLDEN, name + ".npz"), allow_pickle=False)
-
-
-@pytest.fixture
-def mem():
-    m = jobframes.Mem()
-    yield m
-    m.close()
 
 
 def run_job(rect, mem, fmt, planes, iw, ih, quads, kind="host", out_kind="device", pad=0):
@@ -47,10 +40,6 @@ def assert_patches(got, status, want, wstatus, what=""):
     assert got.shape == want.shape
     bad = [k for k in range(len(want)) if not np.array_equal(got[k], want[k])]
     assert not bad, "%s: patches %r differ (patch %d in %d bytes)" % (what, bad[:10], bad[0], int((got[bad[0]] != want[bad[0]]).sum()))
-
-
-def noise_frame(iw, ih, seed=5):
-    return np.random.default_rng(seed).integers(0, 256, (ih, iw, 3), dtype=np.uint8)
 
 
 # ---------------------------------------------------------------------------------------------- anchor: no restatement involved
@@ -331,12 +320,6 @@ SIW, SIH, SN = 640, 480, 12
 FIXED_QUAD = np.array([[(101.5, 80.25), (420.0, 60.0), (500.5, 400.0), (60.0, 330.5)]])
 
 
-@lru_cache(maxsize=None)
-def stream_frames(fmt):
-    """[(planes, the contract's BGR frame)] of SN frames of the synthetic stream in format fmt"""
-    return tuple(pixfmt.convert(cframe(synth.SEED0, SIW, SIH, t), fmt) for t in range(SN))
-
-
 def drive(nslots, n, enqueue, poll):
     out, inflight = [], 0
     for i in range(n):
@@ -354,7 +337,7 @@ def drive(nslots, n, enqueue, poll):
 def stream_run(poly, nslots, fmt, kind, mem, rectifier=None):
     """the stream through a detector, the slots kept full; with a rectifier: after each poll the frame's own rectangles (polyline kind: FIXED_QUAD) are rectified
     from the polled slot and the job is waited for before anything else is enqueued.  [(result of the poll, quads, patches, status)]"""
-    items = stream_frames(fmt)
+    items = stream_frames(fmt, SN)      # [(planes, the contract's BGR frame)]
     det = ra.PolylineDetector(SIW, SIH, nslots=nslots) if poly else ra.Detector(SIW, SIH, nslots=nslots, aperture=TAN36)
     placed = [mem.place(kind, planes, 8) for planes, _ in items] if kind != "host" else None
     out = mem.out("device", 64 * PW * PH * 3) if rectifier else None
@@ -387,7 +370,7 @@ def stream_run(poly, nslots, fmt, kind, mem, rectifier=None):
 @pytest.mark.parametrize("poly,nslots", [(False, 1), (False, 2), (False, 64), (True, 8)], ids=["rect-1", "rect-2", "rect-64", "poly-8"])
 @pytest.mark.parametrize("fmt,kind", [(ra.PIX_BGR, "host"), (ra.PIX_NV12, "device")], ids=["bgr-host", "nv12-device"])
 def test_rectify_polled_behind_every_poll(poly, nslots, fmt, kind, mem):
-    items = stream_frames(fmt)
+    items = stream_frames(fmt, SN)      # [(planes, the contract's BGR frame)]
     plain = stream_run(poly, nslots, fmt, kind, mem)
     rectifier = ra.Rectifier(PW, PH, max_quads=64, njobs=2)
     alone = ra.Rectifier(PW, PH, max_quads=64, njobs=1)

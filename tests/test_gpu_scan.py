@@ -5,10 +5,8 @@ frames, device / pinned output, a misaligned output, a constant and a two-level 
 the poll of both detector kinds, into memory that torch allocated, and from the example program.  Every case also runs the { U8, NHWC, GRAY, m } tensor rectifier on
 the same job and compares the pages with the restatement's steps 2-5 applied to THAT plane, so that a failure names the launch at fault.  Every device output lies
 between guard bytes that must not change.  No tolerance anywhere."""
-import ctypes
 import os
 import subprocess
-from functools import lru_cache
 
 import numpy as np
 import pytest
@@ -16,67 +14,19 @@ import pytest
 import rectdetect_amd as ra
 from rectdetect_amd import synth
 from tests import helpers
-from tests import jobframes
 from tests import pixfmt
-from tests import rectify
+from tests import rectjobs
 from tests import scan
 from tests import tensor
-from tests.jobframes import L, cframe
+from tests.rectjobs import L, Out, STATUS, case, cframe, gray_job, gray_planes, job_quads, mem, run_job      # (mem: the fixture)
 
 pytestmark = pytest.mark.gpu
-TAN36 = float(np.tan(36.0 / 180.0 * np.pi))
-GUARD = 64
 TW, TH = ra.scan_limits()["tile_w"], ra.scan_limits()["tile_h"]
 # the pad bits alone; a tail byte; whole bytes; one bit into the next byte with rows that start misaligned; one short of the 64-pixel word, the word, one more;
 # the tile, one pixel into the next tile in both directions, and three tile columns with a tail, one row short of the tile
 SIZES = ((1, 1), (7, 3), (8, 8), (9, 5), (63, 2), (64, 1), (65, 2), (TW, TH), (TW + 1, TH + 1), (2 * TW + 3, TH - 1))
 RADII = (1, 2, 8, 63)
 KD = ((0, 0), (26, 0), (38, 7), (255, 255))
-
-
-@pytest.fixture
-def mem():
-    m = jobframes.Mem()
-    yield m
-    m.close()
-
-
-def noise_frame(iw, ih, seed=5):
-    return np.random.default_rng(seed).integers(0, 256, (ih, iw, 3), dtype=np.uint8)
-
-
-def job_quads(iw, ih):
-    """an axis-aligned quad, a non-convex (invalid) one BETWEEN valid ones, a rotated quad in perspective, a quad that reaches outside the frame on two sides"""
-    w, h = float(iw), float(ih)
-    return np.array([
-        [(10.5, 8.5), (74.5, 8.5), (74.5, 40.5), (10.5, 40.5)],
-        [(0.0, 0.0), (60.0, 0.0), (20.0, 20.0), (0.0, 50.0)],
-        [(30.25, 6.5), (88.75, 14.0), (80.0, 55.5), (12.5, 41.0)],
-        [(w - 40.0, h - 30.0), (w + 12.5, h - 36.0), (w + 7.0, h + 9.0), (w - 48.0, h + 4.25)],
-    ], np.float64)
-
-
-STATUS = np.array([1, 0, 1, 1], np.uint8)
-
-
-@lru_cache(maxsize=None)
-def case(fmt, seed=0):
-    """(iw, ih, planes, the contract's BGR frame, quads): 97 x 61 for the packed formats, 96 x 60 for 4:2:0"""
-    iw, ih = (97, 61) if fmt <= ra.PIX_RGBA else (96, 60)
-    planes, bgr = pixfmt.convert(noise_frame(iw, ih, 21 + fmt + 100 * seed), fmt)
-    assert np.array_equal(rectify.contract_bgr(fmt, planes), bgr)
-    return iw, ih, planes, bgr, job_quads(iw, ih)
-
-
-@lru_cache(maxsize=None)
-def gray_planes(fmt, pw, ph, m, seed=0):
-    """step 1 restated, computed once and shared (read only): ((n, ph, pw) uint8 G0 planes of the case's quads, status)"""
-    iw, ih, planes, bgr, quads = case(fmt, seed)
-    g, st = tensor.tensors(bgr, quads, pw, ph, ra.tensor_spec(ra.TENSOR_U8, ra.TENSOR_NHWC, ra.TENSOR_GRAY, m))
-    g = g.reshape(len(quads), ph, pw)
-    g.setflags(write=False)
-    st.setflags(write=False)
-    return g, st
 
 
 def reference(fmt, pw, ph, spec, sel=None, seed=0):
@@ -94,48 +44,6 @@ def test_shared_reference_is_the_restatement():
     assert a[1].tolist() == STATUS.tolist() and a[0].shape == (4, 5, 2)
 
 
-class Out:
-    """an output of nbytes in device memory between guards (0xA5, like the output itself before its job), `offset` bytes off its aligned start; or in pinned memory"""
-
-    def __init__(self, mem, kind, nbytes, offset=0):
-        self.mem, self.kind, self.nbytes, self.offset = mem, kind, nbytes, offset
-        if kind == "device":
-            self.total = GUARD + offset + nbytes + GUARD
-            self.base = L().rd_device_alloc(self.total)
-            mem.dev.append(self.base)
-            fill = np.full(self.total, 0xA5, np.uint8)
-            L().rd_upload(self.base, fill.ctypes.data, self.total)
-            self.ptr = self.base + GUARD + offset
-        else:
-            assert offset == 0
-            self.ptr = mem.out("pinned", nbytes)
-
-    def fetch(self, nbytes=None):
-        """the first nbytes the job wrote; everything around them must be 0xA5 still"""
-        nbytes = self.nbytes if nbytes is None else nbytes
-        if self.kind != "device":
-            a = self.mem.fetch("pinned", self.ptr, self.nbytes)
-            assert (a[nbytes:] == 0xA5).all(), "bytes behind the job's last byte were written"
-            return a[:nbytes]
-        a = np.zeros(self.total, np.uint8)
-        L().rd_download(a.ctypes.data, self.base, self.total)
-        lo = GUARD + self.offset
-        assert (a[:lo] == 0xA5).all(), "bytes before `out` were written"
-        assert (a[lo + nbytes:] == 0xA5).all(), "bytes behind the job's last byte were written"
-        return a[lo:lo + nbytes].copy()
-
-
-def run_job(rect, mem, fmt, planes, iw, ih, quads, kind="device", out_kind="device", pad=0, offset=0):
-    """one job, waited for: (the array of rect.shape(n) and rect.dtype, status)"""
-    q = np.asarray(quads, np.float64).reshape(-1, 8)
-    nbytes = len(q) * rect.patch_bytes
-    args, pitches, kw = mem.place(kind, planes, pad)
-    out = Out(mem, out_kind, nbytes, offset)
-    rect.enqueue(fmt, args, pitches, iw, ih, q, out.ptr, out_pinned=out_kind == "pinned", **kw)
-    status = rect.wait()
-    return out.fetch().view(rect.dtype).reshape(rect.shape(len(q))), status
-
-
 def localise(got, status, gpu_plane, want, wstatus, spec, what):
     """(a) the pages against steps 2-5 of the restatement on the plane the GPU's first launch made - a difference here is the scan kernel's -, (b) against the full
     restatement - a difference here alone is the tensor kernel's"""
@@ -147,12 +55,7 @@ def check_specs(mem, fmt, pw, ph, specs, kinds=(("device", "device", 0),), offse
     """every spec (all of one oversampling) on the case's job, with the tensor rectifier's plane of the same job"""
     iw, ih, planes, bgr, quads = case(fmt, seed)
     m = int(specs[0]["oversample"])
-    trect = ra.Rectifier(pw, ph, max_quads=len(quads), njobs=1, tensor=ra.tensor_spec(ra.TENSOR_U8, ra.TENSOR_NHWC, ra.TENSOR_GRAY, m))
-    try:
-        plane, pstatus = run_job(trect, mem, fmt, planes, iw, ih, quads)
-    finally:
-        trect.close()
-    plane = plane.reshape(len(quads), ph, pw)
+    plane, pstatus = gray_job(mem, fmt, planes, iw, ih, quads, pw, ph, m)
     assert pstatus.tolist() == STATUS.tolist()
     for spec in specs:
         assert int(spec["oversample"]) == m
@@ -320,23 +223,9 @@ def test_argument_errors_return_minus_one_and_the_next_job_is_correct(mem):
     for args in ((0, 0, ph, 4, 1), (0, pw, 0, 4, 1), (0, 8193, ph, 4, 1), (0, pw, 8193, 4, 1), (0, pw, ph, 0, 1), (0, pw, ph, 4, 0), (99, pw, ph, 4, 1)):
         assert not create(*args, spec.ctypes.data), args      # rd_rectifier_create's bad arguments (pw * m > 16384 among them)
     rect = ra.Rectifier(pw, ph, max_quads=len(quads), njobs=1, scan=spec)
-    (dframe,), (pitch,), _ = mem.place("device", planes, 3)
     out = Out(mem, "device", len(quads) * rect.patch_bytes)
-    pageable = np.zeros(len(quads) * rect.patch_bytes, np.uint8)
-    q = np.ascontiguousarray(quads).reshape(-1, 8)
-    P, I = ctypes.c_void_p * 3, ctypes.c_int * 3
-
-    def call(fmt=ra.PIX_BGR, pl=(dframe, None, None), pi=(pitch, 0, 0), w=iw, h=ih, kind=1, quads_p=q.ctypes.data, n=len(q), out_p=out.ptr, out_kind=1):
-        return L().rd_rectifier_enqueue(rect.h, fmt, P(*pl), I(*pi), w, h, kind, quads_p, n, out_p, out_kind)
-
-    errors = {"unknown format": dict(fmt=6), "NULL plane": dict(pl=(None, None, None)), "short pitch": dict(pi=(iw * 3 - 1, 0, 0)), "odd width with 4:2:0": dict(fmt=ra.PIX_NV12, pl=(dframe, dframe, None), pi=(pitch, pitch, 0)),
-              "n < 0": dict(n=-1), "n > max_quads": dict(n=len(q) + 1), "pageable out": dict(out_p=pageable.ctypes.data, out_kind=2), "pageable out as device memory": dict(out_p=pageable.ctypes.data),
-              "unknown out_kind": dict(out_kind=0), "unknown on_device": dict(kind=3), "no size": dict(w=0), "NULL quads": dict(quads_p=None), "NULL out": dict(out_p=None)}
     try:
-        for name, kw in errors.items():
-            assert call(**kw) == -1, name
-            assert L().rd_rectifier_wait(rect.h, None) == -1, name + ": nothing may have been enqueued"
-        assert call() == 0      # the first job after all of them: sequence number 0, the right bytes
+        q = rectjobs.refused_enqueues(mem, rect, planes, iw, ih, quads, out)      # and the first job after all of them: the right bytes
         status = rect.wait()
         scan.assert_pages(out.fetch().reshape(rect.shape(len(q))), status, want, wstatus, "the job after the refused ones")
     finally:
@@ -344,56 +233,15 @@ def test_argument_errors_return_minus_one_and_the_next_job_is_correct(mem):
 
 
 # ---------------------------------------------------------------------------------------------- behind the detector's poll
-PW, PH = 100, 60
-SIW, SIH, SN = 640, 480, 3
-FIXED_QUAD = np.array([[(101.5, 80.25), (420.0, 60.0), (500.5, 400.0), (60.0, 330.5)]])
 POLL_SPEC = ra.scan_spec(ra.SCAN_BITS, 15, 26, 0, oversample=2)
-
-
-@lru_cache(maxsize=None)
-def stream_frames(fmt):
-    return tuple(pixfmt.convert(cframe(synth.SEED0, SIW, SIH, t), fmt) for t in range(SN))
 
 
 @pytest.mark.parametrize("kind", ["rect-host", "rect-device", "poly-host", "poly-device", "scaled"])
 def test_rectify_polled_behind_every_poll(kind, mem):
     """after Detector.poll and PolylineDetector.poll, on host frames (the detector's own copy) and device frames, and on a frame that came in at scale 2 - quads in
     detector coordinates, the page from the full-size source (X = 2x + 0.5)"""
-    poly, scaled, device = kind.startswith("poly"), kind == "scaled", kind.endswith("device")
-    fmt = ra.PIX_NV12 if device else ra.PIX_BGR
-    scale = 2 if scaled else 1
-    dw, dh = SIW // scale, SIH // scale
-    det = ra.PolylineDetector(dw, dh, nslots=2) if poly else ra.Detector(dw, dh, nslots=2, aperture=TAN36)
-    rect = ra.Rectifier(PW, PH, max_quads=8, njobs=2, scan=POLL_SPEC)
-    trect = ra.Rectifier(PW, PH, max_quads=8, njobs=2, tensor=scan.gray_spec(POLL_SPEC))
-    total = 0
-    try:
-        out, tout = Out(mem, "device", 8 * rect.patch_bytes), Out(mem, "device", 8 * trect.patch_bytes)
-        with pytest.raises(ValueError):      # nothing polled yet
-            det.rectify_polled(rect, FIXED_QUAD, out.ptr)
-        for t, (planes, bgr) in enumerate(stream_frames(fmt)):
-            if scaled:
-                det.enqueue_scaled(fmt, planes)
-            elif device:
-                args, pitches, kw = mem.place("device", planes, 8)
-                det.enqueue_planes(fmt, args, pitches, **kw)
-            else:
-                det.enqueue_planes(fmt, planes)
-            res = det.poll()[0] if poly else det.poll(TAN36)
-            quads = FIXED_QUAD / scale if poly or len(res) == 0 else np.concatenate([ra.rect_quads(res)[:3], FIXED_QUAD / scale])
-            assert det.rectify_polled(rect, quads, out.ptr) == t and det.rectify_polled(trect, quads, tout.ptr) == t
-            status, tstatus = rect.wait(), trect.wait()
-            got = out.fetch(len(quads) * rect.patch_bytes).reshape(rect.shape(len(quads)))
-            plane = tout.fetch(len(quads) * trect.patch_bytes).reshape(len(quads), PH, PW)
-            want, wstatus = scan.pages(bgr, quads * 2.0 + 0.5 if scaled else quads, PW, PH, POLL_SPEC)
-            assert tstatus.tolist() == wstatus.tolist()
-            localise(got, status, plane, want, wstatus, POLL_SPEC, "%s frame %d" % (kind, t))
-            total += len(quads)
-        assert total > SN or not kind.startswith("rect"), "the stream's frames hold rectangles"
-    finally:
-        rect.close()
-        trect.close()
-        det.close()
+    rectjobs.polled_behind_a_poll(mem, kind, dict(scan=POLL_SPEC), lambda bgr, quads: scan.pages(bgr, quads, rectjobs.PW, rectjobs.PH, POLL_SPEC),
+                                  lambda got, status, plane, want, wstatus, what: localise(got, status, plane, want, wstatus, POLL_SPEC, what), beside=dict(tensor=scan.gray_spec(POLL_SPEC)))
 
 
 # ---------------------------------------------------------------------------------------------- memory that torch allocated
@@ -427,19 +275,15 @@ print("done", flush=True)
 def test_torch_tensors_are_written_through_data_ptr(tmp_path):
     """torch.uint8 tensors of packed bit rows and of flat pages, allocated by torch on the device and written through data_ptr(), read back with t.cpu(): the
     restatement's bytes.  In a child process, because what is tested is a process that imports torch first and so holds one HIP runtime."""
-    pytest.importorskip("torch")
-    import re
-    import sys
     iw, ih, planes, bgr, quads = case(ra.PIX_BGR)
     pw, ph = TW + 1, 9
-    np.savez(tmp_path / "in.npz", frame=bgr, quads=quads, pw=pw, ph=ph)
-    r = subprocess.run([sys.executable, "-c", TORCH_CHILD, str(tmp_path / "in.npz"), str(tmp_path) + os.sep], cwd=helpers.ROOT, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "done" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
-    for name, mode in (("bits", ra.SCAN_BITS), ("flat", ra.SCAN_FLAT)):
+    modes = {"bits": ra.SCAN_BITS, "flat": ra.SCAN_FLAT}
+    child = rectjobs.torch_child(tmp_path, TORCH_CHILD, modes, frame=bgr, quads=quads, pw=pw, ph=ph)
+    for name, mode in modes.items():
         want, wstatus = reference(ra.PIX_BGR, pw, ph, ra.scan_spec(mode, 8, 26, 0, oversample=2))
-        got, status = np.load(tmp_path / (name + ".npy")), np.load(tmp_path / (name + "_status.npy"))
+        got, status, total = child[name]
         scan.assert_pages(got, status, want, wstatus, name)
-        assert int(re.search(name + r" sum (\d+)", r.stdout).group(1)) == int(want.astype(np.int64).sum()), "torch summed the bytes the job wrote"
+        assert int(total) == int(want.astype(np.int64).sum()), "torch summed the bytes the job wrote"
 
 
 # ---------------------------------------------------------------------------------------------- the example program

@@ -2,9 +2,7 @@
 for every dtype, layout, channel kind and oversampling, output sizes on every side of the kernel's tile and tail, all six pixel formats, host / device / pinned
 frames, device / pinned output, a misaligned output, invalid quads, jobs in flight, empty and full jobs, argument errors, behind the poll of both detector kinds,
 into memory that torch allocated, and from the example program.  Every device output lies between guard bytes that must not change.  No tolerance anywhere."""
-import ctypes
 import os
-import re
 import subprocess
 from functools import lru_cache
 
@@ -14,54 +12,18 @@ import pytest
 import rectdetect_amd as ra
 from rectdetect_amd import synth
 from tests import helpers
-from tests import jobframes
 from tests import match
 from tests import pixfmt
 from tests import rectify
+from tests import rectjobs
 from tests import tensor
-from tests.jobframes import L, cframe
+from tests.rectjobs import L, Out, STATUS, case, cframe, mem, run_job      # (mem: the fixture)
 
 pytestmark = pytest.mark.gpu
-TAN36 = float(np.tan(36.0 / 180.0 * np.pi))
-GUARD = 64
 # the output sizes at which the kernel can go wrong: one element; the tail path alone; exactly one wave; one pixel into the next wave in both directions, with a
 # row tail and rows that start misaligned; several threads of a second wave, rows a multiple of 4
 SHAPES = ((1, 1), (5, 3), (32, 8), (33, 9), (36, 12))
 NORM = dict(scale=(1 / 58.395 / 1.0, 1 / 57.12, 1 / 57.375), bias=(-2.1179, -2.0357, -1.8044))
-
-
-@pytest.fixture
-def mem():
-    m = jobframes.Mem()
-    yield m
-    m.close()
-
-
-def noise_frame(iw, ih, seed=5):
-    return np.random.default_rng(seed).integers(0, 256, (ih, iw, 3), dtype=np.uint8)
-
-
-def job_quads(iw, ih):
-    """an axis-aligned quad, a non-convex (invalid) one BETWEEN valid ones, a rotated quad in perspective, a quad that reaches outside the frame on two sides"""
-    w, h = float(iw), float(ih)
-    return np.array([
-        [(10.5, 8.5), (74.5, 8.5), (74.5, 40.5), (10.5, 40.5)],
-        [(0.0, 0.0), (60.0, 0.0), (20.0, 20.0), (0.0, 50.0)],
-        [(30.25, 6.5), (88.75, 14.0), (80.0, 55.5), (12.5, 41.0)],
-        [(w - 40.0, h - 30.0), (w + 12.5, h - 36.0), (w + 7.0, h + 9.0), (w - 48.0, h + 4.25)],
-    ], np.float64)
-
-
-STATUS = np.array([1, 0, 1, 1], np.uint8)
-
-
-@lru_cache(maxsize=None)
-def case(fmt):
-    """(iw, ih, planes, the contract's BGR frame, quads): 97 x 61 for the packed formats, 96 x 60 for 4:2:0"""
-    iw, ih = (97, 61) if fmt <= ra.PIX_RGBA else (96, 60)
-    planes, bgr = pixfmt.convert(noise_frame(iw, ih, 21 + fmt), fmt)
-    assert np.array_equal(rectify.contract_bgr(fmt, planes), bgr)
-    return iw, ih, planes, bgr, job_quads(iw, ih)
 
 
 @lru_cache(maxsize=None)
@@ -99,48 +61,6 @@ def test_shared_reference_is_the_restatement():
     a, b = reference(ra.PIX_BGR, 33, 9, spec), tensor.tensors(bgr, quads, 33, 9, spec)
     tensor.assert_tensors(a[0], a[1], b[0], b[1])
     assert a[1].tolist() == STATUS.tolist()
-
-
-class Out:
-    """an output of nbytes in device memory between guards (0xA5, like the output itself before its job), `offset` bytes off its aligned start; or in pinned memory"""
-
-    def __init__(self, mem, kind, nbytes, offset=0):
-        self.mem, self.kind, self.nbytes, self.offset = mem, kind, nbytes, offset
-        if kind == "device":
-            self.total = GUARD + offset + nbytes + GUARD
-            self.base = L().rd_device_alloc(self.total)
-            mem.dev.append(self.base)
-            fill = np.full(self.total, 0xA5, np.uint8)
-            L().rd_upload(self.base, fill.ctypes.data, self.total)
-            self.ptr = self.base + GUARD + offset
-        else:
-            assert offset == 0
-            self.ptr = mem.out("pinned", nbytes)
-
-    def fetch(self, nbytes=None):
-        """the first nbytes the job wrote; everything around them must be 0xA5 still"""
-        nbytes = self.nbytes if nbytes is None else nbytes
-        if self.kind != "device":
-            a = self.mem.fetch("pinned", self.ptr, self.nbytes)
-            assert (a[nbytes:] == 0xA5).all(), "bytes behind the job's last byte were written"
-            return a[:nbytes]
-        a = np.zeros(self.total, np.uint8)
-        L().rd_download(a.ctypes.data, self.base, self.total)
-        lo = GUARD + self.offset
-        assert (a[:lo] == 0xA5).all(), "bytes before `out` were written"
-        assert (a[lo + nbytes:] == 0xA5).all(), "bytes behind the job's last byte were written"
-        return a[lo:lo + nbytes].copy()
-
-
-def run_job(rect, mem, fmt, planes, iw, ih, quads, kind="device", out_kind="device", pad=0, offset=0):
-    """one job, waited for: (the array of rect.shape(n) and rect.dtype, status)"""
-    q = np.asarray(quads, np.float64).reshape(-1, 8)
-    nbytes = len(q) * rect.patch_bytes
-    args, pitches, kw = mem.place(kind, planes, pad)
-    out = Out(mem, out_kind, nbytes, offset)
-    rect.enqueue(fmt, args, pitches, iw, ih, q, out.ptr, out_pinned=out_kind == "pinned", **kw)
-    status = rect.wait()
-    return out.fetch().view(rect.dtype).reshape(rect.shape(len(q))), status
 
 
 def check_spec(mem, fmt, pw, ph, spec, kinds=(("device", "device", 0),), offset=0):
@@ -318,23 +238,9 @@ def test_argument_errors_return_minus_one_and_the_next_job_is_correct(mem):
         assert not create(*args, sp.ctypes.data), args      # rd_rectifier_create's bad arguments (pw * m > 16384 among them)
     assert L().rd_rectifier_patch_bytes(None) == 0
     rect = ra.Rectifier(pw, ph, max_quads=len(quads), njobs=1, tensor=spec)
-    (dframe,), (pitch,), _ = mem.place("device", planes, 3)
     out = Out(mem, "device", len(quads) * rect.patch_bytes)
-    pageable = np.zeros(len(quads) * rect.patch_bytes, np.uint8)
-    q = np.ascontiguousarray(quads).reshape(-1, 8)
-    P, I = ctypes.c_void_p * 3, ctypes.c_int * 3
-
-    def call(fmt=ra.PIX_BGR, pl=(dframe, None, None), pi=(pitch, 0, 0), w=iw, h=ih, kind=1, quads_p=q.ctypes.data, n=len(q), out_p=out.ptr, out_kind=1):
-        return L().rd_rectifier_enqueue(rect.h, fmt, P(*pl), I(*pi), w, h, kind, quads_p, n, out_p, out_kind)
-
-    errors = {"unknown format": dict(fmt=6), "NULL plane": dict(pl=(None, None, None)), "short pitch": dict(pi=(iw * 3 - 1, 0, 0)), "odd width with 4:2:0": dict(fmt=ra.PIX_NV12, pl=(dframe, dframe, None), pi=(pitch, pitch, 0)),
-              "n < 0": dict(n=-1), "n > max_quads": dict(n=len(q) + 1), "pageable out": dict(out_p=pageable.ctypes.data, out_kind=2), "pageable out as device memory": dict(out_p=pageable.ctypes.data),
-              "unknown out_kind": dict(out_kind=0), "unknown on_device": dict(kind=3), "no size": dict(w=0), "NULL quads": dict(quads_p=None), "NULL out": dict(out_p=None)}
     try:
-        for name, kw in errors.items():
-            assert call(**kw) == -1, name
-            assert L().rd_rectifier_wait(rect.h, None) == -1, name + ": nothing may have been enqueued"
-        assert call() == 0      # the first job after all of them: sequence number 0, the right elements
+        q = rectjobs.refused_enqueues(mem, rect, planes, iw, ih, quads, out)      # and the first job after all of them: the right elements
         status = rect.wait()
         tensor.assert_tensors(out.fetch().view(rect.dtype).reshape(rect.shape(len(q))), status, want, wstatus, "the job after the refused ones")
     finally:
@@ -342,52 +248,15 @@ def test_argument_errors_return_minus_one_and_the_next_job_is_correct(mem):
 
 
 # ---------------------------------------------------------------------------------------------- behind the detector's poll
-PW, PH = 100, 60
-SIW, SIH, SN = 640, 480, 4
-FIXED_QUAD = np.array([[(101.5, 80.25), (420.0, 60.0), (500.5, 400.0), (60.0, 330.5)]])
 POLL_SPEC = ra.tensor_spec(ra.TENSOR_F16, ra.TENSOR_NCHW, ra.TENSOR_RGB, 2, **NORM)
-
-
-@lru_cache(maxsize=None)
-def stream_frames(fmt):
-    return tuple(pixfmt.convert(cframe(synth.SEED0, SIW, SIH, t), fmt) for t in range(SN))
 
 
 @pytest.mark.parametrize("kind", ["rect-host", "rect-device", "poly-host", "poly-device", "scaled"])
 def test_rectify_polled_behind_every_poll(kind, mem):
     """after Detector.poll and PolylineDetector.poll, on host frames (the detector's own copy) and device frames, and on a frame that came in at scale 2 - quads in
     detector coordinates, the tensor from the full-size source (X = 2x + 0.5)"""
-    poly, scaled, device = kind.startswith("poly"), kind == "scaled", kind.endswith("device")
-    fmt = ra.PIX_NV12 if device else ra.PIX_BGR
-    scale = 2 if scaled else 1
-    dw, dh = SIW // scale, SIH // scale
-    det = ra.PolylineDetector(dw, dh, nslots=2) if poly else ra.Detector(dw, dh, nslots=2, aperture=TAN36)
-    rect = ra.Rectifier(PW, PH, max_quads=64, njobs=2, tensor=POLL_SPEC)
-    total = 0
-    try:
-        out = Out(mem, "device", 64 * rect.patch_bytes)
-        with pytest.raises(ValueError):      # nothing polled yet
-            det.rectify_polled(rect, FIXED_QUAD, out.ptr)
-        for t, (planes, bgr) in enumerate(stream_frames(fmt)):
-            if scaled:
-                det.enqueue_scaled(fmt, planes)
-            elif device:
-                args, pitches, kw = mem.place("device", planes, 8)
-                det.enqueue_planes(fmt, args, pitches, **kw)
-            else:
-                det.enqueue_planes(fmt, planes)
-            res = det.poll()[0] if poly else det.poll(TAN36)
-            quads = FIXED_QUAD / scale if poly or len(res) == 0 else np.concatenate([ra.rect_quads(res)[:6], FIXED_QUAD / scale])
-            assert det.rectify_polled(rect, quads, out.ptr) == t
-            status = rect.wait()
-            got = out.fetch(len(quads) * rect.patch_bytes).view(rect.dtype).reshape(rect.shape(len(quads)))
-            want, wstatus = tensor.tensors(bgr, quads * 2.0 + 0.5 if scaled else quads, PW, PH, POLL_SPEC)
-            tensor.assert_tensors(got, status, want, wstatus, "%s frame %d" % (kind, t))
-            total += len(quads)
-        assert total > SN or not kind.startswith("rect"), "the stream's frames hold rectangles"
-    finally:
-        rect.close()
-        det.close()
+    rectjobs.polled_behind_a_poll(mem, kind, dict(tensor=POLL_SPEC), lambda bgr, quads: tensor.tensors(bgr, quads, rectjobs.PW, rectjobs.PH, POLL_SPEC),
+                                  lambda got, status, _, want, wstatus, what: tensor.assert_tensors(got, status, want, wstatus, what), max_quads=64, nrects=6, nframes=4)
 
 
 # ---------------------------------------------------------------------------------------------- memory that torch allocated
@@ -422,19 +291,15 @@ print("done", flush=True)
 def test_torch_tensors_are_written_through_data_ptr(tmp_path):
     """a torch.float16 NCHW and a torch.bfloat16 NHWC tensor, allocated by torch on the device and written through data_ptr(), read back with t.cpu(): the
     restatement's bits.  In a child process, because what is tested is a process that imports torch first and so holds one HIP runtime."""
-    pytest.importorskip("torch")
-    import sys
     iw, ih, planes, bgr, quads = case(ra.PIX_BGR)
     pw, ph = 33, 9
-    np.savez(tmp_path / "in.npz", frame=bgr, quads=quads, pw=pw, ph=ph, scale=np.array(NORM["scale"], np.float32), bias=np.array(NORM["bias"], np.float32))
-    r = subprocess.run([sys.executable, "-c", TORCH_CHILD, str(tmp_path / "in.npz"), str(tmp_path) + os.sep], cwd=helpers.ROOT, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "done" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
-    for name, spec in (("f16_nchw", ra.tensor_spec(ra.TENSOR_F16, ra.TENSOR_NCHW, ra.TENSOR_RGB, 2, **NORM)), ("bf16_nhwc", ra.tensor_spec(ra.TENSOR_BF16, ra.TENSOR_NHWC, ra.TENSOR_RGB, 1, **NORM))):
+    specs = {"f16_nchw": ra.tensor_spec(ra.TENSOR_F16, ra.TENSOR_NCHW, ra.TENSOR_RGB, 2, **NORM), "bf16_nhwc": ra.tensor_spec(ra.TENSOR_BF16, ra.TENSOR_NHWC, ra.TENSOR_RGB, 1, **NORM)}
+    child = rectjobs.torch_child(tmp_path, TORCH_CHILD, specs, frame=bgr, quads=quads, pw=pw, ph=ph, scale=np.array(NORM["scale"], np.float32), bias=np.array(NORM["bias"], np.float32))
+    for name, spec in specs.items():
         want, wstatus = reference(ra.PIX_BGR, pw, ph, spec)
-        got, status = np.load(tmp_path / (name + ".npy")).view(np.uint16), np.load(tmp_path / (name + "_status.npy"))
-        tensor.assert_tensors(got, status, np.ascontiguousarray(want).view(np.uint16), wstatus, name)
-        total = float(re.search(name + r" sum (\S+)", r.stdout).group(1))
-        assert np.isfinite(total), "the tensors hold finite values and torch summed them"
+        got, status, total = child[name]
+        tensor.assert_tensors(got.view(np.uint16), status, np.ascontiguousarray(want).view(np.uint16), wstatus, name)
+        assert np.isfinite(float(total)), "the tensors hold finite values and torch summed them"
 
 
 # ---------------------------------------------------------------------------------------------- the example program
