@@ -16,56 +16,30 @@ Every GPU step is a child process under a time limit of its own; the tool stops 
 import argparse
 import json
 import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+from tools import benchlib as bl
+from tools.benchlib import TAN36
 
-from tools.bench_rectify import random_quads, synth_frames
-
-TAN36 = float(np.tan(36.0 / 180.0 * np.pi))
 NJOBS = 4
 IW, IH = 1920, 1080
 LOOP_MODES = ("none", "rectify", "annotate", "annotate_out")
 
 
 def timed_jobs(an, job, label, extra):
-    for k in range(64):      # warm-up
-        job(k)
-        an.wait()
-    lat = []
-    for k in range(300):
-        t = time.perf_counter()
-        job(k)
-        an.wait()
-        lat.append(time.perf_counter() - t)
     n = 4000
-    t = time.perf_counter()
-    inflight = 0
-    for k in range(n):
-        if inflight == NJOBS:
-            an.wait()
-            inflight -= 1
-        job(k)
-        inflight += 1
-    while inflight:
-        an.wait()
-        inflight -= 1
-    dt = time.perf_counter() - t
-    lat = np.sort(np.array(lat)) * 1e6
+    lat, dt = bl.timed_jobs(job, lambda k: an.wait(), NJOBS, 64, 300, n)
     print(json.dumps(dict({"step": "jobs", "job": label, "size": "%dx%d" % (IW, IH), "jobs_in_flight": NJOBS, "jobs": n, "us_per_job_in_flight": round(dt / n * 1e6, 2),
-                           "job_latency_us_median": round(float(lat[len(lat) // 2]), 1), "job_latency_us_p10": round(float(lat[len(lat) // 10]), 1),
-                           "job_latency_us_p90": round(float(lat[len(lat) * 9 // 10]), 1)}, **extra)), flush=True)
+                           **bl.latency_fields(lat)}, **extra)), flush=True)
 
 
 def child_jobs():
     import rectdetect_amd as ra
     from tests import pixfmt
     L = ra.lib()
-    frame = synth_frames(IW, IH, 1)[0]
+    frame = bl.synth_frames(IW, IH, 1)[0]
     det = ra.Detector(IW, IH, nslots=1, aperture=TAN36)
     det.enqueue(frame)
     rect_prims = ra.annot_rects(det.poll(TAN36))
@@ -75,25 +49,21 @@ def child_jobs():
     seg_prims = ra.annot_segments(pdet.poll()[0], ra.ANNOT_SEG_ALL)
     pdet.close()
     an = ra.Annotator(max_prims=max(len(rect_prims), len(seg_prims), 1), njobs=NJOBS)
-    dframe = L.rd_device_alloc(frame.nbytes)
-    L.rd_upload(dframe, frame.ctypes.data, frame.nbytes)
+    dframe = bl.upload([frame])[0]
     timed_jobs(an, lambda k: an.enqueue(ra.PIX_BGR, (dframe,), (IW * 3,), IW, IH, rect_prims, on_device=True), "a: rectangles, BGR in place",
                {"primitives": len(rect_prims), "format": "BGR", "frames": "device, in place", "clear": False})
     timed_jobs(an, lambda k: an.enqueue(ra.PIX_BGR, (dframe,), (IW * 3,), IW, IH, seg_prims, ra.ANNOT_CLEAR, on_device=True), "b: segments on black, BGR in place",
                {"primitives": len(seg_prims), "format": "BGR", "frames": "device, in place", "clear": True})
     (y, uv), _ = pixfmt.convert(frame, ra.PIX_NV12)
     y, uv = np.ascontiguousarray(y), np.ascontiguousarray(uv)
-    src = [L.rd_device_alloc(y.nbytes), L.rd_device_alloc(uv.nbytes)]
+    src = bl.upload([y, uv])
     dst = [L.rd_device_alloc(y.nbytes), L.rd_device_alloc(uv.nbytes)]
-    L.rd_upload(src[0], y.ctypes.data, y.nbytes)
-    L.rd_upload(src[1], uv.ctypes.data, uv.nbytes)
     timed_jobs(an, lambda k: an.enqueue(ra.PIX_NV12, src, (IW, IW), IW, IH, seg_prims, ra.ANNOT_CLEAR, out_planes=dst, out_pitches=(IW, IW), on_device=True),
                "c: segments on black, NV12 device to device", {"primitives": len(seg_prims), "format": "NV12", "frames": "device to device", "clear": True})
     timed_jobs(an, lambda k: an.enqueue(ra.PIX_NV12, src, (IW, IW), IW, IH, rect_prims, out_planes=dst, out_pitches=(IW, IW), on_device=True),
                "rectangles, NV12 device to device", {"primitives": len(rect_prims), "format": "NV12", "frames": "device to device", "clear": False})
     an.close()
-    for q in [dframe] + src + dst:
-        L.rd_device_free(q)
+    bl.free([dframe] + src + dst)
 
 
 def child_loop(nslots, pattern):
@@ -102,65 +72,34 @@ def child_loop(nslots, pattern):
     # a pool with a device frame of its own for EVERY frame of a run (16 images in turn, 7 GB): in place each frame is drawn into once, after its detection, and never
     # detected again, so the detector's work is the same in all four modes; and no frame in flight is ever drawn into
     frames, warmup, p = 1024, 128, 128
-    base = synth_frames(IW, IH, 16)
+    base = bl.synth_frames(IW, IH, 16)
     imgs = [base[k % 16] for k in range(frames + warmup)]
-    dptrs = []
-    for a in imgs:
-        q = L.rd_device_alloc(a.nbytes)
-        L.rd_upload(q, a.ctypes.data, a.nbytes)
-        dptrs.append(q)
-    quads = random_quads(IW, IH, 32)
+    dptrs = bl.upload(imgs)
+    quads = bl.random_quads(IW, IH, 32)
     outs = [L.rd_device_alloc(32 * p * p * 3) for _ in range(NJOBS)]
     oframes = [L.rd_device_alloc(IW * IH * 3) for _ in range(NJOBS)]
     rect = ra.Rectifier(p, p, max_quads=32, njobs=NJOBS)
     an = ra.Annotator(max_prims=1024, njobs=NJOBS)
 
-    def run(det, first, n, mode, tally):
-        inflight = jobs = 0
-        worker = rect if mode == "rectify" else an
+    def enqueue(det, i):
+        det.enqueue(dptrs[i], IW * 3, on_device=True)
 
-        def poll():
-            nonlocal jobs
-            rects = det.poll(TAN36)
-            tally[0] += len(rects)
-            if mode == "none":
-                return
-            if jobs == NJOBS:
-                worker.wait()
-                jobs -= 1
+    def run(det, mode, timed, tally):
+        def behind(det, worker, rects, i, k):
             if mode == "rectify":
-                det.rectify_polled(rect, quads, outs[tally[1] % NJOBS])
+                det.rectify_polled(rect, quads, outs[k % NJOBS])
+                return 0
+            prims = ra.annot_rects(rects[:170])
+            if mode == "annotate":
+                det.annotate_polled(an, prims)
             else:
-                prims = ra.annot_rects(rects[:170])
-                tally[2] += len(prims)
-                if mode == "annotate":
-                    det.annotate_polled(an, prims)
-                else:
-                    det.annotate_polled(an, prims, out_planes=(oframes[tally[1] % NJOBS],), out_pitches=(IW * 3,))
-            tally[1] += 1
-            jobs += 1
+                det.annotate_polled(an, prims, out_planes=(oframes[k % NJOBS],), out_pitches=(IW * 3,))
+            return len(prims)
 
-        for i in range(n):
-            if inflight == nslots:
-                poll()
-                inflight -= 1
-            det.enqueue(dptrs[first + i], IW * 3, on_device=True)
-            inflight += 1
-        while inflight:
-            poll()
-            inflight -= 1
-        while jobs:
-            worker.wait()
-            jobs -= 1
+        worker = None if mode == "none" else (rect if mode == "rectify" else an)
+        bl.detector_loop(det, frames if timed else warmup, nslots, enqueue, tally, first=warmup if timed else 0, worker=worker, njobs=NJOBS, behind=behind)
 
-    for r, mode in enumerate(pattern):
-        det = ra.Detector(IW, IH, nslots=nslots, nworkers=1, aperture=TAN36)
-        run(det, 0, warmup, mode, [0, 0, 0])
-        tally = [0, 0, 0]
-        t = time.perf_counter()
-        run(det, warmup, frames, mode, tally)      # (ends with every frame polled and every job waited for)
-        dt = time.perf_counter() - t
-        det.close()
+    for r, mode, dt, tally in bl.detector_runs(pattern, lambda: ra.Detector(IW, IH, nslots=nslots, nworkers=1, aperture=TAN36), run):
         if mode == "annotate":      # (the next run starts from the pool as it was uploaded)
             for q, a in zip(dptrs, imgs):
                 L.rd_upload(q, a.ctypes.data, a.nbytes)
@@ -168,8 +107,7 @@ def child_loop(nslots, pattern):
                           "frames_per_s": round(frames / dt, 1), "rectangles": tally[0], "primitives_per_frame": round(tally[2] / frames, 1), "frames_kind": "device"}), flush=True)
     rect.close()
     an.close()
-    for q in outs + oframes + dptrs:
-        L.rd_device_free(q)
+    bl.free(outs + oframes + dptrs)
 
 
 def main():
@@ -179,14 +117,12 @@ def main():
     ap.add_argument("--repeat", type=int, default=3, help="rounds of (none, rectify, annotate, annotate_out) in the loop step")
     ap.add_argument("--pattern", default=None, help="the loop step's runs in one process, e.g. none,none,annotate (default: all four --repeat times)")
     ap.add_argument("--timeout", type=int, default=300, help="seconds allowed per GPU step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "annotate_bench.jsonl"))
+    ap.add_argument("--out", default=os.path.join(bl.ROOT, "profiles", "annotate_bench.jsonl"))
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     pattern = a.pattern or ",".join([",".join(LOOP_MODES)] * a.repeat)
     if a.child:
-        import rectdetect_amd as ra
-        if not ra.gpu_available():
-            raise SystemExit("bench_annotate: no HIP device - nothing is measured without one")
+        bl.require_gpu("bench_annotate")
         if a.child == "jobs":
             child_jobs()
         else:
@@ -195,23 +131,8 @@ def main():
                 raise SystemExit("bench_annotate: --pattern takes %s" % ", ".join(LOOP_MODES))
             child_loop(a.nslots, modes)
         return 0
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    for step in a.steps.split(","):
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", step, "--nslots", str(a.nslots), "--pattern", pattern]
-        try:
-            res = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=a.timeout)
-        except subprocess.TimeoutExpired:
-            print("bench_annotate: step %s ran into its time limit of %d s - stopping" % (step, a.timeout), file=sys.stderr)
-            return 124
-        text = res.stdout.decode()
-        sys.stdout.write(text)
-        sys.stdout.flush()
-        if res.returncode != 0:
-            print("bench_annotate: step %s failed with status %d - stopping" % (step, res.returncode), file=sys.stderr)
-            return res.returncode if res.returncode > 0 else 1
-        with open(a.out, "a") as f:
-            f.write(text)
-    return 0
+    cmd = lambda step: [sys.executable, os.path.abspath(__file__), "--child", step, "--nslots", str(a.nslots), "--pattern", pattern]
+    return bl.drive("bench_annotate", a.steps.split(","), cmd, a.out, a.timeout)
 
 
 if __name__ == "__main__":

@@ -24,63 +24,18 @@ stops at the first step that fails.  bench.py is not involved.
     python tools/bench_code.py [--size 1920x1080] [--patch 128] [--oversample 1] [--steps rates,kernels,loop] [--rounds R] [--repeat R] [--out FILE]
 """
 import argparse
-import csv
 import ctypes
-import glob
 import json
 import os
-import shutil
-import signal
-import subprocess
 import sys
-import tempfile
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+from tools import benchlib as bl
 
-TAN36 = float(np.tan(36.0 / 180.0 * np.pi))
 NJOBS = 4
 NDICTS = (0, 64, 1024, 4096)
 SLOW = ("gray-pinned-host",)      # configurations timed over fewer jobs
-
-
-def run_step(cmd, timeout, capture_stderr=False):
-    """cmd in a process group of its own, the whole group killed at the time limit - under the tracer the GPU is open in a grandchild, which the death of its parent
-    would not end: (return code, stdout, stderr or None); subprocess.TimeoutExpired once every process of the step is gone"""
-    p = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE if capture_stderr else None, start_new_session=True)
-    try:
-        out, err = p.communicate(timeout=timeout)
-    except subprocess.TimeoutExpired:
-        try:
-            os.killpg(p.pid, signal.SIGKILL)
-        except ProcessLookupError:
-            pass
-        p.communicate()
-        raise
-    return p.returncode, out, err
-
-
-def synth_frames(iw, ih, n):
-    import rectdetect_amd as ra
-    out = []
-    for t in range(n):
-        a = np.empty((ih, iw, 3), np.uint8)
-        ra.lib().rd_synth_frame(a.ctypes.data, iw, ih, iw * 3, 0x5EED0000, t, 1)
-        out.append(a)
-    return out
-
-
-def own_quads(frame):
-    """the quads of the frame's own rectangles"""
-    import rectdetect_amd as ra
-    ih, iw = frame.shape[:2]
-    det = ra.Detector(iw, ih, nslots=1, aperture=TAN36)
-    det.enqueue(frame)
-    rects = det.poll(TAN36)
-    det.close()
-    return ra.rect_quads(rects)
 
 
 def code_spec(m):
@@ -95,18 +50,11 @@ def dictionary(nd):
 
 
 def child_rates(iw, ih, p, m, rounds, trace_only):
-    import rectdetect_amd as ra
     from tests import code as restated
-    if not ra.gpu_available():
-        raise SystemExit("bench_code: no HIP device - nothing is measured without one")
+    ra = bl.require_gpu("bench_code")
     L = ra.lib()
-    frame = synth_frames(iw, ih, 1)[0]
-    quads = own_quads(frame)[:64]
+    frame, quads, dframe = bl.own_frame("bench_code", iw, ih, 64)
     n = len(quads)
-    if n == 0:
-        raise SystemExit("bench_code: the synthetic frame holds no rectangle")
-    dframe = L.rd_device_alloc(frame.nbytes)
-    L.rd_upload(dframe, frame.ctypes.data, frame.nbytes)
     spec = code_spec(m)
     gray = lambda: ra.Rectifier(p, p, max_quads=n, njobs=NJOBS, tensor=ra.tensor_spec(ra.TENSOR_U8, ra.TENSOR_NHWC, ra.TENSOR_GRAY, m))
     rects = {"gray": gray()}
@@ -140,46 +88,18 @@ def child_rates(iw, ih, p, m, rounds, trace_only):
         if not np.array_equal(host, mine):
             raise SystemExit("bench_code: the host's decoder and the code job disagree")
 
-    lat = {name: [] for name in rects}
-    rate = {name: [] for name in rects}
-    for name in rects:      # warm-up (under the tracer: all there is)
-        for k in range(3 if name in SLOW else (100 if trace_only else 32)):
-            job(name, k)
-            done(name, k)
-    for r in range(0 if trace_only else rounds):
-        for name in rects:
-            one = []
-            for k in range(5 if name in SLOW else 100):
-                t = time.perf_counter()
-                job(name, k)
-                done(name, k)
-                one.append(time.perf_counter() - t)
-            lat[name].append(float(np.median(one)) * 1e6)
-        for name in rects:
-            njobs_timed, inflight = 8 if name in SLOW else 400, 0
-            t = time.perf_counter()
-            for k in range(njobs_timed):
-                if inflight == NJOBS:
-                    done(name, k - NJOBS)
-                    inflight -= 1
-                job(name, k)
-                inflight += 1
-            while inflight:
-                done(name, njobs_timed - inflight)
-                inflight -= 1
-            rate[name].append(njobs_timed / (time.perf_counter() - t))
+    # (under the tracer the warm-up is all there is)
+    lat, rate = bl.alternating_rounds(rects, job, done, 0 if trace_only else rounds, NJOBS, (100 if trace_only else 32, 100, 400), slow=SLOW, slow_counts=(3, 5, 8))
     if not trace_only:
         base = float(np.median(lat["gray"]))
         for name in rects:
-            med = float(np.median(lat[name]))
             print(json.dumps({"step": "rates", "config": name, "size": "%dx%d" % (iw, ih), "patch": "%dx%d" % (p, p), "oversample": m, "quads_per_job": n, "jobs_in_flight": NJOBS, "rounds": rounds,
-                              "bytes_per_quad": rects[name].patch_bytes, "job_latency_us_median": round(med, 1), "job_latency_us_min_round": round(min(lat[name]), 1),
-                              "job_latency_us_max_round": round(max(lat[name]), 1), "over_the_gray_job_us": round(med - base, 1), "jobs_per_s_median": round(float(np.median(rate[name])), 1),
-                              "quads_per_s_median": round(float(np.median(rate[name])) * n, 1), "frames": "device", "output": "pinned" if pinned(name) else "device"}), flush=True)
+                              "bytes_per_quad": rects[name].patch_bytes, **bl.round_fields(lat[name]), "over_the_gray_job_us": round(float(np.median(lat[name])) - base, 1),
+                              "jobs_per_s_median": round(float(np.median(rate[name])), 1), "quads_per_s_median": round(float(np.median(rate[name])) * n, 1), "frames": "device",
+                              "output": "pinned" if pinned(name) else "device"}), flush=True)
     for rect in rects.values():
         rect.close()
-    for q in ptrs + [dframe]:
-        L.rd_device_free(q)
+    bl.free(ptrs + [dframe])
     for q in pins:
         L.rd_host_free(q)
 
@@ -187,102 +107,29 @@ def child_rates(iw, ih, p, m, rounds, trace_only):
 def step_kernels(a, timeout):
     """the rates child under the tracer: the JSON lines as text, or None where there is no tracer.  The code kernel's launches come in the order of the
     configurations, 100 each: the trace is cut into those runs"""
-    if not shutil.which("rocprofv3"):
-        print("bench_code: rocprofv3 is not installed - the kernels step is left out", file=sys.stderr)
+    cmd = [sys.executable, os.path.abspath(__file__), "--child", "trace", "--size", a.size, "--patch", str(a.patch), "--oversample", str(a.oversample)]
+    durations = bl.kernel_trace("bench_code", cmd, timeout, lambda name: "k_code" in name or "k_grade" in name or "k_rectify_tensor" in name)
+    if durations is None:
         return None
+    code = [v for short in list(durations) if "k_code" in short for v in durations.pop(short)]
+    if len(code) != 100 * len(NDICTS):
+        print("bench_code: %d launches of the code kernel in the trace, expected %d - not cut into configurations" % (len(code), 100 * len(NDICTS)), file=sys.stderr)
+        return None
+    for i, nd in enumerate(NDICTS):
+        durations["k_code ndict %d" % nd] = code[100 * i:100 * (i + 1)]
     lines = []
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "-f", "csv", "-d", d, "-o", "k", "--", sys.executable, os.path.abspath(__file__), "--child", "trace", "--size", a.size, "--patch", str(a.patch),
-               "--oversample", str(a.oversample)]
-        rc, _, err = run_step(cmd, timeout, capture_stderr=True)
-        if rc != 0:
-            sys.stderr.write(err.decode()[-2000:])
-            raise subprocess.CalledProcessError(rc, cmd)
-        rows = []
-        for path in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
-            rows += list(csv.DictReader(open(path)))
-        rows.sort(key=lambda row: int(row["Start_Timestamp"]))
-        durations = {}
-        ncode = 0
-        for row in rows:
-            name = row["Kernel_Name"]
-            if "k_code" in name:
-                key = "k_code ndict %d" % NDICTS[min(ncode // 100, len(NDICTS) - 1)]
-                ncode += 1
-            elif "k_grade" in name or "k_rectify_tensor" in name:
-                key = name[name.index("k_"):].split("(")[0]
-            else:
-                continue
-            durations.setdefault(key, []).append((int(row["End_Timestamp"]) - int(row["Start_Timestamp"])) / 1000.0)
-        if ncode != 100 * len(NDICTS):
-            print("bench_code: %d launches of the code kernel in the trace, expected %d - not cut into configurations" % (ncode, 100 * len(NDICTS)), file=sys.stderr)
-            return None
-        for key in sorted(durations):
-            v = durations[key]
-            lines.append(json.dumps({"step": "kernels", "kernel": key, "size": a.size, "patch": "%dx%d" % (a.patch, a.patch), "oversample": a.oversample, "launches": len(v),
-                                     "kernel_us_median": round(float(np.median(v)), 2), "kernel_us_min": round(min(v), 2), "kernel_us_max": round(max(v), 2)}))
+    for key in sorted(durations):
+        lines.append(json.dumps({"step": "kernels", "kernel": key, "size": a.size, "patch": "%dx%d" % (a.patch, a.patch), "oversample": a.oversample, **bl.kernel_fields(durations[key])}))
     return "".join(line + "\n" for line in lines)
 
 
 def child_loop(iw, ih, p, m, nslots, pattern):
-    import rectdetect_amd as ra
-    if not ra.gpu_available():
-        raise SystemExit("bench_code: no HIP device - nothing is measured without one")
-    L = ra.lib()
-    imgs = synth_frames(iw, ih, 16)
-    dptrs = []
-    for a in imgs:
-        q = L.rd_device_alloc(a.nbytes)
-        L.rd_upload(q, a.ctypes.data, a.nbytes)
-        dptrs.append(q)
-    frames, warmup, maxq = 1024 if iw * ih <= 1920 * 1080 else 256, 128, 64
-    rects = {"code-d1024": ra.Rectifier(p, p, max_quads=maxq, njobs=NJOBS, code=code_spec(m), dictionary=dictionary(1024))}
-    outs = [L.rd_device_alloc(maxq * max(r.patch_bytes for r in rects.values())) for _ in range(NJOBS)]
-
-    def run(det, n, which, tally):
-        inflight = jobs = 0
-        rect = rects.get(which)
-
-        def poll():
-            nonlocal jobs
-            found = det.poll(TAN36)
-            tally[0] += len(found)
-            if rect is not None:
-                if jobs == NJOBS:
-                    rect.wait()
-                    jobs -= 1
-                det.rectify_polled(rect, ra.rect_quads(found[:maxq]), outs[tally[1] % NJOBS])
-                tally[1] += 1
-                tally[2] += min(len(found), maxq)
-                jobs += 1
-
-        for i in range(n):
-            if inflight == nslots:
-                poll()
-                inflight -= 1
-            det.enqueue(dptrs[i % len(dptrs)], iw * 3, on_device=True)
-            inflight += 1
-        while inflight:
-            poll()
-            inflight -= 1
-        while jobs:
-            rect.wait()
-            jobs -= 1
-
-    for r, which in enumerate(pattern):
-        det = ra.Detector(iw, ih, nslots=nslots, nworkers=1, aperture=TAN36)
-        run(det, warmup, which, [0, 0, 0])
-        tally = [0, 0, 0]
-        t = time.perf_counter()
-        run(det, frames, which, tally)      # (ends with every frame polled and every job waited for)
-        dt = time.perf_counter() - t
-        det.close()
+    ra = bl.require_gpu("bench_code")
+    rects = {"code-d1024": ra.Rectifier(p, p, max_quads=64, njobs=NJOBS, code=code_spec(m), dictionary=dictionary(1024))}
+    for r, which, frames, dt, tally in bl.rectify_polled_runs(iw, ih, nslots, pattern, rects):
         print(json.dumps({"step": "loop", "size": "%dx%d" % (iw, ih), "patch": "%dx%d" % (p, p), "oversample": m, "nslots": nslots, "rectify_polled": which, "run": r, "first_detector_of_process": r == 0,
                           "frames": frames, "frames_per_s": round(frames / dt, 1), "rectangles": tally[0], "quads_per_s": round(tally[2] / dt, 1), "frames_kind": "device", "output": "device"}), flush=True)
-    for rect in rects.values():
-        rect.close()
-    for q in outs + dptrs:
-        L.rd_device_free(q)
+    rects["code-d1024"].close()
 
 
 def main():
@@ -295,7 +142,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5, help="rounds of the alternating configurations in the rates step")
     ap.add_argument("--repeat", type=int, default=2, help="rounds of (none, code-d1024) in the loop step")
     ap.add_argument("--timeout", type=int, default=240, help="seconds allowed per GPU step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "code_bench.jsonl"))
+    ap.add_argument("--out", default=os.path.join(bl.ROOT, "profiles", "code_bench.jsonl"))
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     iw, ih = (int(v) for v in a.size.split("x"))
@@ -307,33 +154,9 @@ def main():
         else:
             child_loop(iw, ih, a.patch, a.oversample, a.nslots, ["none", "code-d1024"] * a.repeat)
         return 0
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    for step in a.steps.split(","):
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", step, "--size", a.size, "--patch", str(a.patch), "--oversample", str(a.oversample), "--nslots", str(a.nslots), "--rounds", str(a.rounds),
-               "--repeat", str(a.repeat)]
-        try:
-            if step == "kernels":
-                text = step_kernels(a, a.timeout)
-                if text is None:
-                    continue
-            else:
-                rc, out, _ = run_step(cmd, a.timeout)
-                text = out.decode()
-                if rc != 0:
-                    sys.stdout.write(text)
-                    print("bench_code: step %s failed with status %d - stopping" % (step, rc), file=sys.stderr)
-                    return rc if rc > 0 else 1
-        except subprocess.TimeoutExpired:
-            print("bench_code: step %s ran into its time limit of %d s - stopping" % (step, a.timeout), file=sys.stderr)
-            return 124
-        except subprocess.CalledProcessError as e:
-            print("bench_code: step %s failed with status %d - stopping" % (step, e.returncode), file=sys.stderr)
-            return e.returncode if e.returncode > 0 else 1
-        sys.stdout.write(text)
-        sys.stdout.flush()
-        with open(a.out, "a") as f:
-            f.write(text)
-    return 0
+    cmd = lambda step: [sys.executable, os.path.abspath(__file__), "--child", step, "--size", a.size, "--patch", str(a.patch), "--oversample", str(a.oversample), "--nslots", str(a.nslots),
+                        "--rounds", str(a.rounds), "--repeat", str(a.repeat)]
+    return bl.drive("bench_code", a.steps.split(","), cmd, a.out, a.timeout, traced={"kernels": lambda timeout: step_kernels(a, timeout)})
 
 
 if __name__ == "__main__":

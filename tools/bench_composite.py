@@ -19,17 +19,13 @@ Every GPU step is a child process under a time limit of its own; the tool stops 
 import argparse
 import json
 import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+from tools import benchlib as bl
+from tools.benchlib import TAN36
 
-from tools.bench_rectify import random_quads, synth_frames
-
-TAN36 = float(np.tan(36.0 / 180.0 * np.pi))
 NJOBS = 4
 IW, IH = 1920, 1080
 P = 128
@@ -38,43 +34,18 @@ PROBE_MODES = ("composite_empty", "composite_cached")      # --pattern only: whe
 
 
 def timed_jobs(comp, job, label, extra):
-    for k in range(64):      # warm-up
-        job(k)
-        comp.wait()
-    lat = []
-    for k in range(300):
-        t = time.perf_counter()
-        job(k)
-        comp.wait()
-        lat.append(time.perf_counter() - t)
     n = 4000
-    t = time.perf_counter()
-    inflight = 0
-    for k in range(n):
-        if inflight == NJOBS:
-            comp.wait()
-            inflight -= 1
-        job(k)
-        inflight += 1
-    while inflight:
-        comp.wait()
-        inflight -= 1
-    dt = time.perf_counter() - t
-    lat = np.sort(np.array(lat)) * 1e6
+    lat, dt = bl.timed_jobs(job, lambda k: comp.wait(), NJOBS, 64, 300, n)
     print(json.dumps(dict({"step": "jobs", "job": label, "size": "%dx%d" % (IW, IH), "jobs_in_flight": NJOBS, "jobs": n, "us_per_job_in_flight": round(dt / n * 1e6, 2),
-                           "job_latency_us_median": round(float(lat[len(lat) // 2]), 1), "job_latency_us_p10": round(float(lat[len(lat) // 10]), 1),
-                           "job_latency_us_p90": round(float(lat[len(lat) * 9 // 10]), 1)}, **extra)), flush=True)
+                           **bl.latency_fields(lat)}, **extra)), flush=True)
 
 
 def child_jobs(kinds):
     import rectdetect_amd as ra
     from tests import pixfmt
     L = ra.lib()
-    frame = synth_frames(IW, IH, 1)[0]
-    det = ra.Detector(IW, IH, nslots=1, aperture=TAN36)
-    det.enqueue(frame)
-    quads = ra.rect_quads(det.poll(TAN36))
-    det.close()
+    frame = bl.synth_frames(IW, IH, 1)[0]
+    quads = bl.own_quads(frame)
     if len(quads) == 0:
         raise SystemExit("bench_composite: the synthetic frame has no rectangle")
     n = len(quads)
@@ -83,16 +54,12 @@ def child_jobs(kinds):
     tiles = len(ra.composite_tiles(fills, IW, IH))
     comp = ra.Compositor(P, P, max_items=n, njobs=NJOBS)
     patches = np.random.default_rng(1).integers(0, 256, (n, P, P, 3), dtype=np.uint8)
-    dpatches = L.rd_device_alloc(patches.nbytes)
-    L.rd_upload(dpatches, patches.ctypes.data, patches.nbytes)
-    dframe, dout = L.rd_device_alloc(frame.nbytes), L.rd_device_alloc(frame.nbytes)
-    L.rd_upload(dframe, frame.ctypes.data, frame.nbytes)
+    dpatches, dframe = bl.upload([patches, frame])
+    dout = L.rd_device_alloc(frame.nbytes)
     (y, uv), _ = pixfmt.convert(frame, ra.PIX_NV12)
     y, uv = np.ascontiguousarray(y), np.ascontiguousarray(uv)
-    src = [L.rd_device_alloc(y.nbytes), L.rd_device_alloc(uv.nbytes)]
+    src = bl.upload([y, uv])
     dst = [L.rd_device_alloc(y.nbytes), L.rd_device_alloc(uv.nbytes)]
-    L.rd_upload(src[0], y.ctypes.data, y.nbytes)
-    L.rd_upload(src[1], uv.ctypes.data, uv.nbytes)
     for what, items, pk in (("fills", fills, {}), ("pastes of 128x128 patches", pastes, {"patches": (dpatches, n), "patches_on_device": True})):
         if what.split()[0] not in kinds:
             continue
@@ -106,8 +73,7 @@ def child_jobs(kinds):
         timed_jobs(comp, lambda k: comp.enqueue(ra.PIX_NV12, src, (IW, IW), IW, IH, items, out_planes=dst, out_pitches=(IW, IW), on_device=True, **pk),
                    "b: %s, NV12 device to device" % what, dict(extra, format="NV12", frames="device to device"))
     comp.close()
-    for q in [dframe, dout, dpatches] + src + dst:
-        L.rd_device_free(q)
+    bl.free([dframe, dout, dpatches] + src + dst)
 
 
 def child_loop(nslots, pattern):
@@ -116,14 +82,10 @@ def child_loop(nslots, pattern):
     # a pool with a device frame of its own for EVERY frame of a run (16 images in turn, 7 GB): in place each frame is written into once, after its detection, and
     # never detected again, so the detector's work is the same in all four modes; and no frame in flight is ever written into
     frames, warmup = 1024, 128
-    base = synth_frames(IW, IH, 16)
+    base = bl.synth_frames(IW, IH, 16)
     imgs = [base[k % 16] for k in range(frames + warmup)]
-    dptrs = []
-    for a in imgs:
-        q = L.rd_device_alloc(a.nbytes)
-        L.rd_upload(q, a.ctypes.data, a.nbytes)
-        dptrs.append(q)
-    quads = random_quads(IW, IH, 32)
+    dptrs = bl.upload(imgs)
+    quads = bl.random_quads(IW, IH, 32)
     outs = [L.rd_device_alloc(32 * P * P * 3) for _ in range(NJOBS)]
     rect = ra.Rectifier(P, P, max_quads=32, njobs=NJOBS)
     an = ra.Annotator(max_prims=1024, njobs=NJOBS)
@@ -131,60 +93,30 @@ def child_loop(nslots, pattern):
     workers = {"rectify": rect, "annotate": an, "composite": comp, "composite_empty": comp, "composite_cached": comp}
     cache = {}      # composite_cached: the items of image k % 16 (the stream is the same 16 images in turn, and their rectangles the same every time)
 
-    def run(det, first, n, mode, tally):
-        inflight = jobs = 0
-        worker = workers.get(mode)
-        polled = first
+    def enqueue(det, i):
+        det.enqueue(dptrs[i], IW * 3, on_device=True)
 
-        def poll():
-            nonlocal jobs, polled
-            rects = det.poll(TAN36)
-            tally[0] += len(rects)
-            image = polled % 16
-            polled += 1
-            if mode == "none":
-                return
-            if jobs == NJOBS:
-                worker.wait()
-                jobs -= 1
+    def run(det, mode, timed, tally):
+        def behind(det, worker, rects, i, k):
             if mode == "rectify":
-                det.rectify_polled(rect, quads, outs[tally[1] % NJOBS])
-            elif mode == "annotate":
+                det.rectify_polled(rect, quads, outs[k % NJOBS])
+                return 0
+            if mode == "annotate":
                 prims = ra.annot_rects(rects[:170])
-                tally[2] += len(prims)
                 det.annotate_polled(an, prims)
+                return len(prims)
+            image = i % 16
+            if mode == "composite_cached" and image in cache:
+                items = cache[image]
             else:
-                if mode == "composite_cached" and image in cache:
-                    items = cache[image]
-                else:
-                    items = ra.comp_items(ra.rect_quads(rects[:256]), colour=(16, 16, 16))
-                    cache.setdefault(image, items)
-                tally[2] += len(items)
-                det.composite_polled(comp, items[:0] if mode == "composite_empty" else items)
-            tally[1] += 1
-            jobs += 1
+                items = ra.comp_items(ra.rect_quads(rects[:256]), colour=(16, 16, 16))
+                cache.setdefault(image, items)
+            det.composite_polled(comp, items[:0] if mode == "composite_empty" else items)
+            return len(items)
 
-        for i in range(n):
-            if inflight == nslots:
-                poll()
-                inflight -= 1
-            det.enqueue(dptrs[first + i], IW * 3, on_device=True)
-            inflight += 1
-        while inflight:
-            poll()
-            inflight -= 1
-        while jobs:
-            worker.wait()
-            jobs -= 1
+        bl.detector_loop(det, frames if timed else warmup, nslots, enqueue, tally, first=warmup if timed else 0, worker=workers.get(mode), njobs=NJOBS, behind=behind)
 
-    for r, mode in enumerate(pattern):
-        det = ra.Detector(IW, IH, nslots=nslots, nworkers=1, aperture=TAN36)
-        run(det, 0, warmup, mode, [0, 0, 0])
-        tally = [0, 0, 0]
-        t = time.perf_counter()
-        run(det, warmup, frames, mode, tally)      # (ends with every frame polled and every job waited for)
-        dt = time.perf_counter() - t
-        det.close()
+    for r, mode, dt, tally in bl.detector_runs(pattern, lambda: ra.Detector(IW, IH, nslots=nslots, nworkers=1, aperture=TAN36), run):
         if mode in ("annotate", "composite", "composite_cached"):      # (the next run starts from the pool as it was uploaded)
             for q, a in zip(dptrs, imgs):
                 L.rd_upload(q, a.ctypes.data, a.nbytes)
@@ -193,8 +125,7 @@ def child_loop(nslots, pattern):
     rect.close()
     an.close()
     comp.close()
-    for q in outs + dptrs:
-        L.rd_device_free(q)
+    bl.free(outs + dptrs)
 
 
 def main():
@@ -205,14 +136,12 @@ def main():
     ap.add_argument("--pattern", default=None, help="the loop step's runs in one process, e.g. none,none,composite (default: all four --repeat times)")
     ap.add_argument("--kinds", default="fills,pastes", help="the jobs step's item kinds (a kernel trace of one kind: --child jobs --kinds fills)")
     ap.add_argument("--timeout", type=int, default=300, help="seconds allowed per GPU step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "composite_bench.jsonl"))
+    ap.add_argument("--out", default=os.path.join(bl.ROOT, "profiles", "composite_bench.jsonl"))
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     pattern = a.pattern or ",".join([",".join(LOOP_MODES)] * a.repeat)
     if a.child:
-        import rectdetect_amd as ra
-        if not ra.gpu_available():
-            raise SystemExit("bench_composite: no HIP device - nothing is measured without one")
+        bl.require_gpu("bench_composite")
         if a.child == "jobs":
             child_jobs(a.kinds.split(","))
         else:
@@ -221,23 +150,8 @@ def main():
                 raise SystemExit("bench_composite: --pattern takes %s" % ", ".join(LOOP_MODES + PROBE_MODES))
             child_loop(a.nslots, modes)
         return 0
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    for step in a.steps.split(","):
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", step, "--nslots", str(a.nslots), "--pattern", pattern, "--kinds", a.kinds]
-        try:
-            res = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=a.timeout)
-        except subprocess.TimeoutExpired:
-            print("bench_composite: step %s ran into its time limit of %d s - stopping" % (step, a.timeout), file=sys.stderr)
-            return 124
-        text = res.stdout.decode()
-        sys.stdout.write(text)
-        sys.stdout.flush()
-        if res.returncode != 0:
-            print("bench_composite: step %s failed with status %d - stopping" % (step, res.returncode), file=sys.stderr)
-            return res.returncode if res.returncode > 0 else 1
-        with open(a.out, "a") as f:
-            f.write(text)
-    return 0
+    cmd = lambda step: [sys.executable, os.path.abspath(__file__), "--child", step, "--nslots", str(a.nslots), "--pattern", pattern, "--kinds", a.kinds]
+    return bl.drive("bench_composite", a.steps.split(","), cmd, a.out, a.timeout)
 
 
 if __name__ == "__main__":

@@ -17,24 +17,14 @@ import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import rectdetect_amd as ra
+from tools.benchlib import synth_frames
 from tests import pixfmt
 
 TAN36 = float(np.tan(36.0 / 180.0 * np.pi))
 FMT = {v: k for k, v in ra.PIX_NAMES.items()}
-
-
-def synth_frames(iw, ih, n):
-    """n distinct frames of the synthetic stream (C generator), seed 0x5EED0000, as they come"""
-    out = []
-    for t in range(n):
-        a = np.empty((ih, iw, 3), np.uint8)
-        ra.lib().rd_synth_frame(a.ctypes.data, iw, ih, iw * 3, 0x5EED0000, t, 1)
-        out.append(a)
-    return out
 
 
 def same_content(img, fmt):

@@ -17,17 +17,13 @@ Every GPU step is a child process under a time limit of its own; the tool stops 
 import argparse
 import json
 import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+from tools import benchlib as bl
+from tools.benchlib import TAN36
 
-from tools.bench_rectify import synth_frames
-
-TAN36 = float(np.tan(36.0 / 180.0 * np.pi))
 NJOBS = 4
 IW, IH = 1920, 1080
 G, M = 32, 4
@@ -42,47 +38,21 @@ def library(matcher, T):
 
 
 def timed_jobs(service, job, label, extra, rep):
-    for k in range(64):      # warm-up
-        job(k)
-        service.wait()
-    lat = []
-    for k in range(300):
-        t = time.perf_counter()
-        job(k)
-        service.wait()
-        lat.append(time.perf_counter() - t)
     n = 2000
-    t = time.perf_counter()
-    inflight = 0
-    for k in range(n):
-        if inflight == NJOBS:
-            service.wait()
-            inflight -= 1
-        job(k)
-        inflight += 1
-    while inflight:
-        service.wait()
-        inflight -= 1
-    dt = time.perf_counter() - t
-    lat = np.sort(np.array(lat)) * 1e6
+    lat, dt = bl.timed_jobs(job, lambda k: service.wait(), NJOBS, 64, 300, n)
     print(json.dumps(dict({"step": "jobs", "job": label, "repeat": rep, "size": "%dx%d" % (IW, IH), "jobs_in_flight": NJOBS, "jobs": n, "us_per_job_in_flight": round(dt / n * 1e6, 2),
-                           "job_latency_us_median": round(float(lat[len(lat) // 2]), 1), "job_latency_us_p10": round(float(lat[len(lat) // 10]), 1),
-                           "job_latency_us_p90": round(float(lat[len(lat) * 9 // 10]), 1)}, **extra)), flush=True)
+                           **bl.latency_fields(lat)}, **extra)), flush=True)
 
 
 def child_jobs(repeat):
     import rectdetect_amd as ra
     L = ra.lib()
-    frame = synth_frames(IW, IH, 1)[0]
-    det = ra.Detector(IW, IH, nslots=1, aperture=TAN36)
-    det.enqueue(frame)
-    quads = ra.rect_quads(det.poll(TAN36))
-    det.close()
+    frame = bl.synth_frames(IW, IH, 1)[0]
+    quads = bl.own_quads(frame)
     if len(quads) == 0:
         raise SystemExit("bench_match: the synthetic frame has no rectangle")
     n = len(quads)
-    dframe = L.rd_device_alloc(frame.nbytes)
-    L.rd_upload(dframe, frame.ctypes.data, frame.nbytes)
+    dframe = bl.upload([frame])[0]
     dout = L.rd_device_alloc(n * P * P * 3)
     matchers = {}
     for T in (16, 1024):
@@ -99,76 +69,41 @@ def child_jobs(repeat):
     for mt in matchers.values():
         mt.close()
     rect.close()
-    L.rd_device_free(dframe)
-    L.rd_device_free(dout)
+    bl.free([dframe, dout])
 
 
 def child_loop(nslots, pattern):
     import rectdetect_amd as ra
     L = ra.lib()
     frames, warmup = 1024, 128
-    base = synth_frames(IW, IH, 16)
-    dptrs = []
-    for a in base:
-        q = L.rd_device_alloc(a.nbytes)
-        L.rd_upload(q, a.ctypes.data, a.nbytes)
-        dptrs.append(q)
+    dptrs = bl.upload(bl.synth_frames(IW, IH, 16))
     outs = [L.rd_device_alloc(64 * P * P * 3) for _ in range(NJOBS)]
     rect = ra.Rectifier(P, P, max_quads=64, njobs=NJOBS)
     mt = ra.Matcher(G, M, max_templates=16, max_quads=64, njobs=NJOBS)
     library(mt, 16)
     workers = {"rectify": rect, "match": mt}
 
-    def run(det, first, n, mode, tally):
-        inflight = jobs = 0
-        worker = workers.get(mode)
+    def enqueue(det, i):
+        det.enqueue(dptrs[i % 16], IW * 3, on_device=True)
 
-        def poll():
-            nonlocal jobs
-            rects = det.poll(TAN36)
-            tally[0] += len(rects)
-            if mode == "none":
-                return
-            if jobs == NJOBS:
-                worker.wait()
-                jobs -= 1
+    def run(det, mode, timed, tally):
+        def behind(det, worker, rects, i, k):
             quads = ra.rect_quads(rects[:64])
-            tally[2] += len(quads)
             if mode == "rectify":
-                det.rectify_polled(rect, quads, outs[tally[1] % NJOBS])
+                det.rectify_polled(rect, quads, outs[k % NJOBS])
             else:
                 det.match_polled(mt, quads)
-            tally[1] += 1
-            jobs += 1
+            return len(quads)
 
-        for i in range(n):
-            if inflight == nslots:
-                poll()
-                inflight -= 1
-            det.enqueue(dptrs[(first + i) % 16], IW * 3, on_device=True)
-            inflight += 1
-        while inflight:
-            poll()
-            inflight -= 1
-        while jobs:
-            worker.wait()
-            jobs -= 1
+        bl.detector_loop(det, frames if timed else warmup, nslots, enqueue, tally, first=warmup if timed else 0, worker=workers.get(mode), njobs=NJOBS, behind=behind)
 
-    for r, mode in enumerate(pattern):
-        det = ra.Detector(IW, IH, nslots=nslots, nworkers=1, aperture=TAN36)
-        run(det, 0, warmup, mode, [0, 0, 0])
-        tally = [0, 0, 0]
-        t = time.perf_counter()
-        run(det, warmup, frames, mode, tally)      # (ends with every frame polled and every job waited for)
-        dt = time.perf_counter() - t
-        det.close()
+    for r, mode, dt, tally in bl.detector_runs(pattern, lambda: ra.Detector(IW, IH, nslots=nslots, nworkers=1, aperture=TAN36), run):
         print(json.dumps({"step": "loop", "size": "%dx%d" % (IW, IH), "nslots": nslots, "behind_the_poll": mode, "run": r, "first_detector_of_process": r == 0, "frames": frames,
                           "frames_per_s": round(frames / dt, 1), "rectangles": tally[0], "quads_per_frame": round(tally[2] / frames, 1), "templates": 16, "grid": G, "oversample": M,
                           "frames_kind": "device"}), flush=True)
     rect.close()
     mt.close()
-    for q in outs + dptrs:
-        L.rd_device_free(q)
+    bl.free(outs + dptrs)
 
 
 def main():
@@ -177,35 +112,18 @@ def main():
     ap.add_argument("--nslots", type=int, default=64)
     ap.add_argument("--repeat", type=int, default=2, help="rounds of the alternating runs in either step")
     ap.add_argument("--timeout", type=int, default=300, help="seconds allowed per GPU step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "match_bench.jsonl"))
+    ap.add_argument("--out", default=os.path.join(bl.ROOT, "profiles", "match_bench.jsonl"))
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.child:
-        import rectdetect_amd as ra
-        if not ra.gpu_available():
-            raise SystemExit("bench_match: no HIP device - nothing is measured without one")
+        bl.require_gpu("bench_match")
         if a.child == "jobs":
             child_jobs(a.repeat)
         else:
             child_loop(a.nslots, list(LOOP_MODES) * a.repeat)
         return 0
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    for step in a.steps.split(","):
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", step, "--nslots", str(a.nslots), "--repeat", str(a.repeat)]
-        try:
-            res = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=a.timeout)
-        except subprocess.TimeoutExpired:
-            print("bench_match: step %s ran into its time limit of %d s - stopping" % (step, a.timeout), file=sys.stderr)
-            return 124
-        text = res.stdout.decode()
-        sys.stdout.write(text)
-        sys.stdout.flush()
-        if res.returncode != 0:
-            print("bench_match: step %s failed with status %d - stopping" % (step, res.returncode), file=sys.stderr)
-            return res.returncode if res.returncode > 0 else 1
-        with open(a.out, "a") as f:
-            f.write(text)
-    return 0
+    cmd = lambda step: [sys.executable, os.path.abspath(__file__), "--child", step, "--nslots", str(a.nslots), "--repeat", str(a.repeat)]
+    return bl.drive("bench_match", a.steps.split(","), cmd, a.out, a.timeout)
 
 
 if __name__ == "__main__":

@@ -12,21 +12,10 @@ import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import rectdetect_amd as ra
-
-
-def synth_frames(iw, ih, n):
-    """n distinct frames of the synthetic stream (C generator), seed 0x5EED0000"""
-    L = ra.lib()
-    out = []
-    for t in range(n):
-        a = np.empty((ih, iw, 3), np.uint8)
-        L.rd_synth_frame(a.ctypes.data, iw, ih, iw * 3, 0x5EED0000, t, 1)
-        out.append(a)
-    return out
+from tools.benchlib import synth_frames
 
 
 def measure(iw, ih, where, nslots, frames, warmup, distinct=16):

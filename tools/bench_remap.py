@@ -12,7 +12,8 @@ At 1920x1080 -> 1920x1080 with k1 = -0.1 (fx = fy = 1000, the principal point at
                (--njobs jobs in flight, the remap of the frames ahead running while the host polls), next to the same loop fed the SAME remapped frames made
                beforehand; the two alternate --repeat times in one process, a new detector per run.  The first detector of a process runs faster than every
                later one ("Rectified patches"): compare runs 1 and later.
-Every GPU step is a child process under a time limit of its own; the tool stops at the first one that fails.  bench.py is not involved.
+Every GPU step is a child process in a process group of its own under a time limit of its own, at which the whole group is killed (the tracer's child too); the tool
+stops at the first step that fails.  bench.py is not involved.
 
     python tools/bench_remap.py [--steps latency,kernel,loop] [--repeat R] [--njobs J] [--out FILE] [--trace-dir DIR]
 """
@@ -26,9 +27,9 @@ import sys
 import tempfile
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+from tools import benchlib as bl
 
 IW, IH = 1920, 1080
 PITCH = IW * 3
@@ -40,16 +41,6 @@ def cameras():
     import rectdetect_amd as ra
     lens = ra.lens(F, F, (IW - 1) / 2, (IH - 1) / 2, k1=K1)
     return lens, ra.view(F, F, (IW - 1) / 2, (IH - 1) / 2)
-
-
-def synth_frames(n):
-    import rectdetect_amd as ra
-    out = []
-    for t in range(n):
-        a = np.empty((IH, IW, 3), np.uint8)
-        ra.lib().rd_synth_frame(a.ctypes.data, IW, IH, IW * 3, 0x5EED0000, t, 1)
-        out.append(a)
-    return out
 
 
 def nv12_of(bgr):
@@ -79,7 +70,7 @@ class Work:
         import torch
         import rectdetect_amd as ra
         self.ra, self.torch = ra, torch
-        frame = synth_frames(1)[0]
+        frame = bl.synth_frames(IW, IH, 1)[0]
         y, uv = nv12_of(frame)
         dev = torch.device("cuda:0")
         self.bgr, self.y, self.uv = (torch.from_numpy(a).to(dev) for a in (frame, y, uv))
@@ -177,12 +168,7 @@ def child_loop(nslots, njobs, pattern):
     L = ra.lib()
     lens, view = cameras()
     tan_aov = ra.view_tan_aov(view, IW)
-    imgs = synth_frames(16)
-    srcs = []
-    for a in imgs:
-        q = L.rd_device_alloc(a.nbytes)
-        L.rd_upload(q, a.ctypes.data, a.nbytes)
-        srcs.append(q)
+    srcs = bl.upload(bl.synth_frames(IW, IH, 16))
     remapper = ra.Remapper(IW, IH, IW, IH, lens=lens, view=view, njobs=njobs)
     nout = nslots + njobs + 1      # a remapped frame stays until its poll returned, and njobs more are being made
     outs = [L.rd_device_alloc(IH * PITCH) for _ in range(nout)]
@@ -194,7 +180,8 @@ def child_loop(nslots, njobs, pattern):
         ready.append(o)
     frames, warmup = 1024, 128
 
-    def run(det, n, remap, tally):
+    def run(det, remap, timed, tally):
+        n = frames if timed else warmup
         inflight = 0
         feed = lambda i: remapper.enqueue(ra.PIX_BGR, (srcs[i % len(srcs)],), (PITCH,), True, outs[i % nout], PITCH)
         if remap:
@@ -214,20 +201,30 @@ def child_loop(nslots, njobs, pattern):
             tally[0] += len(det.poll(tan_aov))
             inflight -= 1
 
-    for r, remap in enumerate(pattern):
-        det = ra.Detector(IW, IH, nslots=nslots, nworkers=1, aperture=tan_aov)
-        run(det, warmup, remap, [0])
-        tally = [0]
-        t = time.perf_counter()
-        run(det, frames, remap, tally)
-        dt = time.perf_counter() - t
-        det.close()
+    for r, remap, dt, tally in bl.detector_runs(pattern, lambda: ra.Detector(IW, IH, nslots=nslots, nworkers=1, aperture=tan_aov), run):
         print(json.dumps({"step": "loop", "size": "%dx%d" % (IW, IH), "k1": K1, "nslots": nslots, "remap_ahead_of_every_enqueue": remap, "remap_jobs_in_flight": njobs if remap else 0, "run": r,
                           "first_detector_of_process": r == 0, "frames": frames, "frames_per_s": round(frames / dt, 1), "us_per_frame": round(dt / frames * 1e6, 2), "rectangles": tally[0],
                           "frames_kind": "device"}), flush=True)
     remapper.close()
-    for q in outs + srcs + ready:
-        L.rd_device_free(q)
+    bl.free(outs + srcs + ready)
+
+
+def step_kernel(a, cmd, timeout):
+    """the kernel child under the tracer, and from the tracer's database the duration of every launch: the JSON lines as text"""
+    if a.trace_dir is None:
+        a.trace_dir = tempfile.mkdtemp(prefix="remap_trace_")
+    os.makedirs(a.trace_dir, exist_ok=True)
+    cmd = ["rocprofv3", "--kernel-trace", "-d", a.trace_dir, "-o", "remap", "--"] + cmd
+    rc, out, _ = bl.run_step(cmd, timeout)
+    if rc != 0:
+        sys.stdout.write(out.decode())
+        raise subprocess.CalledProcessError(rc, cmd)
+    dbs = sorted(glob.glob(os.path.join(a.trace_dir, "**", "*.db"), recursive=True), key=os.path.getmtime)
+    if not dbs:
+        print("bench_remap: the kernel trace left no database under %s" % a.trace_dir, file=sys.stderr)
+        raise subprocess.CalledProcessError(1, cmd)
+    return "".join(json.dumps({"step": "kernel", "size": "%dx%d" % (IW, IH), "k1": K1, "kernel": name, "bytes_by_design": traffic_bytes() if "k_remap" in name else None,
+                               "duration": pct(v)}) + "\n" for name, v in sorted(kernel_stats(dbs[-1]).items()))
 
 
 def main():
@@ -238,19 +235,13 @@ def main():
     ap.add_argument("--repeat", type=int, default=3, help="rounds of (without, with) in the loop step")
     ap.add_argument("--pattern", default=None, help="the loop step's runs in one process as 0 (without) / 1 (with the remapper), e.g. 0,0,1,0 (default: 0,1 --repeat times)")
     ap.add_argument("--timeout", type=int, default=240, help="seconds allowed per GPU step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "remap_bench.jsonl"))
+    ap.add_argument("--out", default=os.path.join(bl.ROOT, "profiles", "remap_bench.jsonl"))
     ap.add_argument("--trace-dir", default=None, help="where the kernel step's trace goes (default: a new temporary directory)")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     pattern = a.pattern or ",".join(["0,1"] * a.repeat)
     if a.child:
-        if a.child in ("latency", "kernel"):
-            import torch      # before the library: one HIP runtime in the process
-            if not torch.cuda.is_available():
-                raise SystemExit("bench_remap: torch sees no HIP device - nothing is measured without one")
-        import rectdetect_amd as ra
-        if not ra.gpu_available():
-            raise SystemExit("bench_remap: no HIP device - nothing is measured without one")
+        bl.require_gpu("bench_remap", torch_first=a.child in ("latency", "kernel"))      # (torch before the library: one HIP runtime in the process)
         if a.child == "latency":
             child_latency(a.njobs)
         elif a.child == "kernel":
@@ -258,36 +249,8 @@ def main():
         else:
             child_loop(a.nslots, a.njobs, [v == "1" for v in pattern.split(",")])
         return 0
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    for step in a.steps.split(","):
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", step, "--nslots", str(a.nslots), "--njobs", str(a.njobs), "--pattern", pattern]
-        if step == "kernel":
-            if a.trace_dir is None:
-                a.trace_dir = tempfile.mkdtemp(prefix="remap_trace_")
-            os.makedirs(a.trace_dir, exist_ok=True)
-            cmd = ["rocprofv3", "--kernel-trace", "-d", a.trace_dir, "-o", "remap", "--"] + cmd
-        try:
-            res = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=a.timeout)
-        except subprocess.TimeoutExpired:
-            print("bench_remap: step %s ran into its time limit of %d s - stopping" % (step, a.timeout), file=sys.stderr)
-            return 124
-        text = res.stdout.decode()
-        if res.returncode != 0:
-            sys.stdout.write(text)
-            print("bench_remap: step %s failed with status %d - stopping" % (step, res.returncode), file=sys.stderr)
-            return res.returncode if res.returncode > 0 else 1
-        if step == "kernel":
-            dbs = sorted(glob.glob(os.path.join(a.trace_dir, "**", "*.db"), recursive=True), key=os.path.getmtime)
-            if not dbs:
-                print("bench_remap: the kernel trace left no database under %s - stopping" % a.trace_dir, file=sys.stderr)
-                return 1
-            text = "".join(json.dumps({"step": "kernel", "size": "%dx%d" % (IW, IH), "k1": K1, "kernel": name, "bytes_by_design": traffic_bytes() if "k_remap" in name else None,
-                                       "duration": pct(v)}) + "\n" for name, v in sorted(kernel_stats(dbs[-1]).items()))
-        sys.stdout.write(text)
-        sys.stdout.flush()
-        with open(a.out, "a") as f:
-            f.write(text)
-    return 0
+    cmd = lambda step: [sys.executable, os.path.abspath(__file__), "--child", step, "--nslots", str(a.nslots), "--njobs", str(a.njobs), "--pattern", pattern]
+    return bl.drive("bench_remap", a.steps.split(","), cmd, a.out, a.timeout, traced={"kernel": lambda timeout: step_kernel(a, cmd("kernel"), timeout)})
 
 
 if __name__ == "__main__":

@@ -22,10 +22,10 @@ import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import rectdetect_amd as ra
+from tools import benchlib
 from tests import pixfmt
 
 TAN36 = float(np.tan(36.0 / 180.0 * np.pi))
@@ -40,12 +40,7 @@ def half(a):
 
 def synth_frames(iw, ih, n):
     """n distinct frames of the synthetic stream (C generator), seed 0x5EED0000, and for each the BGR frame the conversion contract gives for its I420 planes"""
-    out = []
-    for t in range(n):
-        a = np.empty((ih, iw, 3), np.uint8)
-        ra.lib().rd_synth_frame(a.ctypes.data, iw, ih, iw * 3, 0x5EED0000, t, 1)
-        out.append((a, pixfmt.convert(a, ra.PIX_I420)[1]))
-    return out
+    return [(a, pixfmt.convert(a, ra.PIX_I420)[1]) for a in benchlib.synth_frames(iw, ih, n)]
 
 
 class Frames:

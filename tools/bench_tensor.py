@@ -20,38 +20,14 @@ Every GPU step is a child process under a time limit of its own; the tool stops 
 import argparse
 import json
 import os
-import subprocess
 import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+from tools import benchlib as bl
 
-TAN36 = float(np.tan(36.0 / 180.0 * np.pi))
 NJOBS = 4
 MEAN, STD = (123.675, 116.28, 103.53), (58.395, 57.12, 57.375)      # per OUTPUT channel (R, G, B), in 0 .. 255 units
-
-
-def synth_frames(iw, ih, n):
-    import rectdetect_amd as ra
-    out = []
-    for t in range(n):
-        a = np.empty((ih, iw, 3), np.uint8)
-        ra.lib().rd_synth_frame(a.ctypes.data, iw, ih, iw * 3, 0x5EED0000, t, 1)
-        out.append(a)
-    return out
-
-
-def own_quads(frame):
-    """the quads of the frame's own rectangles"""
-    import rectdetect_amd as ra
-    ih, iw = frame.shape[:2]
-    det = ra.Detector(iw, ih, nslots=1, aperture=TAN36)
-    det.enqueue(frame)
-    rects = det.poll(TAN36)
-    det.close()
-    return ra.rect_quads(rects)
 
 
 def spec_f16(m):
@@ -60,16 +36,11 @@ def spec_f16(m):
 
 
 def child_rates(iw, ih, p, rounds):
-    import torch      # before the library: one HIP runtime in the process
+    import torch      # (bl.require_gpu imported it before the library: one HIP runtime in the process)
     import rectdetect_amd as ra
     L = ra.lib()
-    frame = synth_frames(iw, ih, 1)[0]
-    quads = own_quads(frame)[:64]
+    frame, quads, dframe = bl.own_frame("bench_tensor", iw, ih, 64)
     n = len(quads)
-    if n == 0:
-        raise SystemExit("bench_tensor: the synthetic frame holds no rectangle")
-    dframe = L.rd_device_alloc(frame.nbytes)
-    L.rd_upload(dframe, frame.ctypes.data, frame.nbytes)
     mean = torch.tensor(MEAN, dtype=torch.float32, device="cuda").view(1, 3, 1, 1)
     std = torch.tensor(STD, dtype=torch.float32, device="cuda").view(1, 3, 1, 1)
     configs = {}
@@ -97,106 +68,26 @@ def child_rates(iw, ih, p, rounds):
             torch.cuda.synchronize()
             return t
 
-    lat = {name: [] for name in configs}
-    rate = {name: [] for name in configs}
-    for name in configs:      # warm-up
-        for k in range(32):
-            job(name, k)
-            finish(name, k)
-    for r in range(rounds):
-        for name in configs:
-            one = []
-            for k in range(100):
-                t = time.perf_counter()
-                job(name, k)
-                finish(name, k)
-                one.append(time.perf_counter() - t)
-            lat[name].append(float(np.median(one)) * 1e6)
-        for name in configs:
-            njobs_timed, inflight, first = 400, 0, 0
-            t = time.perf_counter()
-            for k in range(njobs_timed):
-                if inflight == NJOBS:
-                    finish(name, first)
-                    first += 1
-                    inflight -= 1
-                job(name, k)
-                inflight += 1
-            while inflight:
-                finish(name, first)
-                first += 1
-                inflight -= 1
-            rate[name].append(njobs_timed / (time.perf_counter() - t))
+    lat, rate = bl.alternating_rounds(configs, job, finish, rounds, NJOBS, (32, 100, 400))
     for name in configs:
         print(json.dumps({"step": "rates", "config": name, "size": "%dx%d" % (iw, ih), "patch": "%dx%d" % (p, p), "quads_per_job": n, "jobs_in_flight": NJOBS, "rounds": rounds,
-                          "job_latency_us_median": round(float(np.median(lat[name])), 1), "job_latency_us_min_round": round(min(lat[name]), 1), "job_latency_us_max_round": round(max(lat[name]), 1),
-                          "jobs_per_s_median": round(float(np.median(rate[name])), 1), "patches_per_s_median": round(float(np.median(rate[name])) * n, 1),
+                          **bl.round_fields(lat[name]), "jobs_per_s_median": round(float(np.median(rate[name])), 1), "patches_per_s_median": round(float(np.median(rate[name])) * n, 1),
                           "frames": "device", "output": "device"}), flush=True)
     for name, (rect, outs, ptrs) in configs.items():
         rect.close()
         if outs is None:
-            for q in ptrs:
-                L.rd_device_free(q)
-    L.rd_device_free(dframe)
+            bl.free(ptrs)
+    bl.free([dframe])
 
 
 def child_loop(iw, ih, p, nslots, pattern):
     import rectdetect_amd as ra
-    L = ra.lib()
-    imgs = synth_frames(iw, ih, 16)
-    dptrs = []
-    for a in imgs:
-        q = L.rd_device_alloc(a.nbytes)
-        L.rd_upload(q, a.ctypes.data, a.nbytes)
-        dptrs.append(q)
-    frames, warmup, maxq = 1024 if iw * ih <= 1920 * 1080 else 256, 128, 64
-    rects = {"u8": ra.Rectifier(p, p, max_quads=maxq, njobs=NJOBS), "f16": ra.Rectifier(p, p, max_quads=maxq, njobs=NJOBS, tensor=spec_f16(1))}
-    outs = [L.rd_device_alloc(maxq * max(r.patch_bytes for r in rects.values())) for _ in range(NJOBS)]
-
-    def run(det, n, which, tally):
-        inflight = jobs = 0
-        rect = rects.get(which)
-
-        def poll():
-            nonlocal jobs
-            found = det.poll(TAN36)
-            tally[0] += len(found)
-            if rect is not None:
-                if jobs == NJOBS:
-                    rect.wait()
-                    jobs -= 1
-                det.rectify_polled(rect, ra.rect_quads(found[:maxq]), outs[tally[1] % NJOBS])
-                tally[1] += 1
-                tally[2] += min(len(found), maxq)
-                jobs += 1
-
-        for i in range(n):
-            if inflight == nslots:
-                poll()
-                inflight -= 1
-            det.enqueue(dptrs[i % len(dptrs)], iw * 3, on_device=True)
-            inflight += 1
-        while inflight:
-            poll()
-            inflight -= 1
-        while jobs:
-            rect.wait()
-            jobs -= 1
-
-    for r, which in enumerate(pattern):
-        det = ra.Detector(iw, ih, nslots=nslots, nworkers=1, aperture=TAN36)
-        run(det, warmup, which, [0, 0, 0])
-        tally = [0, 0, 0]
-        t = time.perf_counter()
-        run(det, frames, which, tally)      # (ends with every frame polled and every job waited for)
-        dt = time.perf_counter() - t
-        det.close()
+    rects = {"u8": ra.Rectifier(p, p, max_quads=64, njobs=NJOBS), "f16": ra.Rectifier(p, p, max_quads=64, njobs=NJOBS, tensor=spec_f16(1))}
+    for r, which, frames, dt, tally in bl.rectify_polled_runs(iw, ih, nslots, pattern, rects):
         print(json.dumps({"step": "loop", "size": "%dx%d" % (iw, ih), "patch": "%dx%d" % (p, p), "nslots": nslots, "rectify_polled": which, "run": r, "first_detector_of_process": r == 0,
                           "frames": frames, "frames_per_s": round(frames / dt, 1), "rectangles": tally[0], "patches_per_s": round(tally[2] / dt, 1), "frames_kind": "device", "output": "device"}), flush=True)
     for rect in rects.values():
         rect.close()
-    for q in outs + dptrs:
-        L.rd_device_free(q)
 
 
 def main():
@@ -208,36 +99,19 @@ def main():
     ap.add_argument("--rounds", type=int, default=5, help="rounds of the alternating configurations in the rates step")
     ap.add_argument("--repeat", type=int, default=2, help="rounds of (none, u8, f16) in the loop step")
     ap.add_argument("--timeout", type=int, default=240, help="seconds allowed per GPU step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tensor_bench.jsonl"))
+    ap.add_argument("--out", default=os.path.join(bl.ROOT, "profiles", "tensor_bench.jsonl"))
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     iw, ih = (int(v) for v in a.size.split("x"))
     if a.child:
+        bl.require_gpu("bench_tensor", torch_first=a.child == "rates")
         if a.child == "rates":
             child_rates(iw, ih, a.patch, a.rounds)
         else:
-            import rectdetect_amd as ra
-            if not ra.gpu_available():
-                raise SystemExit("bench_tensor: no HIP device - nothing is measured without one")
             child_loop(iw, ih, a.patch, a.nslots, ["none", "u8", "f16"] * a.repeat)
         return 0
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    for step in a.steps.split(","):
-        cmd = [sys.executable, os.path.abspath(__file__), "--child", step, "--size", a.size, "--patch", str(a.patch), "--nslots", str(a.nslots), "--rounds", str(a.rounds), "--repeat", str(a.repeat)]
-        try:
-            res = subprocess.run(cmd, stdout=subprocess.PIPE, timeout=a.timeout)
-        except subprocess.TimeoutExpired:
-            print("bench_tensor: step %s ran into its time limit of %d s - stopping" % (step, a.timeout), file=sys.stderr)
-            return 124
-        text = res.stdout.decode()
-        sys.stdout.write(text)
-        sys.stdout.flush()
-        if res.returncode != 0:
-            print("bench_tensor: step %s failed with status %d - stopping" % (step, res.returncode), file=sys.stderr)
-            return res.returncode if res.returncode > 0 else 1
-        with open(a.out, "a") as f:
-            f.write(text)
-    return 0
+    cmd = lambda step: [sys.executable, os.path.abspath(__file__), "--child", step, "--size", a.size, "--patch", str(a.patch), "--nslots", str(a.nslots), "--rounds", str(a.rounds), "--repeat", str(a.repeat)]
+    return bl.drive("bench_tensor", a.steps.split(","), cmd, a.out, a.timeout)
 
 
 if __name__ == "__main__":
